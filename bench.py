@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Headline benchmark: query-points/sec, forward+backward(+Adam), IF-Net 128^3 grid x 50k points.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`ms_per_step` = wall time of the K timed
+steps / K).  --full adds everything else behind the timed region: the single-stream per-kernel steps (`roofline_kernels`),
+the stand-alone gather, the other backward arithmetics, forward only, the query path and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (loss, gradients, updated parameters and BatchNorm
+statistics) as DIR/<name>.npy.  Every step starts from the same state (_SameStart), so what a step computes is a function
+of the arguments alone.
 
 N = 1 runs in this process.  N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N` (RANK / WORLD_SIZE in the environment; WORLD_SIZE must equal N), or -- without a launcher
@@ -212,12 +219,48 @@ class _KernelTimer:
         return sum(v) / max(len(v), 1)
 
 
+class _SameStart:
+    """Puts the trainer back into the state it was created in before every step of the benchmark: parameters and BatchNorm
+    running statistics as loaded, Adam's moments and step counters zeroed in place (= the state Adam creates in its first
+    step).  Chained training steps on one batch would carry each step's float-atomic rounding into the next one's inputs
+    and compound it (27 chained steps: parameters ~1e-3 apart between two runs, gradients ~0.5 in L2); restored, every
+    step computes the same thing from the same inputs.  A few multi-tensor launches (~30 MB copied or zeroed on the
+    step's stream) in front of each step; the weight planes are re-made after it as after an optimizer step (they are
+    keyed by the parameters' versions)."""
+
+    STATE_BUFFERS = ("running_mean", "running_var", "num_batches_tracked")
+
+    def __init__(self, module, optimizer):
+        import torch
+        self.torch = torch
+        self.optimizer = optimizer
+        live = list(module.parameters()) + [b for n, b in module.named_buffers() if n.endswith(self.STATE_BUFFERS)]
+        self.groups = {}                         # dtype -> (live tensors, their initial values)
+        for t in live:
+            g = self.groups.setdefault(t.dtype, ([], []))
+            g[0].append(t)
+            g[1].append(t.detach().clone())
+
+    def __call__(self):
+        torch = self.torch
+        with torch.no_grad():
+            for dst, src in self.groups.values():
+                torch._foreach_copy_(dst, src)
+            moments = {}
+            for st in self.optimizer.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        moments.setdefault(v.dtype, []).append(v)
+            for ts in moments.values():
+                torch._foreach_zero_(ts)
+
+
 def _conv_key(op, x, co, ci):
     B, D, H, W = x.shape[0], x.shape[1], x.shape[2], x.shape[3]
     return f"{op}:{B}x{D}x{H}x{W}:{ci}->{co}"
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -242,7 +285,22 @@ def main():
                          "without the split")
     ap.add_argument("--dist", choices=["uniform", "surface"], default="uniform",
                     help="query-point distribution; uniform (default) is the reported worst case")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements behind the timed region (per-kernel single-stream steps, stand-alone gather, "
+                         "other backward arithmetics, forward only, query path, CPU baseline); the --no-* options still apply")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, gradients, updated parameters, BatchNorm statistics) "
+                         "as DIR/<name>.npy in float32")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.no_cpu_baseline = a.no_fwd_only = a.no_query = a.no_diag = a.no_f32_backward = True
+    return a
+
+
+def main():
+    a = parse_args()
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ     # under torch.distributed.run
     if a.gpus > 1 and not launched:
@@ -286,6 +344,11 @@ def main():
     opt = torch.optim.Adam(trainer.ifnet.parameters(), lr=trainer.hparams.lr, fused=True)
     dp = DataParallelTrainer(trainer, optimizer=opt)
     batch = synth_batch(103 + rank, a.batch, a.grid, a.points, dev, a.dist)
+    same_start = _SameStart(trainer, opt)
+
+    def step():
+        same_start()
+        return dp.step(batch)
 
     def sync():
         if launched:
@@ -296,12 +359,12 @@ def main():
     # scatter form is decided from the statistics of the step PULL_DECISION_LAG (3) steps back (ifnet.SCATTER_FORM "auto")
     # -- SETUP_STEPS + the W warm-up steps of the contract run before the timed region
     for _ in range(SETUP_STEPS):
-        dp.step(batch)
+        step()
     sync()
     gc.collect()      # (see below: in FRONT of the warm-up steps, so that the GPU does not sit idle for the ~0.1 s of the collection
     gc.freeze()       #  right before the timed region -- the first timed step then also pays for the clock ramp)
     for _ in range(a.warmup):
-        dp.step(batch)
+        step()
     # live HIP-event timing over the timed region, on the stream the work is enqueued on: the roofline kernel (the fused
     # gather -> fc_0 launch alone, ops.gather_fc0_run; ops.gather_fwd where the fused kernel does not apply), the gradient
     # all-reduce, and one event per step boundary (per-step GPU times without a host synchronisation)
@@ -324,7 +387,7 @@ def main():
     marks[0].record()
     for i in range(a.steps):
         h0 = time.perf_counter()
-        loss_t = dp.step(batch)["loss"].detach()     # (not the graph: a kept loss tensor keeps its step's activations alive)
+        loss_t = step()["loss"].detach()     # (not the graph: a kept loss tensor keeps its step's activations alive)
         marks[i + 1].record()
         host_ms.append((time.perf_counter() - h0) * 1e3)
         malloc_at.append(torch.cuda.memory_stats(dev).get("num_device_alloc", 0))      # host-side counter, no device call
@@ -339,6 +402,8 @@ def main():
     for mod, name, orig in restore:
         setattr(mod, name, orig)
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
+    if a.dump_outputs and rank == 0:      # before the steps behind the timed region move the parameters on
+        dump_outputs(a.dump_outputs, loss_t, dp, trainer)
     forms = {}
     for key, h in _ifn._pull_hint.items():
         forms[f"level{key[1]}"] = "pull (atomic-free)" if h["use"] else "item-order float atomics"
@@ -369,7 +434,7 @@ def main():
         os.environ["SVR_NO_SIDE_STREAM"] = "1"
         try:
             for _ in range(DIAG_STEPS):
-                dp.step(batch)
+                step()
             sync()
         finally:
             _ifn.OVERLAP_BACKWARD = prev_overlap
@@ -409,11 +474,11 @@ def main():
             ops.BACKWARD_GEMM = ops.BACKWARD_CONV = ops.BACKWARD_CONV_WEIGHT = mode
             try:
                 for _ in range(2):
-                    dp.step(batch)
+                    step()
                 sync()
                 t1 = time.perf_counter()
                 for _ in range(5):
-                    dp.step(batch)
+                    step()
                 sync()
                 alt_ms[key] = (time.perf_counter() - t1) / 5 * 1e3
             finally:
@@ -540,6 +605,30 @@ def main():
     if launched:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss_t, dp, trainer):
+    """--dump-outputs: what the last timed step hands its caller -- the loss, the all-reduced gradient bucket (flat, in
+    parameter order), the parameters after its Adam update (flat, same order) and the BatchNorm running statistics -- as
+    float32 .npy files, ~21 MB at the benched size.  Inputs and initial weights are seeded, so two builds run with the same
+    arguments can be compared file by file: every step starts from the same state (_SameStart), so two runs differ by the
+    float-atomic summation order of one step only."""
+    import numpy as np
+    import torch
+    with torch.no_grad():
+        out = {"loss": loss_t.reshape(1),
+               "grads": dp.bucket.flat,
+               "params": torch.cat([p.detach().reshape(-1) for p in dp.bucket.params]),
+               "bn_stats": torch.cat([b.reshape(-1) for b in trainer.buffers() if b.is_floating_point()])}
+        out = {k: v.float().cpu().numpy() for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def _sig(v, n=5):

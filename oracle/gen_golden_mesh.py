@@ -61,9 +61,24 @@ def cases():
     yield "f32pts", v32, f, rng.uniform(-0.6, 0.6, size=(2500, 3)).astype(np.float32), 64   # float32 inputs (trainer path)
 
 
+def triangle_hash_case():
+    """The reference's Cython TriangleHash on triangles partly outside its 32 x 32 grid: the (point, triangle) candidate
+    pairs it returns, for tests/test_mesh_oracle_golden.py on machines without the build."""
+    th = sys.modules["data_processing.libmesh.triangle_hash"]
+    rng = np.random.default_rng(3)
+    tri = rng.uniform(-2, 34, size=(300, 3, 2))
+    pts = rng.uniform(-3, 35, size=(2000, 2))
+    p, t = (np.asarray(v) for v in th.TriangleHash(tri, 32).query(pts))
+    path = os.path.join(OUT, "mesh_triangle_hash.npz")
+    np.savez_compressed(path, triangles=tri, points=pts, resolution=np.int64(32), point_idx=p.astype(np.int16),
+                        tri_idx=t.astype(np.int16))
+    print(f"{path}: {len(p)} candidate pairs, {os.path.getsize(path) / 1024:.0f} KiB")
+
+
 def main():
     im = load_reference()
     os.makedirs(OUT, exist_ok=True)
+    triangle_hash_case()
     for tag, v, f, pts, res in cases():
         mesh = types.SimpleNamespace(vertices=v, faces=f)
         contains, holes = im.check_mesh_contains(mesh, pts, res)

@@ -117,3 +117,59 @@ def test_compact_line_is_short_and_complete(world, tmp_path):
     full = json.loads(open(detail).read())
     assert "roofline_kernels" in full and "step_ms_list" in full and len(full["ranks"]) == world
     assert err.getvalue().startswith("bench_detail {")
+
+
+def test_plain_run_is_lean_and_full_keeps_the_extra_legs():
+    legs = ("no_cpu_baseline", "no_fwd_only", "no_query", "no_diag", "no_f32_backward")
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert all(getattr(a, k) for k in legs)                  # a plain run times the steps and nothing else
+    f = bench.parse_args(["--steps", "7", "--full"])
+    assert f.full and not any(getattr(f, k) for k in legs)   # --full runs everything behind the timed region, as before
+    assert bench.parse_args(["--full", "--no-query"]).no_query
+    with pytest.raises(SystemExit), redirect_stderr(io.StringIO()):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float32_arrays_of_the_step(tmp_path):
+    import numpy as np
+    import torch
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(5, 4), torch.nn.BatchNorm1d(4))
+    from svr_amd.dp import GradBucket
+    dp = argparse.Namespace(bucket=GradBucket(list(net.parameters())))
+    loss = net(torch.randn(6, 5)).square().mean()
+    loss.backward()
+    dp.bucket.collect_grads()
+    bench.dump_outputs(str(tmp_path / "out"), loss.detach(), dp, net)
+    got = {p.name[:-4]: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(got) == {"loss", "grads", "params", "bn_stats"}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"][0] == pytest.approx(loss.item())
+    assert np.array_equal(got["grads"], torch.cat([p.grad.reshape(-1) for p in net.parameters()]).numpy())
+    assert np.array_equal(got["params"], torch.cat([p.detach().reshape(-1) for p in net.parameters()]).numpy())
+    assert got["bn_stats"].size == 8                         # running mean + running variance (the step counter is not float)
+
+
+def test_every_step_starts_from_the_same_state():
+    import torch
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(5, 4), torch.nn.BatchNorm1d(4), torch.nn.Linear(4, 1))
+    opt = torch.optim.Adam(net.parameters(), lr=1e-2)
+    x = torch.randn(6, 5)
+    same_start = bench._SameStart(net, opt)
+
+    def step():
+        same_start()
+        opt.zero_grad()
+        loss = net(x).square().mean()
+        loss.backward()
+        opt.step()
+        return loss.detach(), [p.detach().clone() for p in net.parameters()], net[1].running_mean.clone()
+
+    first = step()
+    for _ in range(3):
+        last = step()
+    assert torch.equal(first[0], last[0]) and torch.equal(first[2], last[2])     # same loss, same BatchNorm statistics
+    assert all(torch.equal(a, b) for a, b in zip(first[1], last[1]))           # same update from the same moments
+    assert int(net[1].num_batches_tracked) == 1

@@ -1,7 +1,7 @@
 """CPU: the numpy restatement of the reference's occupancy labelling (oracle/mesh_oracle.py) against the outputs of the
 reference's own inside_mesh.py (tests/golden/mesh_*.npz, made by oracle/gen_golden_mesh.py with the reference's
-triangle_hash.pyx compiled into oracle/_ref/) -- bit for bit -- and, when that build is present, the CSR triangle hash
-against the reference's Cython TriangleHash directly."""
+triangle_hash.pyx compiled into oracle/_ref/) -- bit for bit -- and the CSR triangle hash against the stored outputs of
+the reference's Cython TriangleHash (and against that build directly where it is present)."""
 import glob
 import importlib.util
 import os
@@ -33,18 +33,18 @@ def test_oracle_matches_reference_outputs(tag):
 
 
 def test_triangle_hash_equals_reference_cython_build():
+    # the reference's Cython TriangleHash on these inputs, stored by oracle/gen_golden_mesh.py (tests/golden/mesh_triangle_hash.npz)
+    z = np.load(os.path.join(GOLD, "mesh_triangle_hash.npz"), allow_pickle=False)
+    tri, pts, res = z["triangles"], z["points"], int(z["resolution"])      # some triangles stick out of the 32 x 32 grid
+    got_p, got_t = M.TriangleHash(tri, res).query(pts)
+    assert np.array_equal(z["point_idx"], got_p) and np.array_equal(z["tri_idx"], got_t)
     so = glob.glob(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "triangle_hash*.so"))
-    if not so:
-        pytest.skip("oracle/_ref/triangle_hash*.so not built (needs /root/reference: oracle/build_ref.py)")
-    spec = importlib.util.spec_from_file_location("triangle_hash", so[0])          # PyInit_triangle_hash
-    th = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(th)
-    rng = np.random.default_rng(3)
-    tri = rng.uniform(-2, 34, size=(300, 3, 2))                     # some triangles stick out of the 32 x 32 grid
-    pts = rng.uniform(-3, 35, size=(2000, 2))
-    ref_p, ref_t = th.TriangleHash(tri, 32).query(pts)
-    got_p, got_t = M.TriangleHash(tri, 32).query(pts)
-    assert np.array_equal(np.asarray(ref_p), got_p) and np.array_equal(np.asarray(ref_t), got_t)
+    if so:                                                          # and against the build itself where oracle/build_ref.py made it
+        spec = importlib.util.spec_from_file_location("triangle_hash", so[0])          # PyInit_triangle_hash
+        th = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(th)
+        ref_p, ref_t = th.TriangleHash(tri, res).query(pts)
+        assert np.array_equal(np.asarray(ref_p), got_p) and np.array_equal(np.asarray(ref_t), got_t)
 
 
 def test_waterproofing_closes_the_holes_of_an_open_box():

@@ -3,10 +3,11 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 A=${1:-bf16x3}; B=${2:-f16x3s}
-for m in $A $B; do SVR_BACKWARD=$m python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-query --no-fwd-only --no-f32-backward --detail gpurun_out/detail_$m.json > /dev/null 2>&1; done
+OUT=${OUT:-prof_out}; mkdir -p "$OUT"
+for m in $A $B; do SVR_BACKWARD=$m python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-query --no-fwd-only --no-f32-backward --detail "$OUT/detail_$m.json" > /dev/null 2>&1; done
 python - <<PY
 import json
-a=json.load(open("gpurun_out/detail_$A.json")); b=json.load(open("gpurun_out/detail_$B.json"))
+a=json.load(open("$OUT/detail_$A.json")); b=json.load(open("$OUT/detail_$B.json"))
 print("step", round(a["ms_per_step"],3), round(b["ms_per_step"],3))
 ka={k["kernel"]:k for k in a["roofline_kernels"]}; kb={k["kernel"]:k for k in b["roofline_kernels"]}
 tot=0

@@ -10,6 +10,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r03}; shift || true
+set -- --full "$@"      # the stand-alone gather and the single-stream steps run behind the timed region
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf "$R/gpurun_out/pmc_traffic_$C"
   timeout -k 10 420 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$R/gpurun_out/pmc_traffic_$C" -o p -- \
