@@ -610,6 +610,34 @@ int svr_mesh_contains(const void *points, int32_t points_f64, int64_t n, const d
                       uint8_t *holes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Marching cubes (replaces marching_cubes.marching_cubes + export_obj of util/visualize.py:23-25, behind
+ * implicit_to_mesh, model/ifnet.py:232-234, and visualize_sdf).  field: (X, Y, Z) float32, C order, on the device;
+ * output: a welded, indexed triangle mesh in the field's index space (a vertex (x, y, z) has x along axis 0).
+ *   - a lattice point is inside iff (double)v < level (NaN: outside); every cell (i, j, k), i < X-1, j < Y-1,
+ *     k < Z-1, is polygonised; any extent below 2 gives an empty mesh; the border is not padded (open surfaces);
+ *   - one vertex per crossing lattice edge (exactly one endpoint inside), shared by the cells around it, at
+ *     (float)((double)p_axis + fmin(fmax((level - a) / (b - a), 0), 1)), a at the lower endpoint p, b at p + e_axis;
+ *   - vertices ordered by owner point (lower endpoint, C order), then axis 0, 1, 2; faces by cell (C order of the
+ *     minimum corner), then case-table order; normals point from inside to outside.
+ *   svr_mc_workspace_bytes: device workspace for a lattice (negative = SVR_E_BADSHAPE: 2^31 points or more).
+ *   svr_mc_count:  classify + scan; writes the device int64 totals[2] = {V, F}.  The caller reads them back and
+ *                  allocates verts (V, 3) float32 and faces (F, 3) int32; faces are int32, so V, F < 2^31 is the
+ *                  caller's check before svr_mc_emit.
+ *   svr_mc_emit:   fills verts / faces from the same field, level and workspace (after svr_mc_count on the stream).
+ *   svr_mc_case_table: host only; out[256 * 16] = the kernels' case table, 3 edge ids per triangle, -1 padded
+ *                  (edge 4 * axis + (o_u | o_v << 1), corner c at offset (c & 1, c >> 1 & 1, c >> 2 & 1)).
+ *   svr_write_obj: host only; verts (nv, 3) float32 and faces (nf, 3) int32 HOST arrays -> `v x y z` lines (%.9g,
+ *                  float32 round trip) then `f a b c` lines (1-based).  SVR_E_IO on a failed open / write.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_mc_workspace_bytes(int32_t X, int32_t Y, int32_t Z);
+int svr_mc_count(const float *field, int32_t X, int32_t Y, int32_t Z, double level, void *ws, int64_t ws_bytes,
+                 int64_t *totals, void *stream);
+int svr_mc_emit(const float *field, int32_t X, int32_t Y, int32_t Z, double level, void *ws, float *verts, int32_t *faces,
+                void *stream);
+int svr_mc_case_table(int8_t *out);
+int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * Host side (plain C++ + zlib; `out` / `payload` are HOST buffers, ideally pinned):

@@ -144,6 +144,11 @@ SIGNATURES = {
     "svr_mesh_hash_entries": (I64, [P, I64, P, I64, I32, P]),
     "svr_mesh_hash_build": (C.c_int, [P, I64, P, I64, I32, P, P, P, I64]),
     "svr_mesh_contains": (C.c_int, [P, I32, I64, P, P, P, I32, P, P, P, P]),
+    "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
+    "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
+    "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),
+    "svr_mc_case_table": (C.c_int, [P]),
+    "svr_write_obj": (C.c_int, [C.c_char_p, P, I64, P, I64]),
     "svr_df_dims": (C.c_int, [C.c_char_p, P]),
     "svr_df_read": (C.c_int, [C.c_char_p, P, I64]),
     "svr_npz_member_info": (C.c_int, [C.c_char_p, C.c_char_p, P, P, P, P]),

@@ -34,6 +34,7 @@ SOURCES = {
     "projection.hip": ["-ffp-contract=off"],
     "bf16_path.hip": ["-ffp-contract=off"],
     "mesh_occupancy.hip": ["-ffp-contract=off"],
+    "marching_cubes.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "conv2d.hip": [],
     "conv2d_igemm.hip": [],

@@ -36,6 +36,8 @@ int linear_bwd_data_f16_nn(const float *dY, int64_t lddy, const float *W, int64_
                            void *workspace, hipStream_t s);
 size_t scan_sum_excl_i32_temp_bytes(int64_t n);
 hipError_t scan_sum_excl_i32(void *tmp, size_t tmp_bytes, const int32_t *in, int32_t *out, int64_t n, hipStream_t s);
+size_t scan_sum_excl_u64_temp_bytes(int64_t n);
+hipError_t scan_sum_excl_u64(void *tmp, size_t tmp_bytes, const uint64_t *in, uint64_t *out, int64_t n, hipStream_t s);
 }  // namespace svr
 
 #ifdef __HIPCC__

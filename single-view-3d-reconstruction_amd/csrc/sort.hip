@@ -161,6 +161,16 @@ size_t scan_sum_excl_i32_temp_bytes(int64_t n) {
 hipError_t scan_sum_excl_i32(void *tmp, size_t tmp_bytes, const int32_t *in, int32_t *out, int64_t n, hipStream_t s) {
   return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), s);
 }
+// exclusive prefix sum of packed 64-bit counts (marching_cubes.hip: vertex | triangle << 32 per lattice point)
+size_t scan_sum_excl_u64_temp_bytes(int64_t n) {
+  size_t tmp = 0;
+  rocprim::exclusive_scan(nullptr, tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, (size_t)n,
+                          rocprim::plus<uint64_t>(), (hipStream_t)0);
+  return tmp;
+}
+hipError_t scan_sum_excl_u64(void *tmp, size_t tmp_bytes, const uint64_t *in, uint64_t *out, int64_t n, hipStream_t s) {
+  return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
+}
 }  // namespace svr
 
 extern "C" int64_t svr_points_morton_order_workspace(int32_t B, int32_t N) {

@@ -4,7 +4,7 @@ Same public surface as the reference (model/ifnet.py:10-61,64-199,202-229): ``IF
 with ``forward(x (B,1,D,H,W), points (B,N,3)) -> logits (B,N)``, submodule / parameter names of
 SURVEY.md App. A.1 (so Lightning checkpoints `ifnet.*` load), feature extractors
 ``IFNetFeatureExtractor128`` / ``IFNetFeatureExtractor`` and the inference helpers
-``make_3d_grid`` / ``evaluate_network_on_grid``.  The one deliberate difference: the architecture
+``make_3d_grid`` / ``evaluate_network_on_grid`` / ``implicit_to_mesh``.  The one deliberate difference: the architecture
 is a constructor argument (``net_res=128``) instead of a value parsed from sys.argv at import
 (model/ifnet.py:8).
 
@@ -1040,13 +1040,12 @@ def make_3d_grid(bb_min, bb_max, shape, res_increase=1):
     return torch.stack([pxs, pys, pzs], dim=1)
 
 
-def evaluate_network_on_grid(network, x, resolution, res_increase=1, points_batch_size=2048 * 16, storage="f32"):
-    """Occupancy probabilities on the dense lattice (model/ifnet.py:215-229).
+def evaluate_network_on_grid_device(network, x, resolution, res_increase=1, points_batch_size=2048 * 16, storage="f32"):
+    """Occupancy probabilities on the dense lattice (model/ifnet.py:215-229), as a device tensor (X, Y, Z) float32.
 
     Same result as the reference loop, but the encoder pyramid is computed once (network.encode) instead of
-    once per chunk, the lattice is built on the device, and the values stay on the device until the single
-    D2H copy at the end (the reference does one per chunk, :226).  `network` in eval() mode reproduces the
-    reference's validation call; any module without encode()/query() falls back to network(x, chunk)."""
+    once per chunk, the lattice is built on the device, and the values stay on the device.  `network` in eval() mode
+    reproduces the reference's validation call; any module without encode()/query() falls back to network(x, chunk)."""
     pointsf = make_3d_grid((-0.5,) * 3, (0.5,) * 3, resolution, res_increase).to(x.device)
     values = []
     with torch.no_grad():
@@ -1057,6 +1056,24 @@ def evaluate_network_on_grid(network, x, resolution, res_increase=1, points_batc
             z = (network.query(levels, pi, prepared=prep) if prep is not None else network.query(levels, pi)) \
                 if levels is not None else network(x, pi)
             values.append(torch.sigmoid(z).squeeze(0))
-    value = torch.cat(values, dim=0).cpu().numpy()
     r = [int(s) * res_increase for s in resolution]
-    return value.reshape(r[0], r[1], r[2])
+    return torch.cat(values, dim=0).view(r[0], r[1], r[2])
+
+
+def evaluate_network_on_grid(network, x, resolution, res_increase=1, points_batch_size=2048 * 16, storage="f32"):
+    """Occupancy probabilities on the dense lattice (model/ifnet.py:215-229) as a numpy array: the device grid of
+    evaluate_network_on_grid_device with a single D2H copy at the end (the reference does one per chunk, :226)."""
+    return evaluate_network_on_grid_device(network, x, resolution, res_increase, points_batch_size, storage).cpu().numpy()
+
+
+def implicit_to_mesh(network, x, resolution, threshold_p, output_path, res_increase=1):
+    """The reference's implicit_to_mesh (model/ifnet.py:232-234): the mesh of the occupancy lattice at probability
+    `threshold_p`, written to `output_path` as .obj.  Computes what
+    ``visualize_sdf(1 - evaluate_network_on_grid(...), output_path, level=threshold_p)`` computes (1 - p in float32, as
+    the reference's numpy does), but the lattice never leaves the device: only the mesh crosses to the host.
+    Returns (vertices (V,3) float32, faces (F,3) int32) as device tensors."""
+    from ..util.visualize import export_obj, marching_cubes
+    value_grid = evaluate_network_on_grid_device(network, x, resolution, res_increase)
+    vertices, faces = marching_cubes(1 - value_grid, threshold_p)
+    export_obj(vertices, faces, output_path)
+    return vertices, faces

@@ -7,15 +7,19 @@ PyTorch-Lightning (a third-party loop, out of scope): ``ImplicitRefinementTraine
     loss   = BCEWithLogits(logits, batch['occupancies'], reduction='none').sum(-1).mean()
     Adam(ifnet.parameters(), lr=hparams.lr)
 
-so a Lightning ``Trainer`` (or the data-parallel loop in ..dp) can drive it unchanged.
+so a Lightning ``Trainer`` (or the data-parallel loop in ..dp) can drive it unchanged.  ``validation_step(batch,
+batch_idx, output_dir)`` writes the predicted and target meshes as .obj (:49-56).
 """
+from pathlib import Path
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..model.ifnet import IFNet
+from ..model.ifnet import IFNet, implicit_to_mesh
+from ..util.visualize import visualize_sdf
 
 
 class _BCELogitsSumMeanFn(torch.autograd.Function):
@@ -55,3 +59,21 @@ class ImplicitRefinementTrainer(nn.Module):
         logits = self.forward(batch)
         ce_loss = bce_with_logits_sum_mean(logits, batch["occupancies"])
         return {"loss": ce_loss}
+
+    def validation_step(self, batch, batch_idx, output_dir):
+        """trainer_ifnet.py:49-56: for every item, ``<name>_predicted.obj`` (implicit_to_mesh of the network at
+        threshold_p = 0.5 on the round((139, 104, 112) / scale_factor) lattice) and ``<name>_gt.obj`` (visualize_sdf of
+        the target distance field at level 1) in `output_dir` (the reference's runs/<experiment>/vis/<step // 1000>).
+        Unlike the reference, item i is meshed from its own input ``batch['input'][i:i+1]`` and named after its own
+        name: the reference passes the whole batch and names every file after item 0, which is only right at batch
+        size 1."""
+        out = Path(output_dir)
+        out.mkdir(exist_ok=True, parents=True)
+        dims = np.round(np.array((139, 104, 112), dtype=np.float32) / getattr(self.hparams, "scale_factor", 1)).astype(np.int32)
+        x = batch["input"]
+        for i in range(len(batch["name"])):
+            name = batch["name"][i]
+            implicit_to_mesh(self.ifnet, x[i:i + 1], dims, 0.5, out / f"{name}_predicted.obj")
+            target = batch["target"][i]
+            visualize_sdf(target.reshape(target.shape[-3:]).to(x.device), out / f"{name}_gt.obj", level=1)
+        return {"loss": 0}
