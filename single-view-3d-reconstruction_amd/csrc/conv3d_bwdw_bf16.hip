@@ -310,6 +310,298 @@ __global__ __launch_bounds__(NT) void conv3d_bwd_weight_x3_kernel(const float *_
   }
 }
 
+// ---- wave-specialised version of the kernel above (round 5).  The kernel above runs every role in all 8 waves in lockstep, so
+// the split / transposing LDS writes / load waits of one wave never run under the MFMAs of the other wave on its SIMD (its
+// measurement builds: the MFMA phase overlaps nothing).  Here waves 0-3 (one per SIMD) are CONSUMERS: LDS fragment reads and
+// MFMAs only, all x-rows of the brick for their tap group; waves 4-7 are PRODUCERS: global loads of brick b+2, split and
+// transposed writes of brick b+1 into the stage the consumers are not reading.  Same LDS stages, one barrier per brick; the
+// MFMA holds its SIMD's vector issue for 8 of its 32 cycles, the producer's VALU / LDS writes take the other 24.  The two
+// roles run separate loops (same barrier count), so the accumulators and the prefetch registers are never live together.
+// PAIR (Ci <= 16): rows 16-31 of the A tile hold the same channels one halo row (dz, dy) further on, with the same dx: the 9
+// rows x 3 dx taps become 5 row pairs x 3 = 15 tile-taps instead of 27 half-empty ones (only a per-lane row offset changes).
+// One slab part per workgroup (the consumer covers both brick halves).
+constexpr int WS_NP = NT / 2;   // producer threads
+
+// LDS operands of one x-row pair (r = 2 kq + lh) for tap group G: the dout row and the halo rows (row pairs for PAIR) of its taps
+template <int G, bool PAIR>
+struct WsFrag {
+  static constexpr int NTT = PAIR ? 15 : 27, TPW = PAIR ? 4 : TAPS_PER_WAVE;
+  static constexpr int T0 = G * TPW, T1 = (T0 + TPW < NTT) ? T0 + TPW : NTT;
+  static constexpr int RA = T0 / 3, NR = (T1 - 1) / 3 - RA + 1;
+  uint4 bh, bm;
+  uint2 m01[NR], m23[NR], h01[NR], h23[NR];
+  uint32_t m4[NR], h4[NR];
+};
+
+template <int G, bool PAIR>
+__device__ __forceinline__ void ws_fetch(const uint32_t *__restrict__ ibuf, const uint32_t *__restrict__ dbuf, int l31, int r,
+                                         WsFrag<G, PAIR> &f) {
+  using F = WsFrag<G, PAIR>;
+  const int vz = r >> 2, vy = r & 3;
+  f.bh = *reinterpret_cast<const uint4 *>(dbuf + l31 * COS + r * 4);
+  f.bm = *reinterpret_cast<const uint4 *>(dbuf + DO_PLANE + l31 * COS + r * 4);
+  const uint32_t *pl = ibuf + (PAIR ? (l31 & 15) : l31) * CIS + (vz * HLY + vy) * ROWDW;
+#pragma unroll
+  for (int k = 0; k < F::NR; ++k) {
+    const int R = F::RA + k;
+    // halo row (dz, dy) of this lane: R itself, or for PAIR row 2R (lanes 0-15) / 2R + 1 (lanes 16-31; row 9 does not exist:
+    // row 8 again, its products are discarded at the slab write)
+    const int ra = PAIR ? 2 * R : R, rb = PAIR ? (2 * R + 1 < 9 ? 2 * R + 1 : 8) : R;
+    const int oa = ((ra / 3) * HLY + ra % 3) * ROWDW, ob = ((rb / 3) * HLY + rb % 3) * ROWDW;
+    const uint32_t *ph = pl + (PAIR && l31 >= 16 ? ob : oa);
+    f.m01[k] = *reinterpret_cast<const uint2 *>(ph + IN_PLANE);
+    f.m23[k] = *reinterpret_cast<const uint2 *>(ph + IN_PLANE + 2);
+    f.m4[k] = ph[IN_PLANE + 4];
+    f.h01[k] = *reinterpret_cast<const uint2 *>(ph);
+    f.h23[k] = *reinterpret_cast<const uint2 *>(ph + 2);
+    f.h4[k] = ph[4];
+  }
+}
+
+// the MFMAs of one x-row pair: per tap the three split products in the order of the kernel above
+template <int G, bool F16, bool PAIR>
+__device__ __forceinline__ void ws_mfma(const WsFrag<G, PAIR> &f, f32x16 (&acc)[TAPS_PER_WAVE]) {
+  using F = WsFrag<G, PAIR>;
+  const bf16x8 b_hi = frag(f.bh.x, f.bh.y, f.bh.z, f.bh.w), b_mid = frag(f.bm.x, f.bm.y, f.bm.z, f.bm.w);
+#pragma unroll
+  for (int k = 0; k < F::NR; ++k) {
+    const int R = F::RA + k;
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int tt = R * 3 + dx;
+      if (tt < F::T0 || tt >= F::T1) continue;
+      const int i = tt - F::T0;
+      const uint2 m01 = f.m01[k], m23 = f.m23[k], h01 = f.h01[k], h23 = f.h23[k];
+      const uint32_t m4 = f.m4[k], h4 = f.h4[k];
+      const bf16x8 am = dx == 0 ? frag(m01.x, m01.y, m23.x, m23.y)
+                      : dx == 2 ? frag(m01.y, m23.x, m23.y, m4)
+                                : frag(__builtin_amdgcn_alignbit(m01.y, m01.x, 16), __builtin_amdgcn_alignbit(m23.x, m01.y, 16),
+                                       __builtin_amdgcn_alignbit(m23.y, m23.x, 16), __builtin_amdgcn_alignbit(m4, m23.y, 16));
+      const bf16x8 ah = dx == 0 ? frag(h01.x, h01.y, h23.x, h23.y)
+                      : dx == 2 ? frag(h01.y, h23.x, h23.y, h4)
+                                : frag(__builtin_amdgcn_alignbit(h01.y, h01.x, 16), __builtin_amdgcn_alignbit(h23.x, h01.y, 16),
+                                       __builtin_amdgcn_alignbit(h23.y, h23.x, 16), __builtin_amdgcn_alignbit(h4, h23.y, 16));
+      if constexpr (F16) {
+        const f16x8 fam = __builtin_bit_cast(f16x8, am), fah = __builtin_bit_cast(f16x8, ah);
+        const f16x8 fbh = __builtin_bit_cast(f16x8, b_hi), fbm = __builtin_bit_cast(f16x8, b_mid);
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fam, scale_2m11(fbh), acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(scale_2m11(fah), fbm, acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah, fbh, acc[i], 0, 0, 0);
+      } else {
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, b_hi, acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b_mid, acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b_hi, acc[i], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// consumer wave of tap group G: all 16 x-rows of each brick, accumulators over all bricks, then its slab tiles
+template <int G, bool F16, bool PAIR>
+__device__ __forceinline__ void ws_consume(const uint32_t *lds, int n_it, float *__restrict__ slab, int pair,
+                                           const uint32_t *__restrict__ amax_dout) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, lh = lane >> 5;
+  f32x16 acc[TAPS_PER_WAVE];
+#pragma unroll
+  for (int i = 0; i < TAPS_PER_WAVE; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  __syncthreads();   // stage 0 filled
+  int cur = 0;
+  for (int it = 0; it < n_it; ++it) {
+    const uint32_t *ibuf = lds + cur * BUF, *dbuf = ibuf + 2 * IN_PLANE;
+    // (software-pipelining the LDS reads of pair kq + 1 under the MFMAs of pair kq measured the same: not kept)
+#pragma unroll 1
+    for (int kq = 0; kq < 8; ++kq) {   // x-row r = 2 kq + lh = vz*4 + vy
+      WsFrag<G, PAIR> f;
+      ws_fetch<G, PAIR>(ibuf, dbuf, l31, 2 * kq + lh, f);
+      ws_mfma<G, F16, PAIR>(f, acc);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  // slab layout shared with conv3d.hip's reduce kernel: [part][tap][pair][32 ci][32 co], one part per workgroup
+  float inv = 1.f;
+  if constexpr (F16) inv = amax_dout ? w_scale(amax_dout[0], true) : 1.f;
+  const int pairs = gridDim.y;
+  const int64_t part = blockIdx.x;
+  constexpr int NTT = PAIR ? 15 : 27, TPW = PAIR ? 4 : TAPS_PER_WAVE;
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) {
+    const int tt = G * TPW + i;
+    if (tt >= NTT) continue;
+    if constexpr (PAIR) {  // accumulator rows 0-15: halo row 2R, channels 0-15; rows 16-31: halo row 2R + 1
+      const int R = tt / 3, dx = tt % 3;
+      float *lo = slab + ((part * 27 + (2 * R) * 3 + dx) * pairs + pair) * 1024;
+      float *hi = slab + ((part * 27 + (2 * R + 1) * 3 + dx) * pairs + pair) * 1024;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const float v = F16 ? acc[i][r] * inv : acc[i][r];
+        if (r < 8) lo[row * 32 + l31] = v;
+        else if (2 * R + 1 < 9) hi[(row - 16) * 32 + l31] = v;
+      }
+    } else {
+      float *o = slab + ((part * 27 + tt) * pairs + pair) * 1024;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + l31] = F16 ? acc[i][r] * inv : acc[i][r];
+    }
+  }
+}
+
+template <bool F16, bool PAIR>
+__global__ __launch_bounds__(NT) void conv3d_bwd_weight_ws_kernel(const float *__restrict__ in, const float *__restrict__ dout,
+                                                                  float *__restrict__ slab, ConvShape s, int nbz, int nby,
+                                                                  int nbx, int co_tiles, float *__restrict__ dbpart,
+                                                                  const uint32_t *__restrict__ amax_dout) {
+  constexpr int CG = PAIR ? 4 : 8;                                 // 4-channel groups of the input tile that are loaded
+  constexpr int IN_N = HROWS * 5 * CG;                             // (halo row, voxel pair, channel group) items
+  constexpr int IN_PT = (IN_N + WS_NP - 1) / WS_NP;                // 6 (3 for PAIR) input items per producer thread
+  constexpr int DO_PT = DO_ITEMS / WS_NP;                          // 2 dout items
+  static_assert(DO_ITEMS % WS_NP == 0 && WS_NP % 8 == 0, "a producer thread's dout items share one channel group");
+  __shared__ uint32_t lds[2 * BUF];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int pair = blockIdx.y;
+  const int ci0 = (pair / co_tiles) * 32, co0 = (pair % co_tiles) * 32;
+  const int bricks = s.B * nbz * nby * nbx;   // (host: < 2^31)
+  const int n_it = (bricks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;   // host: gridDim.x <= bricks
+  const bool want_db = dbpart != nullptr && ci0 == 0;
+  float4 dbs = make_float4(0.f, 0.f, 0.f, 0.f);
+
+  if (wave < 4) {
+    // ---------------- consumer: tap group `wave` (one whole loop per group: a switch inside the loop made the compiler copy
+    // the 112 accumulator registers around it every x-row pair, and spill)
+    switch (wave) {
+      case 0: ws_consume<0, F16, PAIR>(lds, n_it, slab, pair, amax_dout); break;
+      case 1: ws_consume<1, F16, PAIR>(lds, n_it, slab, pair, amax_dout); break;
+      case 2: ws_consume<2, F16, PAIR>(lds, n_it, slab, pair, amax_dout); break;
+      default: ws_consume<3, F16, PAIR>(lds, n_it, slab, pair, amax_dout); break;
+    }
+  } else {
+    // ---------------- producer: thread p moves input items p + 256 j and dout items p + 256 j of every brick
+    const int p = t - WS_NP;
+    float sy = 1.f;
+    if constexpr (F16) sy = amax_dout ? w_scale(amax_dout[0], false) : 1.f;
+    float4 ia[IN_PT][2], da[DO_PT][2];
+    int iok[IN_PT], dok[DO_PT];  // bit v: voxel v of the pair is inside the volume
+
+    auto load = [&](int brick) {
+      int q = brick;
+      const int bx = q % nbx; q /= nbx;
+      const int by = q % nby; q /= nby;
+      const int bz = q % nbz;
+      const int b = q / nbz;
+      const int z0 = bz * BRZ, y0 = by * BRY, x0 = bx * BRX;
+      const char *inb = reinterpret_cast<const char *>(in + (int64_t)b * s.D * s.H * s.W * s.Ci);
+#pragma unroll
+      for (int j = 0; j < IN_PT; ++j) {
+        const int idx = min(p + WS_NP * j, IN_N - 1);
+        const int hrow = idx / (5 * CG), rem = idx % (5 * CG), pr = rem / CG, cg = rem % CG;
+        const int gz = z0 + hrow / HLY - 1, gy = y0 + hrow % HLY - 1, gx = x0 + 2 * pr - 1;
+        // unconditional loads from clamped coordinates, out-of-range voxels zeroed in store() (see the kernel above)
+        const bool rowok = gz >= 0 && gz < s.D && gy >= 0 && gy < s.H && ci0 + cg * 4 < s.Ci;
+        const int cz = min(max(gz, 0), s.D - 1), cy = min(max(gy, 0), s.H - 1), cc = min(ci0 + cg * 4, s.Ci - 4);
+        const uint32_t ro = __umul24(__umul24(__umul24((uint32_t)cz, (uint32_t)s.H) + (uint32_t)cy, (uint32_t)s.W), (uint32_t)s.Ci) + (uint32_t)cc;
+        ia[j][0] = *reinterpret_cast<const float4 *>(inb + (ro + __umul24((uint32_t)min(max(gx, 0), s.W - 1), (uint32_t)s.Ci)) * 4u);
+        ia[j][1] = *reinterpret_cast<const float4 *>(inb + (ro + __umul24((uint32_t)min(max(gx + 1, 0), s.W - 1), (uint32_t)s.Ci)) * 4u);
+        iok[j] = (rowok && gx >= 0 && gx < s.W ? 1 : 0) | (rowok && gx + 1 >= 0 && gx + 1 < s.W ? 2 : 0);
+      }
+      const char *dob = reinterpret_cast<const char *>(dout + (int64_t)b * s.D * s.H * s.W * s.Co);
+#pragma unroll
+      for (int j = 0; j < DO_PT; ++j) {
+        const int idx = p + WS_NP * j;
+        const int row = idx >> 5, pr = (idx & 31) >> 3, cg = idx & 7;
+        const int gz = z0 + (row >> 2), gy = y0 + (row & 3), gx = x0 + 2 * pr;
+        const bool rowok = gz < s.D && gy < s.H && co0 + cg * 4 < s.Co;
+        const int cz = min(gz, s.D - 1), cy = min(gy, s.H - 1), cc = min(co0 + cg * 4, s.Co - 4);
+        const uint32_t ro = __umul24(__umul24(__umul24((uint32_t)cz, (uint32_t)s.H) + (uint32_t)cy, (uint32_t)s.W), (uint32_t)s.Co) + (uint32_t)cc;
+        da[j][0] = *reinterpret_cast<const float4 *>(dob + (ro + __umul24((uint32_t)min(gx, s.W - 1), (uint32_t)s.Co)) * 4u);
+        da[j][1] = *reinterpret_cast<const float4 *>(dob + (ro + __umul24((uint32_t)min(gx + 1, s.W - 1), (uint32_t)s.Co)) * 4u);
+        dok[j] = (rowok && gx < s.W ? 1 : 0) | (rowok && gx + 1 < s.W ? 2 : 0);
+      }
+    };
+
+    auto store = [&](uint32_t *buf) {
+#pragma unroll
+      for (int j = 0; j < IN_PT; ++j) {
+        const int idx = p + WS_NP * j;
+        if (IN_N % WS_NP == 0 || idx < IN_N) {
+          const int hrow = idx / (5 * CG), rem = idx % (5 * CG), pr = rem / CG, cg = rem % CG;
+          uint32_t *d = buf + (cg * 4) * CIS + hrow * ROWDW + pr;
+          const float4 a0 = ia[j][0], a1 = ia[j][1];
+          const int ok = iok[j];
+          const float v0[4] = {a0.x, a0.y, a0.z, a0.w};
+          const float v1[4] = {a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            uint32_t h, m;
+            if constexpr (F16) split_x((ok & 1) ? v0[c] : 0.f, (ok & 2) ? v1[c] : 0.f, h, m);
+            else split2((ok & 1) ? v0[c] : 0.f, (ok & 2) ? v1[c] : 0.f, h, m);
+            d[c * CIS] = h;
+            d[IN_PLANE + c * CIS] = m;
+          }
+        }
+      }
+      uint32_t *dbuf = buf + 2 * IN_PLANE;
+#pragma unroll
+      for (int j = 0; j < DO_PT; ++j) {
+        const int idx = p + WS_NP * j;
+        const int row = idx >> 5, pr = (idx & 31) >> 3, cg = idx & 7;
+        uint32_t *d = dbuf + (cg * 4) * COS + row * 4 + pr;
+        const float4 a0 = da[j][0], a1 = da[j][1];
+        const int ok = dok[j];
+        float v0[4] = {a0.x, a0.y, a0.z, a0.w};
+        float v1[4] = {a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          v0[c] = (ok & 1) ? v0[c] : 0.f;
+          v1[c] = (ok & 2) ? v1[c] : 0.f;
+          uint32_t h, m;
+          if constexpr (F16) split_x(v0[c] * sy, v1[c] * sy, h, m);
+          else split2(v0[c], v1[c], h, m);
+          d[c * COS] = h;
+          d[DO_PLANE + c * COS] = m;
+        }
+        if (want_db) {
+          dbs.x += v0[0] + v1[0]; dbs.y += v0[1] + v1[1]; dbs.z += v0[2] + v1[2]; dbs.w += v0[3] + v1[3];
+        }
+      }
+    };
+
+    const int b0 = blockIdx.x, g = gridDim.x;
+    load(b0);
+    store(lds);
+    if (n_it > 1) load(b0 + g);
+    __syncthreads();   // stage 0 filled
+    int cur = 0;
+    // iteration it (consumers on brick it): split brick it + 1 (in registers) into the other stage, issue the loads of it + 2
+    for (int it = 0; it < n_it; ++it) {
+      if (it + 1 < n_it) {
+        store(lds + (cur ^ 1) * BUF);
+        if (it + 2 < n_it) load(b0 + (it + 2) * g);
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+
+  if (want_db) {  // fixed-order sum of the 32 producer threads per channel group through LDS (free after the last barrier)
+    float *sred = reinterpret_cast<float *>(lds);
+    if (wave >= 4) {
+      const int p = t - WS_NP;
+      sred[p * 4 + 0] = dbs.x; sred[p * 4 + 1] = dbs.y; sred[p * 4 + 2] = dbs.z; sred[p * 4 + 3] = dbs.w;
+    }
+    __syncthreads();
+    if (t < 32) {
+      const int cg = t >> 2, c = t & 3;
+      float sum = 0.f;
+      for (int i = 0; i < WS_NP / 8; ++i) sum += sred[(i * 8 + cg) * 4 + c];
+      if (co0 + t < s.Co) dbpart[(int64_t)blockIdx.x * s.Co + co0 + t] = sum;
+    }
+  }
+}
+
 // db[co] = f64 tree (fixed order) over the workgroups' partial bias gradients; one workgroup per channel
 __global__ __launch_bounds__(256) void db_reduce_kernel(const float *__restrict__ dbpart, float *__restrict__ db, int Co,
                                                         int parts) {
@@ -390,6 +682,24 @@ int bwd_weight_x3(const float *in, const float *dout, float *dWp, float *db, int
   const int parts = x3_parts(B, D, H, W, Ci, Co);
   float *slab = (float *)workspace;
   float *dbpart = db ? slab + (int64_t)parts * 2 * 27 * cit * cot * 1024 : nullptr;
+  // Dispatch: the wave-specialised kernel when every workgroup gets at least WS_MIN_BRICKS bricks (its pipeline fills and
+  // drains once per launch, and one consumer wave per SIMD has no partner to hide its own latencies); the 8-wave kernel for
+  // the short launches (the 8^3 layer: 2 bricks per workgroup).
+  constexpr int WS_MIN_BRICKS = 8;
+  const int64_t nbricks = (int64_t)B * nbz * nby * nbx;
+  if (nbricks >= (int64_t)parts * WS_MIN_BRICKS) {
+    const dim3 grid((unsigned)parts, (unsigned)(cit * cot));
+    const uint32_t *am = f16 ? amax_dout : nullptr;
+    if (Ci <= 16) {
+      if (f16) hipLaunchKernelGGL((conv3d_bwd_weight_ws_kernel<true, true>), grid, dim3(NT), 0, s, in, dout, slab, sh, nbz, nby, nbx, cot, dbpart, am);
+      else hipLaunchKernelGGL((conv3d_bwd_weight_ws_kernel<false, true>), grid, dim3(NT), 0, s, in, dout, slab, sh, nbz, nby, nbx, cot, dbpart, am);
+    } else {
+      if (f16) hipLaunchKernelGGL((conv3d_bwd_weight_ws_kernel<true, false>), grid, dim3(NT), 0, s, in, dout, slab, sh, nbz, nby, nbx, cot, dbpart, am);
+      else hipLaunchKernelGGL((conv3d_bwd_weight_ws_kernel<false, false>), grid, dim3(NT), 0, s, in, dout, slab, sh, nbz, nby, nbx, cot, dbpart, am);
+    }
+    conv3d_bwd_weight_reduce_launch(slab, dWp, Ci, Co, cit, cot, parts, s, param_layout, dbpart, db, parts);
+    return launch_status("conv3d_bwd_weight_bf16x3");
+  }
   if (f16)
     hipLaunchKernelGGL(conv3d_bwd_weight_x3_kernel<true>, dim3((unsigned)parts, (unsigned)(cit * cot)), dim3(NT), 0, s, in, dout,
                        slab, sh, nbz, nby, nbx, cot, dbpart, amax_dout);
