@@ -409,6 +409,20 @@ int svr_conv3d_k3_bwd_data_f16x3(const float *dout, const float *W, float *din, 
 int svr_conv3d_k3_bwd_weight_f16x3(const float *in, const float *dout, float *dW, float *db, int32_t B,
                                    int32_t D, int32_t H, int32_t W, int32_t Ci, int32_t Co, int32_t param_layout,
                                    const uint32_t *amax_dout, void *workspace, void *stream);
+/* Which kernel instantiation the split-precision 3x3x3 entry points above take for a shape (the launchers ask the same
+ * function).  Host only: no device memory is touched, callable without a GPU.  op = SVR_CONV_*; shapes as the entry point
+ * takes them (Ci / Co of the CONVOLUTION; backward-data writes Ci columns and reduces over Co).  Outputs (each may be NULL):
+ *   ck: channels of the reduction side per LDS chunk (16 / 32);  tn: 32-column output tiles per workgroup (1 / 2 / 4);
+ *   vt: z-slices per wave (2 = the 8x4x8 double-brick tile, 32 columns);  persistent: 1 = conv3d_brick_p_kernel (bricks
+ *   handed to resident workgroups; SVR_CONV_PERSISTENT=0 in the environment turns it off), 0 = one brick per workgroup;
+ *   workgroup_rows: bricks of the volume = grid.x of the one-brick kernels = partial-sum rows of the stats epilogue
+ *   (svr_conv3d_fwd_f16x3_stats_blocks).  SVR_E_UNSUPPORTED for channel counts the entry point refuses.            */
+#define SVR_CONV_FWD_F16X3 0
+#define SVR_CONV_BWD_DATA_F16X3S 1
+#define SVR_CONV_BWD_DATA_BF16X3 2
+#define SVR_CONV_FWD_BF16X6 3
+int svr_conv3d_k3_variant(int32_t op, int32_t B, int32_t D, int32_t H, int32_t Wd, int32_t Ci, int32_t Co, int32_t *ck,
+                          int32_t *tn, int32_t *vt, int32_t *persistent, int64_t *workgroup_rows);
 
 /* ---------------------------------------------------------------------------------------
  * BatchNorm3d (training or eval) + MaxPool3d(2), channels-last

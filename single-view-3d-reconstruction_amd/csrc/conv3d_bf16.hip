@@ -778,6 +778,40 @@ void launch_brick_p(const float *in, const uint16_t *P0, int64_t plane_stride, c
                      mask, sh, nbz, nby, nbx, (int)bricks, mode, amax, spart, amax_in, amax_out);
 }
 
+// The tile choice of the 3x3x3 launchers below, from the shape alone (svr_conv3d_k3_variant exports it).  cols = the output
+// columns (Co forward, Ci backward-data), k = the reduction side.
+//   tn: 32-column tiles per workgroup, as wide as the layer allows (fragment reuse) but narrower on the small volumes so
+//       that the grid still has >= 512 workgroups (the 8^3 / 16^3 layers ran 32 / 256 workgroups of 108 barrier steps);
+//   vt == 2: two z-slices per wave (8x4x8 bricks, 16-channel chunks, 32 columns), persistent where persistent_bricks() allows;
+//   rows: grid.x of the one-brick-per-workgroup kernels = bricks of the persistent one = partial-sum rows of the stats epilogue.
+struct ConvVariant {
+  int ck, tn, vt, nbz, nby, nbx, ycols;
+  bool persistent;
+  int64_t rows;
+};
+ConvVariant conv_variant(int op, int B, int D, int H, int Wd, int k, int cols) {
+  ConvVariant v;
+  v.nbz = (int)cdiv(D, BRZ), v.nby = (int)cdiv(H, BRY), v.nbx = (int)cdiv(Wd, BRX);
+  v.vt = 1, v.persistent = false;
+  v.rows = (int64_t)B * v.nbz * v.nby * v.nbx;
+  v.tn = cols <= 32 ? 1 : (cols <= 64 ? 2 : 4);
+  if (op == SVR_CONV_FWD_BF16X6) {
+    v.ck = 16;
+  } else {
+    while (v.tn > 1 && v.rows * cdiv(cols, v.tn * 32) < 512) v.tn /= 2;
+    const int nbz2 = (int)cdiv(D, 2 * BRZ);
+    const int64_t rows2 = (int64_t)B * nbz2 * v.nby * v.nbx;
+    if (v.tn == 1 && rows2 * cdiv(cols, 32) >= 512) {
+      v.ck = 16, v.vt = 2, v.nbz = nbz2, v.rows = rows2;
+      v.persistent = persistent_bricks(ConvShape{B, D, H, Wd, k, cols});
+    } else {
+      v.ck = k % 32 == 0 ? 32 : 16;
+    }
+  }
+  v.ycols = (int)cdiv(cols, v.tn * 32);
+  return v;
+}
+
 }  // namespace
 
 extern "C" int64_t svr_conv3d_bwd_data_bf16x3_workspace(int32_t Ci, int32_t Co) { return 2LL * 27 * Ci * Co * (int64_t)sizeof(uint16_t) + 256; }
@@ -798,27 +832,19 @@ extern "C" int svr_conv3d_k3_bwd_data_bf16x3(const float *dout, const float *W, 
   SVR_CHECK(B > 0 && D > 0 && H > 0 && Wd > 0, SVR_E_BADSHAPE, "conv3d_bwd_data_bf16x3: empty volume");
   SVR_CHECK(epilogue == SVR_EPI_NONE || (epilogue == SVR_EPI_MASK && mask), SVR_E_BADARG, "conv3d_bwd_data_bf16x3: epilogue %d", epilogue);
   ConvShape sh{B, D, H, Wd, /*K=*/Co, /*NOUT=*/Ci};
-  const int nbz = (int)cdiv(D, BRZ), nby = (int)cdiv(H, BRY), nbx = (int)cdiv(Wd, BRX);
-  const unsigned bricks = (unsigned)((int64_t)B * nbz * nby * nbx);
+  const ConvVariant v = conv_variant(SVR_CONV_BWD_DATA_BF16X3, B, D, H, Wd, Co, Ci);
 #define LAUNCH_X3(CKV, TNV)                                                                                               \
-  hipLaunchKernelGGL((conv3d_brick_x3_kernel<CKV, TNV, 2>), dim3(bricks, (unsigned)cdiv(Ci, TNV * 32)), dim3(256), 0, s, dout, \
-                     hi, (int64_t)27 * Ci * Co, (const float *)nullptr, din, mask, sh, nbz, nby, nbx, epilogue)
-  // output-column tiles per workgroup: as wide as the layer allows (fragment reuse), but narrower on the small volumes
-  // so that the grid still has >= 512 workgroups (the 8^3 / 16^3 layers ran 32 / 256 workgroups of 108 barrier steps)
-  int tn = Ci <= 32 ? 1 : (Ci <= 64 ? 2 : 4);
-  while (tn > 1 && (int64_t)bricks * cdiv(Ci, tn * 32) < 512) tn /= 2;
-  const int nbz2 = (int)cdiv(D, 2 * BRZ);
-  if (tn == 1 && Co % 16 == 0 && (int64_t)B * nbz2 * nby * nbx * cdiv(Ci, 32) >= 512) {
-    // 32 output columns: two z-slices per wave (8x4x8 bricks, 16-channel chunks)
-    if (persistent_bricks(sh))
-      launch_brick_p<16, false, 2>(dout, hi, (int64_t)27 * Ci * Co, nullptr, din, mask, sh, nbz2, nby, nbx, (int)cdiv(Ci, 32), epilogue, nullptr, nullptr, s);
-    else
-    hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, 1, 2, false, 2>), dim3((unsigned)((int64_t)B * nbz2 * nby * nbx), (unsigned)cdiv(Ci, 32)),
-                       dim3(256), 0, s, dout, hi, (int64_t)27 * Ci * Co, (const float *)nullptr, din, mask, sh, nbz2, nby, nbx, epilogue);
-  } else if (Co % 32 == 0) {
-    if (tn == 1) LAUNCH_X3(32, 1); else if (tn == 2) LAUNCH_X3(32, 2); else LAUNCH_X3(32, 4);
+  hipLaunchKernelGGL((conv3d_brick_x3_kernel<CKV, TNV, 2>), dim3((unsigned)v.rows, (unsigned)v.ycols), dim3(256), 0, s, dout, \
+                     hi, (int64_t)27 * Ci * Co, (const float *)nullptr, din, mask, sh, v.nbz, v.nby, v.nbx, epilogue)
+  if (v.persistent) {
+    launch_brick_p<16, false, 2>(dout, hi, (int64_t)27 * Ci * Co, nullptr, din, mask, sh, v.nbz, v.nby, v.nbx, v.ycols, epilogue, nullptr, nullptr, s);
+  } else if (v.vt == 2) {
+    hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, 1, 2, false, 2>), dim3((unsigned)v.rows, (unsigned)v.ycols), dim3(256), 0, s, dout, hi,
+                       (int64_t)27 * Ci * Co, (const float *)nullptr, din, mask, sh, v.nbz, v.nby, v.nbx, epilogue);
+  } else if (v.ck == 32) {
+    if (v.tn == 1) LAUNCH_X3(32, 1); else if (v.tn == 2) LAUNCH_X3(32, 2); else LAUNCH_X3(32, 4);
   } else {
-    if (tn == 1) LAUNCH_X3(16, 1); else if (tn == 2) LAUNCH_X3(16, 2); else LAUNCH_X3(16, 4);
+    if (v.tn == 1) LAUNCH_X3(16, 1); else if (v.tn == 2) LAUNCH_X3(16, 2); else LAUNCH_X3(16, 4);
   }
 #undef LAUNCH_X3
   return launch_status("conv3d_bwd_data_bf16x3");
@@ -846,25 +872,19 @@ extern "C" int svr_conv3d_k3_bwd_data_f16x3(const float *dout, const float *W, f
   SVR_CHECK(B > 0 && D > 0 && H > 0 && Wd > 0, SVR_E_BADSHAPE, "conv3d_bwd_data_f16x3: empty volume");
   SVR_CHECK(epilogue == SVR_EPI_NONE || (epilogue == SVR_EPI_MASK && mask), SVR_E_BADARG, "conv3d_bwd_data_f16x3: epilogue %d", epilogue);
   ConvShape sh{B, D, H, Wd, /*K=*/Co, /*NOUT=*/Ci};
-  const int nbz = (int)cdiv(D, BRZ), nby = (int)cdiv(H, BRY), nbx = (int)cdiv(Wd, BRX);
-  const unsigned bricks = (unsigned)((int64_t)B * nbz * nby * nbx);
+  const ConvVariant v = conv_variant(SVR_CONV_BWD_DATA_F16X3S, B, D, H, Wd, Co, Ci);
 #define LAUNCH_B3(CKV, TNV)                                                                                                     \
-  hipLaunchKernelGGL((conv3d_brick_x3_kernel<CKV, TNV, 2, true>), dim3(bricks, (unsigned)cdiv(Ci, TNV * 32)), dim3(256), 0, s, dout, \
-                     hi, ps, (const float *)nullptr, din, mask, sh, nbz, nby, nbx, epilogue, amax, (double *)nullptr, amax_dout, amax_din)
-  int tn = Ci <= 32 ? 1 : (Ci <= 64 ? 2 : 4);                        // (the tile choice of svr_conv3d_k3_bwd_data_bf16x3)
-  while (tn > 1 && (int64_t)bricks * cdiv(Ci, tn * 32) < 512) tn /= 2;
-  const int nbz2 = (int)cdiv(D, 2 * BRZ);
-  if (tn == 1 && (int64_t)B * nbz2 * nby * nbx * cdiv(Ci, 32) >= 512) {
-    if (persistent_bricks(sh))
-      launch_brick_p<16, true, 2>(dout, hi, ps, nullptr, din, mask, sh, nbz2, nby, nbx, (int)cdiv(Ci, 32), epilogue, amax, nullptr, s, amax_dout, amax_din);
-    else
-      hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, 1, 2, true, 2>), dim3((unsigned)((int64_t)B * nbz2 * nby * nbx), (unsigned)cdiv(Ci, 32)),
-                         dim3(256), 0, s, dout, hi, ps, (const float *)nullptr, din, mask, sh, nbz2, nby, nbx, epilogue, amax, (double *)nullptr,
-                         amax_dout, amax_din);
-  } else if (Co % 32 == 0) {
-    if (tn == 1) LAUNCH_B3(32, 1); else if (tn == 2) LAUNCH_B3(32, 2); else LAUNCH_B3(32, 4);
+  hipLaunchKernelGGL((conv3d_brick_x3_kernel<CKV, TNV, 2, true>), dim3((unsigned)v.rows, (unsigned)v.ycols), dim3(256), 0, s, dout, \
+                     hi, ps, (const float *)nullptr, din, mask, sh, v.nbz, v.nby, v.nbx, epilogue, amax, (double *)nullptr, amax_dout, amax_din)
+  if (v.persistent) {
+    launch_brick_p<16, true, 2>(dout, hi, ps, nullptr, din, mask, sh, v.nbz, v.nby, v.nbx, v.ycols, epilogue, amax, nullptr, s, amax_dout, amax_din);
+  } else if (v.vt == 2) {
+    hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, 1, 2, true, 2>), dim3((unsigned)v.rows, (unsigned)v.ycols), dim3(256), 0, s, dout, hi, ps,
+                       (const float *)nullptr, din, mask, sh, v.nbz, v.nby, v.nbx, epilogue, amax, (double *)nullptr, amax_dout, amax_din);
+  } else if (v.ck == 32) {
+    if (v.tn == 1) LAUNCH_B3(32, 1); else if (v.tn == 2) LAUNCH_B3(32, 2); else LAUNCH_B3(32, 4);
   } else {
-    if (tn == 1) LAUNCH_B3(16, 1); else if (tn == 2) LAUNCH_B3(16, 2); else LAUNCH_B3(16, 4);
+    if (v.tn == 1) LAUNCH_B3(16, 1); else if (v.tn == 2) LAUNCH_B3(16, 2); else LAUNCH_B3(16, 4);
   }
 #undef LAUNCH_B3
   return launch_status("conv3d_bwd_data_f16x3");
@@ -886,12 +906,11 @@ extern "C" int svr_conv3d_k3_fwd_bf16x6(const float *in, const float *W, const f
   const int64_t ps = (int64_t)27 * Ci * Co;
   hipLaunchKernelGGL(pack_fwd_planes_kernel, dim3(cdiv(27 * Co * (Ci / 2), 256)), dim3(256), 0, s, W, p0, p0 + ps, p0 + 2 * ps, Ci, Co);
   ConvShape sh{B, D, H, Wd, Ci, Co};
-  const int nbz = (int)cdiv(D, BRZ), nby = (int)cdiv(H, BRY), nbx = (int)cdiv(Wd, BRX);
-  const unsigned bricks = (unsigned)((int64_t)B * nbz * nby * nbx);
+  const ConvVariant v = conv_variant(SVR_CONV_FWD_BF16X6, B, D, H, Wd, Ci, Co);
 #define LAUNCH_X6(TNV)                                                                                                    \
-  hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, TNV, 3>), dim3(bricks, (unsigned)cdiv(Co, TNV * 32)), dim3(256), 0, s, in, p0, \
-                     ps, bias, out, (const float *)nullptr, sh, nbz, nby, nbx, epilogue)
-  if (Co <= 32) LAUNCH_X6(1); else if (Co <= 64) LAUNCH_X6(2); else LAUNCH_X6(4);
+  hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, TNV, 3>), dim3((unsigned)v.rows, (unsigned)v.ycols), dim3(256), 0, s, in, p0, \
+                     ps, bias, out, (const float *)nullptr, sh, v.nbz, v.nby, v.nbx, epilogue)
+  if (v.tn == 1) LAUNCH_X6(1); else if (v.tn == 2) LAUNCH_X6(2); else LAUNCH_X6(4);
 #undef LAUNCH_X6
   return launch_status("conv3d_fwd_bf16x6");
 }
@@ -930,12 +949,7 @@ namespace {
 int fwd_f16x3(const float *in, const float *W, const float *bias, float *out, int32_t B, int32_t D, int32_t H, int32_t Wd, int32_t Ci,
               int32_t Co, int epilogue, void *workspace, void *stream, double *spart, int *blocks) {
   if (blocks) {   // query: the number of workgroup rows (= partial-sum rows) of the variant this shape takes
-    const int nbz = (int)cdiv(D, BRZ), nby = (int)cdiv(H, BRY), nbx = (int)cdiv(Wd, BRX);
-    const int64_t bricks = (int64_t)B * nbz * nby * nbx;
-    int tn = Co <= 32 ? 1 : (Co <= 64 ? 2 : 4);
-    while (tn > 1 && bricks * cdiv(Co, tn * 32) < 512) tn /= 2;
-    const int nbz2 = (int)cdiv(D, 2 * BRZ);
-    *blocks = (tn == 1 && (int64_t)B * nbz2 * nby * nbx * cdiv(Co, 32) >= 512) ? (int)((int64_t)B * nbz2 * nby * nbx) : (int)bricks;
+    *blocks = (int)conv_variant(SVR_CONV_FWD_F16X3, B, D, H, Wd, Ci, Co).rows;
     return SVR_OK;
   }
   // in == NULL: PREPARE only (W -> scale + split planes in the workspace);  W == NULL: RUN on a workspace prepared earlier
@@ -955,26 +969,42 @@ int fwd_f16x3(const float *in, const float *W, const float *bias, float *out, in
   SVR_CHECK(epilogue == SVR_EPI_NONE || ((epilogue == SVR_EPI_BIAS || epilogue == SVR_EPI_BIAS_RELU) && bias), SVR_E_BADARG,
             "conv3d_fwd_f16x3: epilogue %d", epilogue);
   ConvShape sh{B, D, H, Wd, Ci, Co};
-  const int nbz = (int)cdiv(D, BRZ), nby = (int)cdiv(H, BRY), nbx = (int)cdiv(Wd, BRX);
-  const unsigned bricks = (unsigned)((int64_t)B * nbz * nby * nbx);
+  const ConvVariant v = conv_variant(SVR_CONV_FWD_F16X3, B, D, H, Wd, Ci, Co);
 #define LAUNCH_H3(CKV, TNV)                                                                                                 \
-  hipLaunchKernelGGL((conv3d_brick_x3_kernel<CKV, TNV, 2, true>), dim3(bricks, (unsigned)cdiv(Co, TNV * 32)), dim3(256), 0, s, \
-                     in, p0, ps, bias, out, (const float *)nullptr, sh, nbz, nby, nbx, epilogue, amax, spart)
-  int tn = Co <= 32 ? 1 : (Co <= 64 ? 2 : 4);
-  while (tn > 1 && (int64_t)bricks * cdiv(Co, tn * 32) < 512) tn /= 2;   // see svr_conv3d_k3_bwd_data_bf16x3
-  const int nbz2 = (int)cdiv(D, 2 * BRZ);
-  if (tn == 1 && (int64_t)B * nbz2 * nby * nbx * cdiv(Co, 32) >= 512) {  // two z-slices per wave (8x4x8 bricks, 16-channel chunks)
-    if (persistent_bricks(sh))
-      launch_brick_p<16, true, 2>(in, p0, ps, bias, out, nullptr, sh, nbz2, nby, nbx, (int)cdiv(Co, 32), epilogue, amax, spart, s);
-    else
-    hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, 1, 2, true, 2>), dim3((unsigned)((int64_t)B * nbz2 * nby * nbx), (unsigned)cdiv(Co, 32)),
-                       dim3(256), 0, s, in, p0, ps, bias, out, (const float *)nullptr, sh, nbz2, nby, nbx, epilogue, amax, spart);
-  } else if (Ci % 32 == 0) {
-    if (tn == 1) LAUNCH_H3(32, 1); else if (tn == 2) LAUNCH_H3(32, 2); else LAUNCH_H3(32, 4);
+  hipLaunchKernelGGL((conv3d_brick_x3_kernel<CKV, TNV, 2, true>), dim3((unsigned)v.rows, (unsigned)v.ycols), dim3(256), 0, s, \
+                     in, p0, ps, bias, out, (const float *)nullptr, sh, v.nbz, v.nby, v.nbx, epilogue, amax, spart)
+  if (v.persistent) {
+    launch_brick_p<16, true, 2>(in, p0, ps, bias, out, nullptr, sh, v.nbz, v.nby, v.nbx, v.ycols, epilogue, amax, spart, s);
+  } else if (v.vt == 2) {
+    hipLaunchKernelGGL((conv3d_brick_x3_kernel<16, 1, 2, true, 2>), dim3((unsigned)v.rows, (unsigned)v.ycols), dim3(256), 0, s, in, p0, ps,
+                       bias, out, (const float *)nullptr, sh, v.nbz, v.nby, v.nbx, epilogue, amax, spart);
+  } else if (v.ck == 32) {
+    if (v.tn == 1) LAUNCH_H3(32, 1); else if (v.tn == 2) LAUNCH_H3(32, 2); else LAUNCH_H3(32, 4);
   } else {
-    if (tn == 1) LAUNCH_H3(16, 1); else if (tn == 2) LAUNCH_H3(16, 2); else LAUNCH_H3(16, 4);
+    if (v.tn == 1) LAUNCH_H3(16, 1); else if (v.tn == 2) LAUNCH_H3(16, 2); else LAUNCH_H3(16, 4);
   }
 #undef LAUNCH_H3
   return launch_status("conv3d_fwd_f16x3");
 }
 }  // namespace
+
+// Which kernel instantiation a shape takes (host only, no device memory: callable without a GPU).  The launchers above ask
+// the same conv_variant(), so this cannot drift from what runs.
+extern "C" int svr_conv3d_k3_variant(int32_t op, int32_t B, int32_t D, int32_t H, int32_t Wd, int32_t Ci, int32_t Co, int32_t *ck,
+                                     int32_t *tn, int32_t *vt, int32_t *persistent, int64_t *workgroup_rows) {
+  SVR_CHECK(op >= SVR_CONV_FWD_F16X3 && op <= SVR_CONV_FWD_BF16X6, SVR_E_BADARG, "conv3d_k3_variant: op %d", op);
+  SVR_CHECK(B > 0 && D > 0 && H > 0 && Wd > 0, SVR_E_BADSHAPE, "conv3d_k3_variant: empty volume");
+  const bool fwd = op == SVR_CONV_FWD_F16X3 || op == SVR_CONV_FWD_BF16X6;
+  if (fwd)
+    SVR_CHECK(Ci % 16 == 0 && Ci >= 16 && Co >= 1, SVR_E_UNSUPPORTED, "conv3d_k3_variant: forward needs Ci %% 16 == 0 (Ci=%d Co=%d)", Ci, Co);
+  else
+    SVR_CHECK(Co % 16 == 0 && Co >= 16 && Ci % 2 == 0 && Ci >= 2, SVR_E_UNSUPPORTED,
+              "conv3d_k3_variant: backward-data needs Co %% 16 == 0, Ci even (Ci=%d Co=%d)", Ci, Co);
+  const ConvVariant v = fwd ? conv_variant(op, B, D, H, Wd, Ci, Co) : conv_variant(op, B, D, H, Wd, Co, Ci);
+  if (ck) *ck = v.ck;
+  if (tn) *tn = v.tn;
+  if (vt) *vt = v.vt;
+  if (persistent) *persistent = v.persistent ? 1 : 0;
+  if (workgroup_rows) *workgroup_rows = v.rows;
+  return SVR_OK;
+}

@@ -1013,6 +1013,19 @@ def conv3d_k3_bwd_data(dout, w, mask=None, mode=None):
     return conv3d_k3(dout, wb, mask=mask)
 
 
+CONV_VARIANT_OPS = {"fwd_f16x3": 0, "bwd_data_f16x3s": 1, "bwd_data_bf16x3": 2, "fwd_bf16x6": 3}      # SVR_CONV_* of svr_hip.h
+
+
+def conv3d_k3_variant(op, B, dims, Ci, Co):
+    """The kernel instantiation the split-precision 3x3x3 entry point `op` (a key of CONV_VARIANT_OPS) takes for
+    (B, *dims, Ci -> Co): {"ck", "tn", "vt", "persistent", "workgroup_rows"} (svr_conv3d_k3_variant; host only, no GPU needed)."""
+    D, H, W = dims
+    ck, tn, vt, pers, rows = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    check(_lib.lib().svr_conv3d_k3_variant(CONV_VARIANT_OPS[op], B, D, H, W, Ci, Co, C.byref(ck), C.byref(tn), C.byref(vt),
+                                           C.byref(pers), C.byref(rows)), "conv3d_k3_variant")
+    return {"ck": ck.value, "tn": tn.value, "vt": vt.value, "persistent": bool(pers.value), "workgroup_rows": rows.value}
+
+
 # Arithmetic of the encoder's weight gradients: "bf16x3" (conv3d_bwdw_bf16.hip), "f16x3s" (its scaled f16 form: f32 level)
 # or "f32" (exact-f32 MFMA)
 BACKWARD_CONV_WEIGHT = os.environ.get("SVR_BACKWARD", "f16x3s")

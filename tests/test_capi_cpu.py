@@ -169,3 +169,72 @@ def test_module_copies_and_pickles_after_a_step_left_scratch_state():
     torch.save(m, buf)
     ext.release_step_buffers()
     assert ext._arena.nbytes() == 0
+
+
+def _conv_variants(shapes, persistent_env=None):
+    """svr_conv3d_k3_variant for [(op, B, dims, Ci, Co)] in a child process (persistent_bricks() reads SVR_CONV_PERSISTENT once
+    per process): the variant tags of tests/_conv_cases.py, workgroup rows and svr_conv3d_fwd_f16x3_stats_blocks."""
+    import json
+    import subprocess
+    import sys
+    code = ("import json, sys; sys.path.insert(0, sys.argv[1]); import svr_amd; from svr_amd import ops, _lib; "
+            "from tests import _conv_cases as K; out = []\n"
+            "for op, B, dims, Ci, Co in json.loads(sys.argv[2]):\n"
+            "    v = ops.conv3d_k3_variant(op, B, tuple(dims), Ci, Co)\n"
+            "    out.append([K.tag(v), v['workgroup_rows'], _lib.lib().svr_conv3d_fwd_f16x3_stats_blocks(B, *dims, Ci, Co)])\n"
+            "print('VARIANTS ' + json.dumps(out))")
+    env = {k: v for k, v in os.environ.items() if k != "SVR_CONV_PERSISTENT"}
+    if persistent_env is not None:
+        env["SVR_CONV_PERSISTENT"] = persistent_env
+    r = subprocess.run([sys.executable, "-c", code, REPO, json.dumps(shapes)], env=env, cwd=REPO, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("VARIANTS ")][-1]
+    return json.loads(line[len("VARIANTS "):])
+
+
+def test_conv3d_variant_table_and_every_instantiation_is_reached():
+    """Which kernel of csrc/conv3d_bf16.hip a shape runs, asked of the library (svr_conv3d_k3_variant: the function the
+    launchers themselves call), for the encoder's layers at batch 8 and for every case of tests/test_gpu_conv_paths.py; and the
+    cases of that file, together, reach EVERY instantiation the three launchers can produce.  A case edit that drops a variant
+    fails here, without a GPU."""
+    import __graft_entry__ as ge
+    ge.build()
+    from tests import _conv_cases as K
+    exp = K.expected()
+    got = _conv_variants([(op, B, dims, Ci, Co) for _, op, B, dims, Ci, Co, _ in exp])
+    for (name, op, B, dims, Ci, Co, tag), (gtag, rows, blocks) in zip(exp, got):
+        assert gtag == tag, (name, op, gtag, tag)
+        # the 4 x 4 x 8 bricks of the volume, or its 8 x 4 x 8 double bricks on the two-slices-per-wave tiles
+        bz = 8 if tag in ("P", "VT2") else 4
+        assert rows == B * -(-dims[0] // bz) * -(-dims[1] // 4) * -(-dims[2] // 8), (name, op, rows)
+        if op == "fwd_f16x3":
+            assert blocks == rows, (name, blocks, rows)
+    # the table of DESIGN.md section 4, spelled out once more: (forward, backward-data) of the real layers at batch 8
+    table = {(64, 16, 32): ("P", "P"), (64, 32, 32): ("P", "P"), (32, 32, 64): ("CK32TN2", "P"), (32, 64, 64): ("CK32TN2", "CK32TN2"),
+             (16, 64, 128): ("CK32TN2", "CK32TN1"), (16, 128, 128): ("CK32TN2", "CK32TN2"), (8, 128, 128): ("CK32TN1", "CK32TN1")}
+    real = [K.by_name(n) for n in K.REAL]
+    assert {(c[2][0], c[3], c[4]): (c[6], c[7]) for c in real} == table and all(c[1] == 8 and len(set(c[2])) == 1 for c in real)
+    # the forward bf16x6 entry point: 16-channel chunks, tile width from Co alone (no 512 rule), never persistent
+    x6 = _conv_variants([("fwd_bf16x6", 8, (n, n, n), Ci, Co) for n, Ci, Co in table])
+    assert [t for t, _, _ in x6] == ["CK16TN1", "CK16TN1", "CK16TN2", "CK16TN2", "CK16TN4", "CK16TN4", "CK16TN4"]
+    # SVR_CONV_PERSISTENT=0: every "P" becomes the one-brick form of the same tile, nothing else moves
+    off = _conv_variants([(op, B, dims, Ci, Co) for _, op, B, dims, Ci, Co, _ in exp], persistent_env="0")
+    assert [g[0] for g in off] == ["VT2" if e[-1] == "P" else e[-1] for e in exp]
+    assert [g[1:] for g in off] == [g[1:] for g in got]
+    reached = {(op, tag) for _, op, _, _, _, _, tag in exp}
+    off_cases = {(op, "VT2") for n in K.NO_PERSISTENT for _, op, *_ in [e for e in exp if e[0] == n]}
+    assert off_cases == {(op, "VT2") for op in K.FWD_OPS + K.BWD_OPS}, off_cases      # the child-process cases cover all three too
+    assert reached >= K.ALL_VARIANTS, sorted(K.ALL_VARIANTS - reached)
+    assert len(K.ALL_VARIANTS) == 3 * 8
+
+
+def test_conv3d_variant_refuses_what_the_entry_points_refuse():
+    import svr_amd  # noqa: F401
+    from svr_amd import _lib
+    l = _lib.lib()
+    z = ctypes.c_void_p(0)
+    q = lambda op, *a: l.svr_conv3d_k3_variant(op, *a, z, z, z, z, z)     # noqa: E731  (every output may be NULL)
+    assert q(0, 2, 8, 8, 8, 16, 5) == 0 and q(3, 2, 8, 8, 8, 16, 5) == 0 and q(1, 2, 8, 8, 8, 6, 16) == 0
+    assert q(0, 2, 8, 8, 8, 8, 32) == -4 and q(1, 2, 8, 8, 8, 16, 8) == -4 and q(2, 2, 8, 8, 8, 3, 16) == -4
+    assert q(4, 2, 8, 8, 8, 16, 16) == -1 and q(-1, 2, 8, 8, 8, 16, 16) == -1 and q(0, 2, 0, 8, 8, 16, 16) == -2

@@ -479,7 +479,8 @@ def test_conv3d_backward_at_f32_level_f16x3s(B, dims, Ci, Co, gscale):
     """The encoder's two backward products on the scaled f16 split ("f16x3s": svr_conv3d_k3_bwd_data_f16x3 /
     svr_conv3d_k3_bwd_weight_f16x3) against f64 autograd, with a GRADIENT-like dout (magnitude `gscale`, per-voxel spread
     e^(+-2 sigma): outside f16's range without the scale).  Held to the exact-f32 kernel's gate (3e-6) and to <= 3x its own
-    error; bf16x3 is an order of magnitude away.  The last case takes the persistent 32-column kernel (>= 512 bricks)."""
+    error; bf16x3 is an order of magnitude away.  Every case here has fewer than 512 bricks, i.e. runs conv3d_brick_x3_kernel at TN1
+    (the last one: 72 double bricks); the persistent kernel, its VT2 form, TN2 and TN4 are in tests/test_gpu_conv_paths.py."""
     ops = _ops()
     g = torch.Generator().manual_seed(Ci * 1000 + Co + 7)
     x = F.relu(torch.randn(B, Ci, *dims, generator=g)).requires_grad_(True)
@@ -865,7 +866,8 @@ def test_conv_epilogue_batchnorm_statistics(B, dims, Ci, Co):
     """svr_conv3d_k3_fwd_f16x3_stats + svr_bn_finalize_parts: the BatchNorm that follows a stage's last convolution gets its
     statistics from the convolution kernel's epilogue (per-workgroup f64 partial sums of the values it stores).  Same output
     bits as the plain call; BatchNorm output, pooled output and running statistics equal the separate statistics pass to f32
-    rounding (both sum in f64, in different orders); odd volumes (partial bricks) and every tile variant."""
+    rounding (both sum in f64, in different orders); odd volumes (partial bricks), CK16 and CK32 at TN1 (every case has fewer than
+    512 bricks: the last one 128).  The other tile variants, and the sums against an f64 reference: tests/test_gpu_conv_paths.py."""
     ops = _ops()
     g = torch.Generator().manual_seed(Ci + Co + B)
     x = torch.randn(B, *dims, Ci, generator=g).cuda()
