@@ -652,6 +652,54 @@ int svr_mc_case_table(int8_t *out);
 int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf);
 
 /* ---------------------------------------------------------------------------------------
+ * Mesh evaluation: IoU, Chamfer-L2, normal consistency (replaces what util/evaluate.py:9-119 takes from trimesh --
+ * mesh.sample, face_normals -- and from pykdtree's KDTree.query, and the sampler of data_processing/
+ * mesh_occupancies.py:9-22).  Every rule below is restated in numpy by tests/eval_oracle.py; one rounding per
+ * operation (no contraction).
+ *
+ * svr_mesh_face_table: HOST only.  verts (n_verts,3) float64, faces (n_faces,3) int32; face f = (A, B, C):
+ *     e1 = B - A, e2 = C - A, n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x),
+ *     len = sqrt((nx*nx + ny*ny) + nz*nz), area = 0.5 * len, normals_out[f] = n / len (each component divided);
+ *     a face whose len is not > 0 (zero area, NaN) gets a zero normal and area 0;
+ *     cum_area_out[f] = cum_area_out[f-1] + area, summed sequentially from f = 0 (numpy: np.cumsum).
+ *     SVR_E_BADARG for null pointers, counts <= 0 or a face index outside [0, n_verts).
+ * svr_mesh_sample: tri (n_faces,3,3) float64 = verts[faces], cum_area (n_faces), uniforms (n,3) float64 in [0,1),
+ *     all on the device.  Sample i: x = u0 * cum_area[F-1]; face = the first j with cum_area[j] > x (a face without
+ *     area is never chosen); if there is none (x rounded up to the total), the first j with cum_area[j] >= the total;
+ *     (w1, w2) = (u1, u2), or (1 - u1, 1 - u2) if u1 + u2 > 1;
+ *     p = (A + w1 * (B - A)) + w2 * (C - A) per coordinate in float64, stored as float32.  points_out (n,3) float32,
+ *     face_out (n) int32.  n == 0 is a no-op; n < 0 or n_faces outside [1, 2^31) is SVR_E_BADARG.
+ * svr_nn_search: exact nearest target of every query; queries (Q,3), targets (T,3) float32 on the device.
+ *     d2(q, t) = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)), dx = fl(qx - tx) ..., all float32.  The winner is the
+ *     smallest d2; ties go to the LOWEST target index; a NaN d2 never wins against a number (+inf is a number).
+ *     dist_out[q] = sqrt(d2) correctly rounded to float32, idx_out[q] = the winner.  A query all of whose d2 are NaN
+ *     gets dist NaN and idx -1.  The result does not depend on how the work is split: bit-identical run to run.
+ *     workspace: svr_nn_search_workspace(Q) = 8 * Q bytes on the device.  T == 0 or T >= 2^31: SVR_E_BADSHAPE;
+ *     Q < 0, a null pointer or a short workspace: SVR_E_BADARG; Q == 0: no-op.
+ * svr_nn_normals_dot: dot_out[q] = |n_q / |n_q|  .  n_t[idx[q]] / |n_t[idx[q]]||  in float64 (normals_f64 = 0: both
+ *     normal arrays are float32 and are widened first; 1: float64); |n| = sqrt((x*x + y*y) + z*z), the dot is
+ *     (x*x' + y*y') + z*z'.  idx[q] outside [0, T) gives NaN.
+ * svr_eval_sums: sums_out[3] (device float64) = sum d, sum d*d (d widened to float64 first), sum dot (NaN when
+ *     dot == NULL), over n entries, in a fixed order (fixed grid, fixed trees): bit-identical run to run.
+ *     workspace: SVR_EVAL_SUMS_WORKSPACE_BYTES on the device.
+ * svr_iou_counts: counts_out[2] (device int64) = number of i with a[i] && b[i], with a[i] || b[i] (uint8, 0 = false).
+ * All argument checks return before the first HIP call.
+ * ------------------------------------------------------------------------------------- */
+#define SVR_EVAL_SUMS_WORKSPACE_BYTES 6144
+int svr_mesh_face_table(const double *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, double *normals_out,
+                        double *cum_area_out);
+int svr_mesh_sample(const double *tri, const double *cum_area, int64_t n_faces, const double *uniforms, int64_t n,
+                    float *points_out, int32_t *face_out, void *stream);
+int64_t svr_nn_search_workspace(int64_t Q);
+int svr_nn_search(const float *queries, int64_t Q, const float *targets, int64_t T, float *dist_out, int32_t *idx_out,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+int svr_nn_normals_dot(const void *normals_q, const void *normals_t, int32_t normals_f64, const int32_t *idx, int64_t Q,
+                       int64_t T, double *dot_out, void *stream);
+int svr_eval_sums(const float *dist, const double *dot, int64_t n, double *sums_out, void *workspace, int64_t workspace_bytes,
+                  void *stream);
+int svr_iou_counts(const uint8_t *a, const uint8_t *b, int64_t n, int64_t *counts_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * Host side (plain C++ + zlib; `out` / `payload` are HOST buffers, ideally pinned):

@@ -36,6 +36,7 @@ class GatherDesc(C.Structure):
 
 
 GATHER_WIDE_OFFSETS, GATHER_DETERMINISTIC = 1, 2
+EVAL_SUMS_WORKSPACE_BYTES = 6144      # SVR_EVAL_SUMS_WORKSPACE_BYTES
 
 
 # name -> (restype, argtypes): exactly the declarations of include/svr_hip.h
@@ -145,6 +146,13 @@ SIGNATURES = {
     "svr_mesh_hash_entries": (I64, [P, I64, P, I64, I32, P]),
     "svr_mesh_hash_build": (C.c_int, [P, I64, P, I64, I32, P, P, P, I64]),
     "svr_mesh_contains": (C.c_int, [P, I32, I64, P, P, P, I32, P, P, P, P]),
+    "svr_mesh_face_table": (C.c_int, [P, I64, P, I64, P, P]),
+    "svr_mesh_sample": (C.c_int, [P, P, I64, P, I64, P, P, P]),
+    "svr_nn_search_workspace": (I64, [I64]),
+    "svr_nn_search": (C.c_int, [P, I64, P, I64, P, P, P, I64, P]),
+    "svr_nn_normals_dot": (C.c_int, [P, P, I32, P, I64, I64, P, P]),
+    "svr_eval_sums": (C.c_int, [P, P, I64, P, P, I64, P]),
+    "svr_iou_counts": (C.c_int, [P, P, I64, P, P]),
     "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),

@@ -35,6 +35,7 @@ SOURCES = {
     "bf16_path.hip": ["-ffp-contract=off"],
     "mesh_occupancy.hip": ["-ffp-contract=off"],
     "marching_cubes.hip": ["-ffp-contract=off"],
+    "mesh_eval.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "conv2d.hip": [],
     "conv2d_igemm.hip": [],

@@ -9,7 +9,10 @@ parsed once (small LRU cache keyed by path + mtime), hashed by the library's C++
 Reference quirk, preserved by default (`reference_quirk=True`): lines :29-31 ASSIGN dims[i] to the point coordinates
 instead of dividing by it, so every query point becomes (dims[0], dims[1], dims[2]) -- outside every normalised mesh --
 and the returned occupancies are all zero.  `reference_quirk=False` applies the normalisation the comment describes
-(points - dims/2, / dims)."""
+(points - dims/2, / dims).
+
+``sample_points(mesh_path, dims, sample_num, sigma)`` mirrors :9-22 (the training samples of one mesh: surface samples
+plus noise, 10 % uniform points, their grid coordinates and occupancies) on util.evaluate's surface sampler."""
 import functools
 import os
 from types import SimpleNamespace
@@ -53,6 +56,30 @@ def _as_mesh(m):
     if isinstance(m, (tuple, list)) and len(m) == 2:
         return SimpleNamespace(vertices=np.asarray(m[0]), faces=np.asarray(m[1]))
     return m
+
+
+def sample_points(mesh_path, dims, sample_num, sigma, generator=None):
+    """-> (boundary_points (M,3) float64, occupancies (M,) bool, grid_coords (M,3) float64) on the device,
+    M = sample_num + int(0.1 * sample_num).  The mesh (path, loaded mesh or (V, F) pair, in grid units) is translated by
+    -dims/2 and scaled by 1/dims; `sample_num` area-weighted surface samples (float32, as util.evaluate.sample_surface
+    stores them) get sigma * N(0, 1) noise, int(0.1 * sample_num) points uniform in [-0.5, 0.5)^3 follow; grid_coords
+    swaps x and z and doubles; the labels come from implicit_waterproofing.  `generator` (torch.Generator) drives, in this
+    order, the surface uniforms, the normal noise and the uniform points, all drawn on the device in float64."""
+    from ..util.evaluate import EvalMesh, _device_generator, sample_with_uniforms
+    mesh = _as_mesh(mesh_path)
+    total_size = np.array(dims)
+    norm = EvalMesh(SimpleNamespace(vertices=(np.asarray(mesh.vertices, dtype=np.float64) + (-total_size / 2)) * (1 / total_size),
+                                    faces=mesh.faces))
+    dev = norm.device
+    g = _device_generator(generator, dev)
+    sample_num = int(sample_num)
+    points = sample_with_uniforms(norm, torch.rand((sample_num, 3), device=dev, dtype=torch.float64, generator=g))[0]
+    boundary_points = points.double() + sigma * torch.randn((sample_num, 3), device=dev, dtype=torch.float64, generator=g)
+    random_points = torch.rand((int(sample_num * 0.1), 3), device=dev, dtype=torch.float64, generator=g) - 0.5
+    boundary_points = torch.cat((boundary_points, random_points), dim=0)
+    grid_coords = 2 * boundary_points.flip(1)
+    occupancies = implicit_waterproofing(norm, boundary_points)[0]
+    return boundary_points, occupancies, grid_coords
 
 
 def determine_occupancy(mesh_path, points, dims=(139, 104, 112), reference_quirk=True, points_normalized=False):

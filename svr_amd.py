@@ -23,15 +23,19 @@ class _AliasLoader(importlib.abc.Loader):
     def exec_module(self, module):          # already executed under its real name
         pass
 
+    def get_code(self, fullname):           # `python -m svr_amd.<module>` (runpy asks the loader for the code)
+        return importlib.util.find_spec(self.real).loader.get_code(self.real)
+
 
 class _AliasFinder(importlib.abc.MetaPathFinder):
     def find_spec(self, fullname, path=None, target=None):
         if not fullname.startswith(__name__ + "."):
             return None
         real = _REAL + fullname[len(__name__):]
-        if importlib.util.find_spec(real) is None:
+        real_spec = importlib.util.find_spec(real)
+        if real_spec is None:
             return None
-        return importlib.util.spec_from_loader(fullname, _AliasLoader(real))
+        return importlib.util.spec_from_loader(fullname, _AliasLoader(real), origin=real_spec.origin)
 
 
 if not any(isinstance(f, _AliasFinder) for f in sys.meta_path):
