@@ -14,23 +14,18 @@ LIB = os.path.join(LIBDIR, "libsvr_hip.so")
 # compiled with FP contraction off (see gather.hip / projection.hip headers).
 SOURCES = {
     "capi.cpp": [],
-    "gather.hip": ["-ffp-contract=off"] + ["-D" + d for d in os.environ.get("SVR_GATHER_DEFS", "").split()],   # experiments
-    "gather_fc0.hip": ["-ffp-contract=off"] + [f"-D{k}={os.environ[e]}" for k, e in (("FC_TM", "SVR_FC_TM"), ("FC_DEPTH", "SVR_FC_DEPTH"), ("FC_FMA", "SVR_FC_FMA"))
-                                               if os.environ.get(e)]    # tile-shape experiments
-                      + (["-DSVR_FC0_MEASURE"] if os.environ.get("SVR_FC0_MEASURE") else [])   # role switches (SVR_FC0_DBG)
-                      + ["-D" + d for d in os.environ.get("SVR_FC_DEFS", "").split()]   # experiments: SVR_FC_DEFS="FC_PRIO=1 FC_PK=0"
-                      + (["-fno-slp-vectorize"] if "FC_PK=0" in os.environ.get("SVR_FC_DEFS", "").split() else []),
+    "gather.hip": ["-ffp-contract=off"],
+    "gather_fc0.hip": ["-ffp-contract=off"],
     "sort.hip": [],
     "gemm.hip": [],
     "gemm_bf16x3.hip": [],
     "gemm_bf16x6.hip": [],
     "gemm_f16x3.hip": [],
     "conv3d.hip": [],
-    "conv3d_bf16.hip": ([f"-DSVR_CONV_EXP={os.environ['SVR_CONV_EXP']}"] if os.environ.get("SVR_CONV_EXP") else [])   # measurement builds
-                       + ["-D" + d for d in os.environ.get("SVR_CONV_DEFS", "").split()],
-    "conv3d_bwdw_bf16.hip": [f"-DSVR_WG_EXP={os.environ['SVR_WG_EXP']}"] if os.environ.get("SVR_WG_EXP") else [],   # measurement builds
+    "conv3d_bf16.hip": [],
+    "conv3d_bwdw_bf16.hip": [],
     "bn_pool.hip": [],
-    "stage1.hip": [f"-DS1_EXP={os.environ['SVR_S1_EXP']}"] if os.environ.get("SVR_S1_EXP") else [],   # measurement builds
+    "stage1.hip": [],
     "projection.hip": ["-ffp-contract=off"],
     "bf16_path.hip": ["-ffp-contract=off"],
     "mesh_occupancy.hip": ["-ffp-contract=off"],
@@ -74,7 +69,7 @@ def build(force=False, verbose=False):
         obj = os.path.join(objdir, src.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
         cmd = [_hipcc()] + COMMON + extra + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", path, "-o", obj]
-        # an object built with other flags (a measurement build, SVR_*_EXP) is stale even if the source did not change
+        # an object built with another command line (other COMMON flags, another compiler) is stale even if the source did not change
         flagfile = obj[:-2] + ".flags"
         same_flags = os.path.exists(flagfile) and open(flagfile).read() == " ".join(cmd)
         if force or not same_flags or _stale(obj, [path] + headers):

@@ -423,14 +423,11 @@ int ig_check(const svr_conv2d_desc *d, int Cout, const char *what) {
 
 // reduction splits: enough workgroups to fill the chip (512 four-wave or 1 024 two-wave ones: two waves per SIMD -- a k-step is a
 // dependent chain load -> split -> LDS -> MFMA, and with one wave per SIMD the 512-tile layers ran at 2.8 us per k-step;
-// tools/exp/unet_target.sh), at least 8 k-steps each
+// profiles/r04_unet_split_target.txt), at least 8 k-steps each
 int ig_splits(int64_t tiles, int ksteps, int n_out, int *ksplit) {
-  static const int forced_target = getenv("SVR_IG_TARGET") ? atoi(getenv("SVR_IG_TARGET")) : 0;   // measurement switch
-  const int target = forced_target > 0 ? forced_target : (n_out <= 64 ? 1024 : 512);
+  const int target = n_out <= 64 ? 1024 : 512;
   int splits = (int)std::min<int64_t>(std::max<int64_t>(1, target / std::max<int64_t>(tiles, 1)), std::max(1, ksteps / 8));
   splits = std::min(splits, 64);
-  static const int forced = getenv("SVR_IG_SPLITS") ? atoi(getenv("SVR_IG_SPLITS")) : 0;   // measurement switch
-  if (forced > 0) splits = std::min(forced, ksteps);
   *ksplit = (int)cdiv(ksteps, splits);
   return (int)cdiv(ksteps, *ksplit);
 }

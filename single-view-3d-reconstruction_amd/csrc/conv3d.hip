@@ -872,12 +872,11 @@ extern "C" int svr_conv3d_k3(const float *in, const float *Wp, const float *bias
   if (Co == 1) {
     SVR_CHECK(epilogue == SVR_EPI_NONE, SVR_E_UNSUPPORTED, "conv3d: Co=1 supports no epilogue");
     unsigned grid = (unsigned)cdiv(M, 256);
-    static const int to1_col = getenv("SVR_TO1_COL") ? atoi(getenv("SVR_TO1_COL")) : 1;   // measurement switch: 0 = one output per thread
     constexpr int ZT = 8;
     const int nzb = (int)cdiv(D, ZT), nxb16 = (int)cdiv(W, 16), nxb32 = (int)cdiv(W, 8);
-    if (to1_col && Ci == 16 && (((uintptr_t)in) & 15) == 0)
+    if (Ci == 16 && (((uintptr_t)in) & 15) == 0)
       hipLaunchKernelGGL((conv3d_to1_col_kernel<16, ZT>), dim3((unsigned)cdiv((int64_t)B * nzb * H * nxb16, 4)), dim3(256), 0, s, in, Wp, out, sh, nxb16, nzb);
-    else if (to1_col && Ci == 32 && (((uintptr_t)in) & 15) == 0)
+    else if (Ci == 32 && (((uintptr_t)in) & 15) == 0)
       hipLaunchKernelGGL((conv3d_to1_col_kernel<32, ZT>), dim3((unsigned)cdiv((int64_t)B * nzb * H * nxb32, 4)), dim3(256), 0, s, in, Wp, out, sh, nxb32, nzb);
     else if (Ci == 16) hipLaunchKernelGGL(conv3d_to1_kernel<16>, dim3(grid), dim3(256), 0, s, in, Wp, out, sh);
     else if (Ci == 32) hipLaunchKernelGGL(conv3d_to1_kernel<32>, dim3(grid), dim3(256), 0, s, in, Wp, out, sh);

@@ -209,13 +209,8 @@ __global__ __launch_bounds__(256) void conv3d_brick_x3_kernel(const float *__res
       const bool ok = idx < PIECES && n0 + row < s.Co;
       const uint16_t *base = P0 + (ok ? pl : 0) * plane_stride;
       const uint2 *p = reinterpret_cast<const uint2 *>(base + ((size_t)(tap0 + (ok ? tg : 0)) * s.Co + (ok ? n0 + row : 0)) * s.Ci + k0 + part * 8);
-#if defined(SVR_CONV_EXP) && SVR_CONV_EXP == 4   // measurement build: no weight loads
-      wreg[i][0] = make_uint2((uint32_t)idx, 0x3c003c00u);
-      wreg[i][1] = make_uint2(0x3c003c00u, (uint32_t)(uintptr_t)p);
-#else
       wreg[i][0] = p[0];  // unconditional (clamped to piece 0 when out of range: those columns are never stored)
       wreg[i][1] = p[1];
-#endif
     }
   };
   auto wstore = [&](const uint2 (&wreg)[WPT][2], int buf) {
@@ -247,11 +242,7 @@ __global__ __launch_bounds__(256) void conv3d_brick_x3_kernel(const float *__res
       const int gz = z0 + hz - 1, gy = y0 + hy - 1, gx = x0 + hx - 1;
       if (gz >= 0 && gz < s.D && gy >= 0 && gy < s.H && gx >= 0 && gx < s.W) hok |= 1ull << i;
       const int cz = min(max(gz, 0), s.D - 1), cy = min(max(gy, 0), s.H - 1), cx = min(max(gx, 0), s.W - 1);
-#if defined(SVR_CONV_EXP) && SVR_CONV_EXP == 3   // measurement build: no halo loads (a constant instead)
-      hreg[i] = make_float4((float)cz, 1.f, 2.f, 3.f);
-#else
       hreg[i] = *reinterpret_cast<const float4 *>(inb + (((int64_t)cz * s.H + cy) * s.W + cx) * s.Ci + k0 + c4);
-#endif
     }
 #pragma unroll
     for (int i = 0; i < HIT; ++i) {
@@ -260,11 +251,7 @@ __global__ __launch_bounds__(256) void conv3d_brick_x3_kernel(const float *__res
       const int hv = idx / (CK / 4), c4 = (idx % (CK / 4)) * 4;
       const int hd = slot_dw<SL>((hv / HLX) * HP + hv % HLX, c4 / 8) + (c4 % 8) / 2;   // (hz*HLY + hy)*HP + hx; half a slot
       const bool ok = (hok >> i) & 1ull;
-#if defined(SVR_CONV_EXP) && SVR_CONV_EXP == 5   // measurement build: the halo loads are issued but nobody waits for them here
-      const float4 v = make_float4(ok ? (float)hv : 0.f, 1.f, 2.f, ok ? 3.f : 0.f);
-#else
       const float4 v = make_float4(ok ? hreg[i].x : 0.f, ok ? hreg[i].y : 0.f, ok ? hreg[i].z : 0.f, ok ? hreg[i].w : 0.f);
-#endif
       uint32_t h0, m0, l0 = 0, h1, m1, l1 = 0;
       if constexpr (NP == 3) {
         split3(v.x, v.y, h0, m0, l0);
@@ -289,11 +276,7 @@ __global__ __launch_bounds__(256) void conv3d_brick_x3_kernel(const float *__res
 #pragma unroll
       for (int tg = 0; tg < TG; ++tg) {
         const int tap = tap0 + tg;
-#if defined(SVR_CONV_EXP) && SVR_CONV_EXP == 1   // measurement build: the three dx taps read ONE fragment (wrong results)
-        const int arow = hrow + ((tap / 9 - 1) * HLY + ((tap / 3) % 3 - 1)) * HP;
-#else
         const int arow = hrow + ((tap / 9 - 1) * HLY + ((tap / 3) % 3 - 1)) * HP + (tap % 3 - 1);
-#endif
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const int sub = ks * 2 + lh;
@@ -316,13 +299,9 @@ __global__ __launch_bounds__(256) void conv3d_brick_x3_kernel(const float *__res
               const f16x8 wq = scale_2m11(wh);
 #pragma unroll
               for (int v = 0; v < VT; ++v) {
-#if defined(SVR_CONV_EXP) && SVR_CONV_EXP == 2   // measurement build: no matrix instructions (the fragments are still read)
-                acc[v][j][0] += (float)xl[v][0] * (float)wq[0] + (float)xh[v][1] * (float)wl[1] + (float)wh[2];
-#else
                 acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl[v], wq, acc[v][j], 0, 0, 0);
                 acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[v], wl, acc[v][j], 0, 0, 0);
                 acc[v][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[v], wh, acc[v][j], 0, 0, 0);
-#endif
               }
             }
             continue;
@@ -360,10 +339,6 @@ __global__ __launch_bounds__(256) void conv3d_brick_x3_kernel(const float *__res
       step(st, wregB, wregA);
       if (st + 1 < STEPS) step(st + 1, wregA, wregB);
     }
-#if defined(SVR_CONV_EXP) && SVR_CONV_EXP == 5   // ... the loads land behind the chunk's MFMAs
-#pragma unroll
-    for (int i = 0; i < HIT; ++i) asm volatile("" ::"v"(hreg[i].x), "v"(hreg[i].y), "v"(hreg[i].z), "v"(hreg[i].w));
-#endif
   }
   // BatchNorm statistics of what this workgroup stores (spart: per-workgroup partial sums [brick][2][Co] in f64): the
   // stage's last convolution delivers them and the separate statistics pass over its output disappears
@@ -399,13 +374,9 @@ __global__ __launch_bounds__(256) void conv3d_brick_x3_kernel(const float *__res
         float val = (F16 ? acc[v][j][r] * inv : acc[v][j][r]) + bv;
         if (mode == SVR_EPI_BIAS_RELU) val = fmaxf(val, 0.f);
         if (mode == SVR_EPI_MASK) val = mk[r] > 0.f ? val : 0.f;
-#ifndef SVR_CONV_NO_NT
         // streaming store: the layer's output (268 MB at 64^3 x 32) should not push the halo voxels its neighbours re-read out of
         // L2 (conv forward 1.39 -> 1.37, backward-data 1.54 -> 1.52 ms per step)
         __builtin_nontemporal_store(val, out + o);
-#else
-        out[o] = val;
-#endif
         ssum[j] += val;
         ssq[j] = fmaf(val, val, ssq[j]);
         vmax = fmaxf(vmax, fabsf(val));
@@ -440,7 +411,8 @@ svr_amax_publish(amax_out, vmax);
 
 // ---------------------------------------------------------------------------------------------------------------------
 // PERSISTENT form of the brick kernel for 32 output columns (TNB = 1), round 3.  Measurement builds of the kernel above
-// (tools/exp/conv_variants.sh, SVR_CONV_EXP = 2 / 3 / 5) showed that at 64^3 the matrix instructions are completely hidden
+// (no MFMAs / no halo loads / halo loads not waited for: profiles/r03_conv_variants.txt; no longer in
+// the tree) showed that at 64^3 the matrix instructions are completely hidden
 // (no MFMAs: same time), that the halo tile's global loads cost 19-23 % and that half of that is the WAIT for them: a
 // workgroup that stages a chunk computes nothing, and with two workgroups per CU the other one then has each SIMD to itself,
 // one wave that stalls on every LDS fragment read.  Here a workgroup walks bricks (grid = the resident workgroups) and the
@@ -627,11 +599,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_brick_p_kernel(const float *__r
           float val = (F16 ? acc[v][r] * inv : acc[v][r]) + bv;
           if (mode == SVR_EPI_BIAS_RELU) val = fmaxf(val, 0.f);
           if (mode == SVR_EPI_MASK) val = mk[r] > 0.f ? val : 0.f;
-#ifndef SVR_CONV_NO_NT
           __builtin_nontemporal_store(val, reinterpret_cast<float *>(outb + off[r]));
-#else
-          *reinterpret_cast<float *>(outb + off[r]) = val;
-#endif
           ssum += val;
           ssq = fmaf(val, val, ssq);
           vmax = fmaxf(vmax, fabsf(val));

@@ -56,11 +56,6 @@ static_assert(IN_IT == 3 && DO_ITEMS == NT, "prefetch phases below are written f
 constexpr int TAPS_PER_WAVE = 7;                  // 27 taps over 4 tap groups: 7 / 7 / 7 / 6
 
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t &hi, uint32_t &mid) {
-#if defined(SVR_WG_EXP) && SVR_WG_EXP == 3   // measurement build: no split arithmetic
-  hi = __float_as_uint(x0);
-  mid = __float_as_uint(x1);
-  return;
-#endif
   f32x2 v = {x0, x1};
   bf16x2 h = __builtin_convertvector(v, bf16x2);
   hi = __builtin_bit_cast(uint32_t, h);
@@ -110,9 +105,6 @@ __device__ __forceinline__ void wgrad_rows(const uint32_t *__restrict__ ibuf, co
                                 : frag(__builtin_amdgcn_alignbit(h01.y, h01.x, 16), __builtin_amdgcn_alignbit(h23.x, h01.y, 16),
                                        __builtin_amdgcn_alignbit(h23.y, h23.x, 16), __builtin_amdgcn_alignbit(h4, h23.y, 16));
       // mid plane of the input x hi plane of dout first (small terms first)
-#if defined(SVR_WG_EXP) && SVR_WG_EXP == 1   // measurement build: no matrix instructions (fragments still read and shifted)
-      acc[i][0] += (float)am[0] * (float)b_hi[1] + (float)ah[2] * (float)b_mid[3] + (float)ah[7];
-#else
       if constexpr (F16) {
         const f16x8 fam = __builtin_bit_cast(f16x8, am), fah = __builtin_bit_cast(f16x8, ah);
         const f16x8 fbh = __builtin_bit_cast(f16x8, b_hi), fbm = __builtin_bit_cast(f16x8, b_mid);
@@ -124,7 +116,6 @@ __device__ __forceinline__ void wgrad_rows(const uint32_t *__restrict__ ibuf, co
       acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b_mid, acc[i], 0, 0, 0);
       acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b_hi, acc[i], 0, 0, 0);
       }
-#endif
     }
   }
 }
@@ -175,13 +166,8 @@ __global__ __launch_bounds__(NT) void conv3d_bwd_weight_x3_kernel(const float *_
       // (uniform base + 32-bit byte offsets, 24-bit multiplies: the host checks the ranges)
       const uint32_t ro = __umul24(__umul24(__umul24((uint32_t)cz, (uint32_t)s.H) + (uint32_t)cy, (uint32_t)s.W), (uint32_t)s.Ci) + (uint32_t)cc;
       const char *p = reinterpret_cast<const char *>(inb);
-#if defined(SVR_WG_EXP) && SVR_WG_EXP == 2   // measurement build: no global loads of the next brick
-      ia[j][0] = make_float4((float)idx, 1.f, (float)brick, 3.f);
-      ia[j][1] = make_float4((float)(uintptr_t)p, 1.f, 2.f, 3.f);
-#else
       ia[j][0] = *reinterpret_cast<const float4 *>(p + (ro + __umul24((uint32_t)min(max(gx, 0), s.W - 1), (uint32_t)s.Ci)) * 4u);
       ia[j][1] = *reinterpret_cast<const float4 *>(p + (ro + __umul24((uint32_t)min(max(gx + 1, 0), s.W - 1), (uint32_t)s.Ci)) * 4u);
-#endif
       iok[j] = (rowok && gx >= 0 && gx < s.W ? 1 : 0) | (rowok && gx + 1 >= 0 && gx + 1 < s.W ? 2 : 0);
     }
     if (ph == 1) {
@@ -192,13 +178,8 @@ __global__ __launch_bounds__(NT) void conv3d_bwd_weight_x3_kernel(const float *_
       const int cz = min(gz, s.D - 1), cy = min(gy, s.H - 1), cc = min(co0 + cg * 4, s.Co - 4);
       const uint32_t ro = __umul24(__umul24(__umul24((uint32_t)cz, (uint32_t)s.H) + (uint32_t)cy, (uint32_t)s.W), (uint32_t)s.Co) + (uint32_t)cc;
       const char *p = reinterpret_cast<const char *>(dob);
-#if defined(SVR_WG_EXP) && SVR_WG_EXP == 2
-      da[0] = make_float4((float)t, 1.f, (float)brick, 3.f);
-      da[1] = make_float4((float)(uintptr_t)p, 1.f, 2.f, 3.f);
-#else
       da[0] = *reinterpret_cast<const float4 *>(p + (ro + __umul24((uint32_t)min(gx, s.W - 1), (uint32_t)s.Co)) * 4u);
       da[1] = *reinterpret_cast<const float4 *>(p + (ro + __umul24((uint32_t)min(gx + 1, s.W - 1), (uint32_t)s.Co)) * 4u);
-#endif
       dok = (rowok && gx < s.W ? 1 : 0) | (rowok && gx + 1 < s.W ? 2 : 0);
     }
   };

@@ -180,15 +180,11 @@ __device__ __forceinline__ void gather_fwd_shared_body(const LevelArgs L, const 
       }
     }
     if (I.m & 0x100) {
-#ifndef SVR_GATHER_NO_NT
       // streaming stores: the rows (4.2 GB at config 3) are never read back by this kernel, and as ordinary stores they pushed the
       // volumes' lines out of L2 -- 2.16 -> 1.90 ms stand-alone (tools/exp/bench_fc0.py)
       float *o = feat + I.ro + q4;
       __builtin_nontemporal_store(acc.x, o); __builtin_nontemporal_store(acc.y, o + 1);
       __builtin_nontemporal_store(acc.z, o + 2); __builtin_nontemporal_store(acc.w, o + 3);
-#else
-      *reinterpret_cast<float4 *>(feat + I.ro + q4) = acc;
-#endif
       if ((I.m & 0x200) && q4 == 0) {
         float *row = feat + (I.ro - L.col);  // j == 0: ro = row start + L.col
         for (int cc = pad_start; cc < row_stride; ++cc) row[cc] = 0.f;

@@ -461,12 +461,12 @@ __device__ __forceinline__ bf16x8 tr_frag(const uint32_t *plane, int byte0, int 
 
 // Both operands row-major through the transposing read: dY needs no pre-pass either (ATR); the bias gradient is the
 // column sum of the dY rows the K-tile-0 workgroups load anyway.
-// STAGES = 2: two LDS stages, ONE barrier per k-step -- the split + LDS stores of step k+1 sit in the same barrier
-// interval as the MFMAs of step k (the forward kernel's pipeline); STAGES = 1: store after the MFMAs, two barriers.
-// Measured at 400 000 x 256 x 2592 (round 2): 2.57 vs 2.59 ms -- and two register sets on top (loads two MFMA phases
+// ONE LDS stage: store after the MFMAs, two barriers per k-step.  A form with two LDS stages and ONE barrier per k-step (the
+// split + LDS stores of step k+1 in the same barrier interval as the MFMAs of step k, the forward kernel's pipeline) was
+// measured at 400 000 x 256 x 2592 (round 2): 2.57 vs 2.59 ms -- and two register sets on top (loads two MFMA phases
 // ahead, 246 VGPRs) 2.57 vs 2.51, three sets spill (10.8 ms).  Neither the barrier count nor the load latency binds
 // this kernel; per k-step a wave issues ~110 VALU instructions for the bf16 splits and 16 ds_write_b64 against 24 MFMAs
-// (768 cycles), and the LDS pipe of a CU is ~80 % busy relative to its matrix pipes.  SVR_TN_STAGES=2 selects it.
+// (768 cycles), and the LDS pipe of a CU is ~80 % busy relative to its matrix pipes.  The two-stage form was dropped.
 // F16 ("f16x3s", svr_linear_bwd_weight_f16x3): the scaled f16 split instead of the bf16 one -- dY is multiplied by 2^s (amax_dy:
 // its |max| brought to [2^13, 2^14), exact), both operands split into hi = rn16(v) and lo' = rn16((v - hi) 2^11), products
 // hi hi + (hi 2^-11) lo' + lo' (hi 2^-11) with the 2^-11 applied to the hi FRAGMENTS in registers (v_pk_mul_f16), result * 2^-s:
@@ -482,13 +482,13 @@ struct CwGeom {
   float rWo, rHoWo;
   int k, stride, pad, Cpad;
 };
-template <int STAGES, bool F16 = false, bool CONV = false, bool VEC4 = true>
+template <bool F16 = false, bool CONV = false, bool VEC4 = true>
 __global__ __launch_bounds__(256, 2) void linear_tn_x3_tr_kernel(const float *__restrict__ dY, int64_t lddy,
                                                               const float *__restrict__ X, int64_t ldx,
                                                               float *__restrict__ slab, float *__restrict__ dbpart,
                                                               int64_t M, int64_t N, int64_t K, int64_t rows_per_split,
                                                               int splits, const uint32_t *__restrict__ amax_dy, const CwGeom G) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[STAGES * 4 * TR_XPLANE];  // per stage: dY hi, dY mid, X hi, X mid: [32 m][128 cols]
+  __shared__ __attribute__((aligned(16))) uint32_t lds[4 * TR_XPLANE];  // dY hi, dY mid, X hi, X mid: [32 m][128 cols]
   uint32_t *la = lds, *lx = lds + 2 * TR_XPLANE;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wr = wave >> 1, wc = wave & 1, lh = lane >> 5;
@@ -537,8 +537,7 @@ __global__ __launch_bounds__(256, 2) void linear_tn_x3_tr_kernel(const float *__
   float4 dbs = make_float4(0.f, 0.f, 0.f, 0.f);
   float sy = 1.f;
   if constexpr (F16) sy = amax_dy ? w_scale(amax_dy[0], false) : 1.f;
-  auto lstore = [&](int64_t k0, int stage) {
-    uint32_t *la = lds + stage * 4 * TR_XPLANE, *lx = la + 2 * TR_XPLANE;
+  auto lstore = [&](int64_t k0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = (t >> 5) + 8 * i;
@@ -593,8 +592,7 @@ __global__ __launch_bounds__(256, 2) void linear_tn_x3_tr_kernel(const float *__
   // CONV: output-channel counts of 32 / 64 fill a quarter / half of the tile's 128 rows -- the waves (and the 32-row blocks) past the
   // last valid row skip their fragment reads and matrix instructions (uniform per wave)
   const int nrows_valid = CONV ? (int)min<int64_t>(N - i0, (int64_t)TN_TM) - wr * 64 : 64;
-  auto mma = [&](int stage) {
-    const uint32_t *la = lds + stage * 4 * TR_XPLANE, *lx = la + 2 * TR_XPLANE;
+  auto mma = [&]() {
     if constexpr (CONV) {
       if (nrows_valid <= 0) return;
     }
@@ -645,28 +643,16 @@ __global__ __launch_bounds__(256, 2) void linear_tn_x3_tr_kernel(const float *__
   };
   if (kbeg < kend) {
     gload(kbeg);
-    lstore(kbeg, 0);
+    lstore(kbeg);
     __syncthreads();
-    if constexpr (STAGES == 2) {
-      if (kbeg + XK < kend) gload(kbeg + XK);   // registers hold step k+1 while step k is multiplied
-      int st = 0;
-      for (int64_t k0 = kbeg; k0 < kend; k0 += XK, st ^= 1) {
-        const bool more = k0 + XK < kend;
-        if (more) lstore(k0 + XK, st ^ 1);       // stage st^1 was last read in step k-1: free since the barrier
-        if (k0 + 2 * XK < kend) gload(k0 + 2 * XK);
-        mma(st);
-        __syncthreads();
-      }
-    } else {
-      for (int64_t k0 = kbeg; k0 < kend; k0 += XK) {
-        const bool more = k0 + XK < kend;
-        if (more) gload(k0 + XK);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(0);
-        __syncthreads();  // every wave has read its fragments
-        if (more) lstore(k0 + XK, 0);
-        __syncthreads();
-      }
+    for (int64_t k0 = kbeg; k0 < kend; k0 += XK) {
+      const bool more = k0 + XK < kend;
+      if (more) gload(k0 + XK);
+      __builtin_amdgcn_sched_barrier(0);
+      mma();
+      __syncthreads();  // every wave has read its fragments
+      if (more) lstore(k0 + XK);
+      __syncthreads();
     }
   }
   float *out = slab + split * N * K;
@@ -874,13 +860,8 @@ extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
   if (K % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)X & 15) == 0 && N >= 4 && K >= 4) {
     // both operands row-major, transposing LDS reads: no pre-pass over dY; db from the K-tile-0 workgroups
-    static const int tr_stages = getenv("SVR_TN_STAGES") ? atoi(getenv("SVR_TN_STAGES")) : 1;   // measurement switch
-    if (tr_stages == 2)
-      hipLaunchKernelGGL(linear_tn_x3_tr_kernel<2>, grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
-                         rps, splits, (const uint32_t *)nullptr, CwGeom{});
-    else
-      hipLaunchKernelGGL(linear_tn_x3_tr_kernel<1>, grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
-                         rps, splits, (const uint32_t *)nullptr, CwGeom{});
+    hipLaunchKernelGGL(linear_tn_x3_tr_kernel<>, grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
+                       rps, splits, (const uint32_t *)nullptr, CwGeom{});
     hipLaunchKernelGGL(slab_reduce_x3_kernel, dim3((unsigned)cdiv(N * K, 64)), dim3(256), 0, s, slab, dW, N, K, lddw, splits);
     if (db) hipLaunchKernelGGL(dy_db_reduce_kernel, dim3((unsigned)N), dim3(256), 0, s, dbpart, db, N, (int64_t)splits);
     return launch_status("linear_bwd_weight_bf16x3");
@@ -913,7 +894,7 @@ extern "C" int svr_linear_bwd_weight_f16x3(const float *dY, int64_t lddy, const 
   w += align256b((int64_t)splits * N * K * 4) + 2 * align256b(N * Mpad * 2);
   float *dbpart = (float *)w;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
-  hipLaunchKernelGGL((linear_tn_x3_tr_kernel<1, true>), grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
+  hipLaunchKernelGGL((linear_tn_x3_tr_kernel<true>), grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
                      rps, splits, amax_dy, CwGeom{});
   hipLaunchKernelGGL(slab_reduce_x3_kernel, dim3((unsigned)cdiv(N * K, 64)), dim3(256), 0, s, slab, dW, N, K, lddw, splits);
   if (db) hipLaunchKernelGGL(dy_db_reduce_kernel, dim3((unsigned)N), dim3(256), 0, s, dbpart, db, N, (int64_t)splits);
@@ -980,10 +961,10 @@ extern "C" int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, 
   const bool vec4 = d->C0 % 4 == 0 && d->C1 % 4 == 0 && (((uintptr_t)d->src0 | (uintptr_t)d->src1 | (uintptr_t)dY) & 15) == 0;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
   if (vec4)
-    hipLaunchKernelGGL((linear_tn_x3_tr_kernel<1, true, true, true>), grid, dim3(256), 0, s, dY, (int64_t)Cout, (const float *)nullptr, (int64_t)0,
+    hipLaunchKernelGGL((linear_tn_x3_tr_kernel<true, true, true>), grid, dim3(256), 0, s, dY, (int64_t)Cout, (const float *)nullptr, (int64_t)0,
                        slab, db ? dbpart : nullptr, M, N, K, rps, splits, amax_dy, G);
   else
-    hipLaunchKernelGGL((linear_tn_x3_tr_kernel<1, true, true, false>), grid, dim3(256), 0, s, dY, (int64_t)Cout, (const float *)nullptr, (int64_t)0,
+    hipLaunchKernelGGL((linear_tn_x3_tr_kernel<true, true, false>), grid, dim3(256), 0, s, dY, (int64_t)Cout, (const float *)nullptr, (int64_t)0,
                        slab, db ? dbpart : nullptr, M, N, K, rps, splits, amax_dy, G);
   const int64_t total = (int64_t)Cout * C * d->k * d->k;
   hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)cdiv(total, 64)), dim3(256), 0, s, (const float *)slab, dW, Cout, C,

@@ -35,10 +35,6 @@
 #include "common.h"
 #include "f16x3.h"
 
-#ifndef S1_EXP
-#define S1_EXP 0   // measurement switches (build.py: SVR_S1_EXP): 1 no tail, 2 no MFMA
-#endif
-
 using namespace svr;
 
 namespace svr {
@@ -370,15 +366,6 @@ __global__ __launch_bounds__(256) void stage1_kernel(const S1Args a) {
       __builtin_amdgcn_sched_barrier(0);
       // ---- recompute a = relu(conv + bias) for the tile
       f32x4 acc = {bv, bv, bv, bv};   // the bias rides in the accumulator (every register of a lane is channel l15)
-#if S1_EXP == 2     // measurement build: no matrix instructions
-      if constexpr (H3) {
-#pragma unroll
-        for (int m = 0; m < 8; ++m) acc[m & 3] += __uint_as_float(pc[m]) * bw[m & 3];
-      } else {
-#pragma unroll
-        for (int m = 0; m < 7; ++m) acc[m & 3] += ac[m] * bw[m];
-      }
-#else
       if constexpr (H3) {
         // the lane's 8 taps -> fragments of the hi halves and of the lo * 2^11 halves (one v_perm_b32 per dword)
         union { uint4 q; f16x8 v; } xh, xl;
@@ -393,15 +380,9 @@ __global__ __launch_bounds__(256) void stage1_kernel(const S1Args a) {
 #pragma unroll
         for (int m = 0; m < 7; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[m], bw[m], acc, 0, 0, 0);
       }
-#endif
       float av[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) av[r] = fmaxf(acc[r], 0.f);
-#if S1_EXP == 1     // measurement build: no tail (the sums take the raw accumulator)
-      if (MODE == S1_STATS) { f1 += acc[0] + acc[1]; f2 += acc[2] + acc[3]; }
-      if (false)
-#endif
-
       if (MODE == S1_STATS) {
         if (gc.interior) {   // (uniform) every result counts: no masks
 #pragma unroll

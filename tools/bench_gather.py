@@ -62,7 +62,7 @@ for name, p in (() if "--pull-only" in sys.argv else (("random", pts), ("sorted"
 
 # ---- pull form (atomic-free) vs atomics, per level, on the Morton-sorted point set (what the training step sees)
 p = pts_sorted
-print("pull-form scatter (sorted points), SVR_PULL_VARIANT =", os.environ.get("SVR_PULL_VARIANT", "0"))
+print("pull-form scatter (sorted points)")
 plans = [None] * 6
 for l in (1, 2, 3):
     dims = tuple(vols[l].shape[1:4])
