@@ -13,6 +13,7 @@ nn.Conv3d / nn.BatchNorm3d / nn.Conv1d submodules only HOLD the parameters and b
 torch forward is never called.  There is no CPU fallback.
 """
 import contextlib
+import copy
 import os
 
 import torch
@@ -75,7 +76,7 @@ SCATTER_FORM = os.environ.get("SVR_SCATTER_FORM", "auto")
 # walk); with surface-clustered points the pull form is several times slower, so it is a mode, not
 # the default.  A level that has no atomic-free form (C = 128 without the projection: the 32-architecture) raises.
 DETERMINISTIC = os.environ.get("SVR_DETERMINISTIC") is not None
-PULL_MAX_WALK = int(os.environ.get("SVR_PULL_MAX_WALK", "64"))
+PULL_MAX_WALK = 64      # longest serial walk of a plan up to which the "auto" form takes the pull form
 _pull_hint = {}       # (device, level, dims, C, B, N) -> {"use": last decision, "slots": [(pinned int32[2], event), ...]}
 
 
@@ -107,6 +108,12 @@ def _pull_decision(key, plan, side):
     return h["use"]
 
 
+def _level_dims(D, H, W, l):
+    """Resolution of pyramid level l: the input grid for levels 0 and 1, halved per stage behind them."""
+    s = max(l - 1, 0)
+    return (max(D >> s, 1), max(H >> s, 1), max(W >> s, 1))
+
+
 def _level_orders_async(pts, D, H, W, n_levels, align, layout=None, disp=None, proj_levels=(), arena=None):
     """Backward-scatter preparation that depends only on the points, computed on a side stream beside the encoder;
     returns (orders per level, pull plans per level, ready event).  Level l has the pyramid's resolution
@@ -129,11 +136,11 @@ def _level_orders_async(pts, D, H, W, n_levels, align, layout=None, disp=None, p
     fits32 = layout is not None and N > 0 and 7 * B * N < 2 ** 31 and B * N * layout.row_stride < 2 ** 31
     with torch.cuda.stream(side):
         for l in range(1, n_levels):
-            dhw = (max(D >> (l - 1), 1), max(H >> (l - 1), 1), max(W >> (l - 1), 1))
+            dhw = _level_dims(D, H, W, l)
             C = layout.channels[l] if layout is not None else 0
             tag = f"L{l}."
             if l in proj_levels:                     # backward-only projection: items by (cell, displacement)
-                if DETERMINISTIC or (PROJ_TWO_PASS and min(dhw) >= PROJ_TWO_PASS_MIN_DIM):
+                if DETERMINISTIC:
                     orders[l] = ops.project_plan(pts, dhw, disp, align)      # two-pass form: no float atomics
                     orders[l].record_stream(main)
                 else:
@@ -174,20 +181,12 @@ def _level_orders_async(pts, D, H, W, n_levels, align, layout=None, disp=None, p
 # dP_l[b][voxel][j][256], and two GEMMs over VOXELS (32 768 rows at level 4) give the level's gradient volume and its slice
 # of dW0.  dX0 / dW0 of the point MLP then only cover the remaining 800 columns.  The forward pass is unchanged.
 PROJECT_WIDE_LEVELS = os.environ.get("SVR_NO_PROJECTION") is None
-# Optional two-pass form of the projected scatter for levels of 16^3 voxels and more (run sums stored, then one gather-form
-# pass per dP row: no float atomics, dP written once, bit-reproducible).  At 16^3 x 8 samples there are ~270 000 runs of ~10
-# items: 2.2 GB of run-end atomics against 2.2 GB stored + read plainly, 1.53 -> 1.20 ms alone -- but only 18.25 -> 18.18 ms
-# per step inside the backward's fork (it is not on the critical stream), a 2.7 GB buffer and a longer allocator warm-up, so
-# the atomic form stays the default.  SVR_PROJ_TWO_PASS=1 selects it (at 8^3 the atomic form wins anyway: 0.49 vs 0.55 ms).
-PROJ_TWO_PASS = os.environ.get("SVR_PROJ_TWO_PASS") is not None
-PROJ_TWO_PASS_MIN_DIM = int(os.environ.get("SVR_PROJ_TWO_PASS_MIN_DIM", "16"))
 # Fused gather -> fc_0 forward (gather_fc0.hip): the feature rows are never written to HBM; only the columns a backward
 # still needs (the levels that are not projected) are kept.  SVR_NO_FUSED_FC0=1 restores the two separate kernels.
 FUSE_FC0 = os.environ.get("SVR_NO_FUSED_FC0") is None
 # ... and its bf16-storage variant for the query path's throughput mode (SVR_NO_FUSED_FC0_BF16=1: gather + fc_0 as two kernels)
 FUSE_FC0_BF16 = os.environ.get("SVR_NO_FUSED_FC0_BF16") is None
 # Fused + projected backward: the kept-column branch on the side stream beside the projected branch (SVR_NO_BWD_OVERLAP=1: serial)
-PREPARE_FORWARD_FIRST = os.environ.get("SVR_PREP_FWD_FIRST", "1") != "0"   # "0": one event behind all weight planes (A/B)
 OVERLAP_BACKWARD = os.environ.get("SVR_NO_BWD_OVERLAP") is None
 # First stage of the 128-architecture (conv_in -> ReLU -> BatchNorm -> pool) with conv_in's activation recomputed instead
 # of stored (stage1.hip): 3 of 5 forward and 5 of 7 backward passes over 1 GB tensors less.  SVR_NO_STAGE1=1: the separate
@@ -197,8 +196,8 @@ STAGE1_RECOMPUTE = os.environ.get("SVR_NO_STAGE1") is None
 SORT_ON_SIDE_STREAM = os.environ.get("SVR_SORT_ON_MAIN") is None
 # ... and so do the parameter-only preparations of the split-precision layers (SVR_NO_WEIGHT_PREP=1: in front of every layer)
 PREPARE_WEIGHTS_AHEAD = os.environ.get("SVR_NO_WEIGHT_PREP") is None
-# Level of the kept branch whose scatter runs on the third stream of the backward's fork (SVR_FORK_SPLIT_LEVEL=0: none)
-FORK_SPLIT_LEVEL = int(os.environ.get("SVR_FORK_SPLIT_LEVEL", "3"))
+# Level of the kept branch whose scatter runs on the third stream of the backward's fork
+FORK_SPLIT_LEVEL = 3
 # Per-level events instead of one join in front of the encoder's backward (SVR_NO_FORK_PIPELINE=1: the single join)
 FORK_PIPELINED = os.environ.get("SVR_NO_FORK_PIPELINE") is None
 # BatchNorm statistics of stages 2..5 from the epilogue of the stage's last convolution (SVR_NO_CONV_STATS=1: a separate pass)
@@ -216,8 +215,8 @@ def _fc0_fusable(channels, B, dims, n_out):
     for l, c in enumerate(channels):
         if not (c in (1, 16, 32) or c % 64 == 0):
             return False
-        s = max(l - 1, 0)
-        if B * max(D >> s, 1) * max(H >> s, 1) * max(W >> s, 1) * c >= 2 ** 30:
+        d, h, w = _level_dims(D, H, W, l)
+        if B * d * h * w * c >= 2 ** 30:
             return False
     return True
 
@@ -233,7 +232,6 @@ class _ProjLink:
 
     def __init__(self, levels, layout):
         self.levels = tuple(levels)
-        self.layout = layout
         self.dh0 = None
         self.need_level0 = False
         cols = sorted((layout.col[l], layout.col[l] + 7 * layout.channels[l]) for l in levels)
@@ -255,6 +253,264 @@ class _ProjLink:
         self.raw = set(raw)                             # ... those of them that hold nothing but the raw-grid level
 
 
+def _run_stages(ext, inp, training, for_backward):
+    """The encoder's conv / ReLU / BatchNorm / pool stages over `inp` (B,D,H,W,1): (levels [inp, bn_1, ...], saved).
+    for_backward (the autograd forward; encode_levels passes False): `saved` holds what _stages_bwd reads per stage, (inp,
+    acts | ("stage1", wp), argmax, ss, mean), and in training mode the BatchNorm's statistics come out of the epilogue of
+    the convolution in front of it; otherwise nothing is kept and the plain convolution kernels run."""
+    levels, saved = [inp], []
+    nst = len(ext._stages)
+    for si, (convs, bn) in enumerate(ext._stages):
+        bn_args = (bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, training)
+        bn_kw = dict(eps=bn.eps, momentum=bn.momentum, want_pool=(si + 1 < nst))
+        if _stage1_applies(si, convs, inp):
+            conv = convs[0]
+            y, pooled, argmax, ss, mean, wp = ops.stage1_fwd(inp, conv.weight.detach(), conv.bias.detach(), *bn_args, **bn_kw)
+            acts = ("stage1", wp)      # conv_in's activation is never stored
+        else:
+            acts = []
+            cur = inp
+            stats = None
+            for conv in convs:
+                w, b = conv.weight.detach(), conv.bias.detach()
+                if for_backward and training and len(convs) == 1 and w.shape[1] == 1 and w.shape[0] in (16, 32):
+                    # conv_in: the statistics of the BatchNorm that follows come out of the conv kernel's epilogue
+                    cur, stats = ops.conv3d_c1_fwd_stats(cur, w, b, relu=True)
+                elif for_backward and training and conv is convs[-1] and STATS_IN_CONV_EPILOGUE:
+                    # the stage's last convolution: its epilogue also leaves the BatchNorm's partial sums (no statistics pass)
+                    cur, stats = ops.conv3d_k3_fwd(cur, w, b, relu=True, want_stats=True)
+                else:
+                    cur = ops.conv3d_k3_fwd(cur, w, b, relu=True)
+                if for_backward:
+                    acts.append(cur)
+            y, pooled, argmax, ss, mean = ops.bn_forward(cur, *bn_args, **bn_kw, stats=stats)
+        levels.append(y)
+        if for_backward:
+            saved.append((inp, acts, argmax, ss, mean))
+        inp = pooled
+    return levels, saved
+
+
+def _gvols(arena, levels, plans, proj):
+    """Gradient volumes of the backward scatter for levels 1.. (None for level 0 and for the projected levels, whose
+    volumes come out of a GEMM), from the step arena when there is one; zeroed unless a pull plan writes them by plain stores."""
+    def one(l, like):
+        if arena is None:
+            return torch.zeros_like(like) if plans[l] is None else torch.empty_like(like)
+        g = arena.get(f"gvol{l}", tuple(like.shape), like.dtype, like.device)
+        return g.zero_() if plans[l] is None else g
+    return [None] + [None if l in proj else one(l, v) for l, v in enumerate(levels) if l >= 1]
+
+
+def _zero_fill_async(levels, orders, plans, proj, arena):
+    """The zero-initialised gradient volumes of the backward scatter (1.45 GB of memset at config 3) and the zeroed
+    (voxel, displacement, 256) slabs the projected levels' atomic scatter accumulates into, prepared on the side stream
+    beside the point MLP instead of in front of the scatter.  Returns (gvols, dP slabs per level, ready event)."""
+    x = levels[0]
+    main, side = torch.cuda.current_stream(), _get_side_stream(x.device)
+    with torch.cuda.stream(side):
+        gvols = _gvols(arena, levels, plans, proj)
+        dP = {}
+        if arena is not None:
+            for l in proj:
+                if not isinstance(orders[l], ops.ProjPlan):      # (the two-pass form overwrites its own)
+                    v = levels[l]
+                    dP[l] = arena.get(f"dP{l}", (x.shape[0], v.shape[1] * v.shape[2] * v.shape[3], 7, 256), torch.float32,
+                                      x.device).zero_()
+        else:
+            for g in gvols[1:]:
+                if g is not None:
+                    g.record_stream(main)
+        ready = torch.cuda.Event()
+        ready.record(side)
+    return gvols, dP, ready
+
+
+class _Fork:
+    """Streams and events of the encoder backward's fork (fused forward + projection).  The kept columns' backward (dX0
+    over 800 columns, then the scatter of levels 1-3) and the projected levels' (row scatter + voxel GEMMs) only share dh0
+    and neither saturates the chip: the kept branch runs on the side stream `keep` beside the projected one on `main`, the
+    leaf dW0 of the kept columns on the third stream `w`.
+    split: the kept branch's last level (FORK_SPLIT_LEVEL) is scattered on `w`, behind dW0, as soon as dX0 is there (arena only).
+    pipelined (FORK_PIPELINED): no join in front of the stages' backward -- every level's gradient volume gets an event and
+    stage s only waits for level s + 1, so the deep stages (1.3 ms of small kernels) run while the fine levels are still
+    scattered, one call per level, coarse to fine; the coarsest projected level gets a stream of its own, `p`.
+    Not forking (`on` false; a captured step keeps the serial order): every stream is the caller's, nothing is waited for."""
+
+    def __init__(self, on, main, device, arena, need_pts, skip, proj, n_levels):
+        self.on = on
+        self.main = main
+        self.keep = _get_side_stream(device) if on else main
+        self.w = _get_side_stream(device, 1) if on else main
+        self.p = None
+        s = FORK_SPLIT_LEVEL
+        self.split = s if (on and arena is not None and not need_pts and s not in skip and s not in proj
+                           and 0 < s < n_levels) else None
+        self.pipelined = FORK_PIPELINED and self.split is not None
+        self.dx0_done = self.keep_done = None
+        self.level_done = {}
+
+    def stream(self, s):      # context: run on stream s, or inline when not forking
+        return torch.cuda.stream(s) if self.on else contextlib.nullcontext()
+
+    def start(self, *held):
+        """The side streams branch off main.  No record_stream on what they read: dh0, the kept rows, the gradient volumes
+        ... and `held` stay referenced until backward() returns, behind join() -- or live in the step arena."""
+        self.held = held
+        if self.on:
+            self.keep.wait_stream(self.main)
+            self.w.wait_stream(self.main)
+
+    def mark_level(self, l):
+        self.level_done[l] = torch.cuda.current_stream().record_event()
+
+    def wait_level(self, l):      # pipelined: main waits for level l's gradient volume, from whichever stream scattered it
+        if self.pipelined and l in self.level_done:
+            self.main.wait_event(self.level_done[l])
+
+    def join(self):      # main waits for the leaves of the side streams (dW0's slices, db0) and everything that reads the arena
+        self.main.wait_event(self.keep_done)
+        self.main.wait_stream(self.w)
+        if self.p is not None:
+            self.main.wait_stream(self.p)
+
+
+def _scatter_state(orders, plans, ready, gvols, ext, levels, pts, layout, proj, arena, need_x):
+    """What the forward prepared for the scatter, or the same built now: (orders, plans, ready event, gradient volumes)."""
+    if orders is None:
+        orders, plans, ready = _level_orders_async(pts, *levels[0].shape[1:4], len(levels), ext._align, layout, ext._disp,
+                                                   proj_levels=proj, arena=arena)
+    if ops.GATHER_FLAGS & ops._lib.GATHER_DETERMINISTIC:      # the serial test scatter accumulates into zeros
+        plans = [None] * len(levels)
+        gvols = None
+    g0 = torch.zeros_like(levels[0]) if need_x else None      # the raw grid's: only for d(loss)/d(input)
+    if gvols is None:
+        gvols = _gvols(arena, levels, plans, proj)
+    return orders, plans, ready, [g0] + gvols[1:]
+
+
+def _fc0_kept_bwd(fork, dh0, feat, w0p, klay, arena):
+    """Fused forward: fc_0's backward lives in the encoder's.  dh0 is dz0 (B*N, 256); dW0 / dX0 only over the kept
+    columns, ONE product each over the compact kept-column matrix `feat`: (dW0, db0, the compact gradient rows)."""
+    cols = klay.full_cols_on(w0p.device)
+    w0k = w0p[:, cols]                           # (256, 800): fc_0's weights of the kept columns (zeros behind the padding)
+    dw0_keep = torch.zeros_like(w0p)
+    fork.start(w0k)
+    with fork.stream(fork.w):
+        dwk, db0 = ops.linear_bwd_weight(dh0, feat, want_bias=True)
+        dw0_keep[:, cols[:klay.width]] = dwk[:, :klay.width]
+        if fork.on:
+            db0.record_stream(fork.main)
+    with fork.stream(fork.keep):
+        gfeat = arena.get("kept_grad", tuple(feat.shape), torch.float32, feat.device) if arena is not None else torch.empty_like(feat)
+        ops.linear_bwd_data(dh0, w0k, out=gfeat)
+        if fork.on:
+            fork.dx0_done = torch.cuda.Event()
+            fork.dx0_done.record(fork.keep)
+    return dw0_keep, db0, gfeat
+
+
+def _scatter_kept(fork, ext, levels, gvols, pts, gfeat, layout, orders, plans, ready, skip, proj, need_pts):
+    """Scatter of the gradient rows into the volumes of the levels that are not projected: one call on the `keep` stream,
+    or -- pipelined -- one call and one event per level, the split level on the `w` stream.  Returns d(loss)/d(points)."""
+    n = len(levels)
+    lo = [None if l in proj else o for l, o in enumerate(orders)]
+
+    def scatter(want_gpoints, skip_levels):
+        return ops.gather_bwd(levels, gvols, pts, gfeat, layout, ext._disp, ext._align, want_gpoints=want_gpoints,
+                              level_orders=lo, level_plans=plans, skip_levels=skip_levels)
+
+    def scatter_level(l):
+        scatter(False, tuple(k for k in range(n) if k != l))
+        fork.mark_level(l)
+
+    gpts = None
+    with fork.stream(fork.keep):
+        if ready is not None:
+            torch.cuda.current_stream().wait_event(ready)
+        if fork.pipelined:
+            for l in range(n - 1, -1, -1):      # (level 0, the raw grid, only when d(loss)/d(input) is wanted)
+                if l != fork.split and l not in skip and l not in proj and gvols[l] is not None:
+                    scatter_level(l)
+        else:
+            gpts = scatter(need_pts, skip if fork.split is None else tuple(skip) + (fork.split,))
+        if fork.on:
+            fork.keep_done = torch.cuda.Event()
+            fork.keep_done.record(fork.keep)
+    if fork.split is not None:
+        with torch.cuda.stream(fork.w):
+            fork.w.wait_event(fork.dx0_done)
+            if ready is not None:
+                fork.w.wait_event(ready)
+            scatter_level(fork.split)
+    return gpts
+
+
+def _project_wide(fork, ext, levels, gvols, pts, dh0, w0p, orders, ready, proj, dPs, dw0p):
+    """dP = scatter of the dh0 rows, then two GEMMs over voxels (gather_bwd_proj_kernel): gvols[l] and its slice of dW0."""
+    if fork.on and ready is not None:
+        fork.main.wait_event(ready)
+    if dw0p is None:
+        dw0p = torch.zeros_like(w0p)
+
+    def project_level(l):
+        v = levels[l]
+        B_, Dl, Hl, Wl, Cl = v.shape
+        c0 = ext._layout.col[l]
+        dP = ops.gather_project_bwd(pts, dh0, (Dl, Hl, Wl), orders[l], ext._disp, ext._align, out=dPs.get(l))
+        dP2 = dP.view(B_ * Dl * Hl * Wl, 7 * 256)
+        wl = w0p[:, c0:c0 + 7 * Cl].reshape(256, 7, Cl).permute(1, 0, 2).reshape(7 * 256, Cl).contiguous()   # rows (j, n)
+        gvols[l] = ops.linear_bwd_data(dP2, wl).view(v.shape)
+        dwl, _ = ops.linear_bwd_weight(dP2, v.view(-1, Cl), want_bias=False)                                # (7*256, Cl)
+        dw0p[:, c0:c0 + 7 * Cl] = dwl.view(7, 256, Cl).permute(1, 0, 2).reshape(256, 7 * Cl)
+
+    own = max(proj) if (fork.pipelined and len(proj) > 1) else None     # the coarsest projected level: its own stream
+    if own is not None:
+        fork.p = _get_side_stream(pts.device, 2)
+        fork.p.wait_stream(fork.main)
+        with torch.cuda.stream(fork.p):
+            if ready is not None:
+                fork.p.wait_event(ready)
+            project_level(own)
+            gvols[own].record_stream(fork.main)       # allocated in this stream's pool, read by the stage's backward on main
+            fork.mark_level(own)
+    for l in proj:
+        if l != own:
+            project_level(l)
+    return dw0p
+
+
+def _stages_bwd(fork, ext, saved, gvols, training, need_x):
+    """Backward of the encoder stages, last to first (BN -> ReLU -> conv per stage), from the levels' gradient volumes:
+    ({parameter: gradient}, d(loss)/d(input grid) without the raw-grid level's share, or None)."""
+    grads, dpooled, gx = {}, None, None
+    for si in range(len(ext._stages) - 1, -1, -1):
+        convs, bn = ext._stages[si]
+        inp, acts, argmax, ss, mean = saved[si]
+        fork.wait_level(si + 1)
+        if isinstance(acts, tuple):       # ("stage1", wp): BatchNorm backward + conv_in's weight gradient in two passes
+            conv = convs[0]
+            grads[bn.weight], grads[bn.bias], grads[conv.weight], grads[conv.bias], dout = ops.stage1_bwd(
+                inp, acts[1], conv.bias.detach(), gvols[si + 1], dpooled, argmax if dpooled is not None else None, mean, ss,
+                relu_mask=True, training=training, want_dout=need_x)
+            if need_x:
+                gx = ops.conv3d_k3_bwd_data(dout, conv.weight.detach())
+            continue
+        dout, grads[bn.weight], grads[bn.bias] = ops.bn_backward(
+            acts[-1], gvols[si + 1], dpooled, argmax if dpooled is not None else None, mean, ss, relu_mask=True, training=training)
+        for k in range(len(convs) - 1, -1, -1):
+            conv = convs[k]
+            cin = acts[k - 1] if k > 0 else inp
+            grads[conv.weight], grads[conv.bias] = ops.conv3d_k3_bwd_weight(cin, dout, param_layout=True)
+            if k > 0:
+                dout = ops.conv3d_k3_bwd_data(dout, conv.weight.detach(), mask=acts[k - 1])
+            elif si > 0:
+                dpooled = ops.conv3d_k3_bwd_data(dout, conv.weight.detach())
+            elif need_x:
+                gx = ops.conv3d_k3_bwd_data(dout, conv.weight.detach())
+    return grads, gx
+
+
 class _EncoderGatherFn(torch.autograd.Function):
     """x, points, encoder parameters -> feature rows (B*N, FS) in the internal column layout.
 
@@ -267,24 +523,18 @@ class _EncoderGatherFn(torch.autograd.Function):
         """b0 given (with link and w0p): FUSED form -- the output is h0 = relu(fc_0(rows)) straight from the gather
         (gather_fc0.hip), the rows of the levels that are not projected are kept for the backward, and backward()
         takes the gradient wrt fc_0's PRE-activation (what _PointMLPFn's headless form returns for its input)."""
-        B = x.shape[0]
-        D, H, W = x.shape[2:]
+        B, _, D, H, W = x.shape
         training = ext.training
         x_cl = x.contiguous().view(B, D, H, W, 1)
         pts = points.contiguous()
-        levels = [x_cl]
-        saved = []
-        inp = x_cl
-        nst = len(ext._stages)
-        # The per-level visiting orders of the backward scatter depend only on the points: their radix sorts (dozens
-        # of ~6 us launches) run on a side stream beside the encoder instead of in front of the scatter.
-        ctx.level_orders, ctx.level_plans, ctx.orders_ready = None, None, None
+        nlev = len(ext._stages) + 1
         # only when a backward can follow: grad mode of the CALLER (it is always off inside Function.forward, and
         # needs_input_grad ignores no_grad) and something that requires grad
         will_backward = bool(grad_mode) and any(ctx.needs_input_grad)
         ctx.link = link if (will_backward and link is not None) else None
         if ctx.link is not None:
             ctx.link.need_level0 = bool(ctx.needs_input_grad[6])
+        proj = ctx.link.levels if ctx.link is not None else ()
         # the step arena (large cross-stream buffers, allocated once): held from here to the end of backward()
         if lease is not None and not (will_backward and x.is_cuda):
             lease.release()
@@ -292,45 +542,17 @@ class _EncoderGatherFn(torch.autograd.Function):
         ctx.lease = lease
         arena = lease.arena if lease is not None else None
         ctx.fused = b0 is not None
-        nlev = nst + 1
-        keep = []
-        if ctx.fused and will_backward:
-            keep = [l for l in range(nlev) if ctx.link is None or l not in ctx.link.levels]
+        keep = [l for l in range(nlev) if l not in proj] if (ctx.fused and will_backward) else []
         # fused step: the backward reads the COMPACT kept-column matrix (800 columns at the 128-architecture)
         ctx.klay = ext._layout.subset(keep) if keep else None
+        # The per-level visiting orders of the backward scatter depend only on the points: their radix sorts (dozens
+        # of ~6 us launches) run on a side stream beside the encoder instead of in front of the scatter.
+        ctx.level_orders, ctx.level_plans, ctx.orders_ready = None, None, None
         if will_backward and x.is_cuda:
             ctx.level_orders, ctx.level_plans, ctx.orders_ready = _level_orders_async(
                 pts, D, H, W, nlev, ext._align, ctx.klay if ctx.klay is not None else ext._layout, ext._disp,
-                proj_levels=ctx.link.levels if ctx.link is not None else (), arena=arena)
-        for si, (convs, bn) in enumerate(ext._stages):
-            if _stage1_applies(si, convs, inp):
-                conv = convs[0]
-                y, pooled, argmax, ss, mean, wp = ops.stage1_fwd(
-                    inp, conv.weight.detach(), conv.bias.detach(), bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                    bn.running_var, training, eps=bn.eps, momentum=bn.momentum, want_pool=(si + 1 < nst))
-                levels.append(y)
-                saved.append((inp, ("stage1", wp), argmax, ss, mean))      # conv_in's activation is never stored
-                inp = pooled
-                continue
-            acts = []
-            cur = inp
-            stats = None
-            for conv in convs:
-                if training and len(convs) == 1 and conv.weight.shape[1] == 1 and conv.weight.shape[0] in (16, 32):
-                    # conv_in: the statistics of the BatchNorm that follows come out of the conv kernel's epilogue
-                    cur, stats = ops.conv3d_c1_fwd_stats(cur, conv.weight.detach(), conv.bias.detach(), relu=True)
-                elif training and conv is convs[-1] and STATS_IN_CONV_EPILOGUE:
-                    # the stage's last convolution: its epilogue also leaves the BatchNorm's partial sums (no statistics pass)
-                    cur, stats = ops.conv3d_k3_fwd(cur, conv.weight.detach(), conv.bias.detach(), relu=True, want_stats=True)
-                else:
-                    cur = ops.conv3d_k3_fwd(cur, conv.weight.detach(), conv.bias.detach(), relu=True)
-                acts.append(cur)
-            y, pooled, argmax, ss, mean = ops.bn_forward(
-                cur, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, training,
-                eps=bn.eps, momentum=bn.momentum, want_pool=(si + 1 < nst), stats=stats)
-            levels.append(y)
-            saved.append((inp, acts, argmax, ss, mean))
-            inp = pooled
+                proj_levels=proj, arena=arena)
+        levels, saved = _run_stages(ext, x_cl, training, for_backward=True)
         if training:      # one multi-tensor launch for the counters of all stages
             torch._foreach_add_([bn.num_batches_tracked for _, bn in ext._stages], 1)
         ready, ext._points_ready = getattr(ext, "_points_ready", None), None
@@ -345,34 +567,12 @@ class _EncoderGatherFn(torch.autograd.Function):
             ctx.feat = feat
         else:
             out = feat = ops.gather_fwd(levels, pts, ext._layout, ext._disp, ext._align)
-        # the zero-initialised gradient volumes of the backward scatter (1.45 GB of memset at config 3) are prepared on
-        # the side stream too, beside the point MLP, instead of in front of the scatter
-        ctx.gvols = None
+        ctx.gvols, ctx.dP = None, {}
         if will_backward and x.is_cuda:
-            main, side = torch.cuda.current_stream(), _get_side_stream(x.device)
-            with torch.cuda.stream(side):
-                # (levels with a pull plan are written by plain stores: no zero fill)
-                proj = ctx.link.levels if ctx.link is not None else ()
-                ctx.gvols = [None] + [None if l in proj else _gvol(arena, l, v, zero=ctx.level_plans[l] is None)
-                                      for l, v in enumerate(levels) if l >= 1]
-                # ... and the zeroed (voxel, displacement, 256) slabs the projected levels' atomic scatter accumulates into
-                ctx.dP = {}
-                if arena is not None:
-                    for l in proj:
-                        if not isinstance(ctx.level_orders[l], ops.ProjPlan):      # (the two-pass form overwrites its own)
-                            v = levels[l]
-                            ctx.dP[l] = arena.get(f"dP{l}", (B, v.shape[1] * v.shape[2] * v.shape[3], 7, 256), torch.float32,
-                                                  x.device).zero_()
-                if arena is None:
-                    for g in ctx.gvols[1:]:
-                        if g is not None:
-                            g.record_stream(main)
-                ctx.orders_ready = torch.cuda.Event()
-                ctx.orders_ready.record(side)
+            ctx.gvols, ctx.dP, ctx.orders_ready = _zero_fill_async(levels, ctx.level_orders, ctx.level_plans, proj, arena)
         ctx.ext, ctx.saved, ctx.levels, ctx.pts = ext, saved, levels, pts
         ctx.w0p = w0p.detach() if (ctx.link is not None or ctx.fused) else None
-        ctx.x_shape = x.shape
-        ctx.training = training
+        ctx.x_shape, ctx.training = x.shape, training
         return out
 
     @staticmethod
@@ -392,207 +592,40 @@ class _EncoderGatherFn(torch.autograd.Function):
         arena = lease.arena if lease is not None else None
         klay = ctx.klay if ctx.fused else None
         scatter_layout = klay if klay is not None else ext._layout
-        dw0_keep = db0 = None
-        level_orders, level_plans = ctx.level_orders, ctx.level_plans
-        if level_orders is None:
-            level_orders, level_plans, ready = _level_orders_async(pts, *levels[0].shape[1:4], len(levels), ext._align,
-                                                                   scatter_layout, ext._disp, proj_levels=proj, arena=arena)
-        else:
-            ready = ctx.orders_ready
-        if ops.GATHER_FLAGS & ops._lib.GATHER_DETERMINISTIC:      # the serial test scatter accumulates into zeros
-            level_plans = [None] * len(levels)
-            ctx.gvols = None
-        if ctx.gvols is not None:
-            gvols = [torch.zeros_like(levels[0]) if need_x else None] + ctx.gvols[1:]
-            ctx.gvols = None
-        else:
-            gvols = [torch.zeros_like(levels[0]) if need_x else None] + \
-                    [None if l in proj else _gvol(arena, l, v, zero=level_plans[l] is None)
-                     for l, v in enumerate(levels) if l >= 1]
+        skip = tuple(l for l in range(len(levels)) if klay.col[l] < 0) if ctx.fused else ()
+        dPs, ctx.dP = ctx.dP, None
+        gvols, ctx.gvols = ctx.gvols, None
+        orders, plans, ready, gvols = _scatter_state(ctx.level_orders, ctx.level_plans, ctx.orders_ready, gvols, ext, levels,
+                                                     pts, scatter_layout, proj, arena, need_x)
         main = torch.cuda.current_stream() if gfeat.is_cuda else None
-        # Fused forward + projection: the backward of the KEPT columns (dW0 / dX0 over 800 columns, then the scatter of
-        # levels 1-3) and the backward of the PROJECTED levels (row scatter + voxel GEMMs) only share dh0 as an input;
-        # neither saturates the chip (GEMMs at 2-3x their memory floor, scatters latency / atomics bound), so the kept
-        # branch runs on the side stream beside the projected one and the two join in front of the encoder's backward.
-        fork = (ctx.fused and link is not None and main is not None and OVERLAP_BACKWARD
-                and not torch.cuda.is_current_stream_capturing())      # (a captured step keeps the serial order)
-        keep_stream = _get_side_stream(gfeat.device) if fork else main
-        skip = ()
+        fork = _Fork(ctx.fused and link is not None and main is not None and OVERLAP_BACKWARD
+                     and not torch.cuda.is_current_stream_capturing(),
+                     main, gfeat.device, arena, need_pts, skip, proj, len(levels))
+        dw0 = db0 = None
         if ctx.fused:
-            # fused forward: fc_0's backward lives here.  gfeat is dz0 (B*N, 256); dW0 / dX0 only over the kept columns,
-            # ONE product each over the compact kept-column matrix
-            dh0, feat, w0p = gfeat, ctx.feat, ctx.w0p
-            ctx.feat = None
-            cols = klay.full_cols_on(w0p.device)
-            w0k = w0p[:, cols]                           # (256, 800): fc_0's weights of the kept columns (zeros behind the padding)
-            dw0_keep = torch.zeros_like(w0p)
-            if fork:
-                # (no record_stream on what the side streams read: dh0, the kept rows, the gradient volumes ... stay
-                # referenced until main has joined both streams -- or live in the step arena -- so the allocator cannot
-                # hand them out earlier)
-                keep_stream.wait_stream(main)
-            # dW0 over the kept columns is a leaf (needed at the return only): third stream
-            w_stream = _get_side_stream(gfeat.device, 1) if fork else main
-            if fork:
-                w_stream.wait_stream(main)
-            with torch.cuda.stream(w_stream) if fork else contextlib.nullcontext():
-                dwk, db0 = ops.linear_bwd_weight(dh0, feat, want_bias=True)
-                dw0_keep[:, cols[:klay.width]] = dwk[:, :klay.width]
-                if fork:
-                    db0.record_stream(main)
-            with torch.cuda.stream(keep_stream) if fork else contextlib.nullcontext():
-                if arena is not None:
-                    gfeat = arena.get("kept_grad", tuple(feat.shape), torch.float32, feat.device)
-                else:
-                    gfeat = torch.empty_like(feat)
-                ops.linear_bwd_data(dh0, w0k, out=gfeat)
-                if fork:
-                    dx0_done = torch.cuda.Event()
-                    dx0_done.record(keep_stream)
-            skip = tuple(l for l in range(len(levels)) if klay.col[l] < 0)
+            dh0, feat, ctx.feat = gfeat, ctx.feat, None
+            dw0, db0, gfeat = _fc0_kept_bwd(fork, dh0, feat, ctx.w0p, klay, arena)
             if link is not None:
                 link.dh0 = dh0
         if link is not None and link.dh0 is None:
             raise RuntimeError("IF-Net HIP path: the projected backward needs dh0 from the point MLP's backward")
-        # the kept branch is the longest chain of the fork (dX0 -> scatter of levels 2, 1, 3 one after the other): its last
-        # level moves to the third stream, behind dW0, as soon as dX0 is there (FORK_SPLIT_LEVEL; arena buffers only)
-        split = FORK_SPLIT_LEVEL if (fork and arena is not None and ctx.fused and not need_pts and FORK_SPLIT_LEVEL not in skip
-                                     and FORK_SPLIT_LEVEL not in proj and 0 < FORK_SPLIT_LEVEL < len(levels)) else None
-        lo = [None if l in proj else o for l, o in enumerate(level_orders)]
-        # PIPELINED join (FORK_PIPELINED): instead of joining every branch in front of the encoder's backward, every level's
-        # gradient volume gets its own event and stage s only waits for level s + 1 -- the deep stages' backward (1.3 ms of
-        # small, low-occupancy kernels) runs while the side streams still scatter the fine levels; the kept levels are
-        # scattered one call per level, coarse to fine (the order the stages need them), and the coarsest projected level
-        # gets a stream of its own beside the other one's scatter on the main stream.
-        pipelined = FORK_PIPELINED and split is not None
-        level_done = {}
-
-        def scatter_level(l):
-            ops.gather_bwd(levels, gvols, pts, gfeat, scatter_layout, ext._disp, ext._align, want_gpoints=False,
-                           level_orders=lo, level_plans=level_plans, skip_levels=tuple(k for k in range(len(levels)) if k != l))
-            level_done[l] = torch.cuda.Event()
-            level_done[l].record(torch.cuda.current_stream())
-
-        with torch.cuda.stream(keep_stream) if fork else contextlib.nullcontext():
-            if ready is not None:
-                torch.cuda.current_stream().wait_event(ready)
-            if pipelined:
-                gpts = None
-                for l in range(len(levels) - 1, -1, -1):      # (level 0, the raw grid, only when d(loss)/d(input) is wanted)
-                    if l != split and l not in skip and l not in proj and gvols[l] is not None:
-                        scatter_level(l)
-            else:
-                gpts = ops.gather_bwd(levels, gvols, pts, gfeat, scatter_layout, ext._disp, ext._align, want_gpoints=need_pts,
-                                      level_orders=lo, level_plans=level_plans,
-                                      skip_levels=skip if split is None else tuple(skip) + (split,))
-            if fork:
-                keep_done = torch.cuda.Event()
-                keep_done.record(keep_stream)
-        if split is not None:
-            with torch.cuda.stream(w_stream):
-                w_stream.wait_event(dx0_done)
-                if ready is not None:
-                    w_stream.wait_event(ready)
-                scatter_level(split)
-        dw0p = None
-        p_stream = None
-        dPs, ctx.dP = (getattr(ctx, "dP", None) or {}), None
+        gpts = _scatter_kept(fork, ext, levels, gvols, pts, gfeat, scatter_layout, orders, plans, ready, skip, proj, need_pts)
         if proj:
-            # projected levels: dP = scatter of the dh0 rows, then two GEMMs over voxels (see gather_bwd_proj_kernel)
-            lay, w0p, dh0 = ext._layout, ctx.w0p, link.dh0
-            link.dh0 = None
-            if fork and ready is not None:
-                main.wait_event(ready)
-            dw0p = dw0_keep if dw0_keep is not None else torch.zeros_like(w0p)
-
-            def project_level(l):
-                v = levels[l]
-                B_, Dl, Hl, Wl, Cl = v.shape
-                c0 = lay.col[l]
-                dP = ops.gather_project_bwd(pts, dh0, (Dl, Hl, Wl), level_orders[l], ext._disp, ext._align, out=dPs.get(l))
-                dP2 = dP.view(B_ * Dl * Hl * Wl, 7 * 256)
-                wl = w0p[:, c0:c0 + 7 * Cl].reshape(256, 7, Cl).permute(1, 0, 2).reshape(7 * 256, Cl).contiguous()   # rows (j, n)
-                gvols[l] = ops.linear_bwd_data(dP2, wl).view(v.shape)
-                dwl, _ = ops.linear_bwd_weight(dP2, v.view(-1, Cl), want_bias=False)                                # (7*256, Cl)
-                dw0p[:, c0:c0 + 7 * Cl] = dwl.view(7, 256, Cl).permute(1, 0, 2).reshape(256, 7 * Cl)
-
-            own = max(proj) if (pipelined and len(proj) > 1) else None     # the coarsest projected level: its own stream
-            if own is not None:
-                p_stream = _get_side_stream(gfeat.device, 2)
-                p_stream.wait_stream(main)
-                with torch.cuda.stream(p_stream):
-                    if ready is not None:
-                        p_stream.wait_event(ready)
-                    project_level(own)
-                    gvols[own].record_stream(main)       # allocated in this stream's pool, read by the stage's backward on main
-                    level_done[own] = torch.cuda.Event()
-                    level_done[own].record(p_stream)
-            for l in proj:
-                if l != own:
-                    project_level(l)
-        if fork and not pipelined:
-            main.wait_event(keep_done)
-            main.wait_stream(w_stream)
-            feat = None      # (only now: see the note at the fork)
-        grads = {}
-        dpooled = None
-        gx = None
-        for si in range(len(ext._stages) - 1, -1, -1):
-            convs, bn = ext._stages[si]
-            inp, acts, argmax, ss, mean = saved[si]
-            if pipelined and (si + 1) in level_done:
-                main.wait_event(level_done[si + 1])        # this stage's gradient volume, from whichever stream scattered it
-            if isinstance(acts, tuple):       # ("stage1", wp): BatchNorm backward + conv_in's weight gradient in two passes
-                conv = convs[0]
-                dgamma, dbeta, dwp, db, dout = ops.stage1_bwd(
-                    inp, acts[1], conv.bias.detach(), gvols[si + 1], dpooled, argmax if dpooled is not None else None, mean, ss,
-                    relu_mask=True, training=ctx.training, want_dout=need_x)
-                grads[bn.weight], grads[bn.bias] = dgamma, dbeta
-                grads[conv.weight], grads[conv.bias] = dwp, db
-                if need_x:
-                    gx = ops.conv3d_k3_bwd_data(dout, conv.weight.detach())
-                continue
-            dout, dgamma, dbeta = ops.bn_backward(acts[-1], gvols[si + 1], dpooled, argmax if dpooled is not None else None,
-                                                  mean, ss, relu_mask=True, training=ctx.training)
-            grads[bn.weight], grads[bn.bias] = dgamma, dbeta
-            for k in range(len(convs) - 1, -1, -1):
-                conv = convs[k]
-                cin = acts[k - 1] if k > 0 else inp
-                Co, Ci = conv.weight.shape[0], conv.weight.shape[1]
-                grads[conv.weight], grads[conv.bias] = ops.conv3d_k3_bwd_weight(cin, dout, param_layout=True)
-                if k > 0:
-                    dout = ops.conv3d_k3_bwd_data(dout, conv.weight.detach(), mask=acts[k - 1])
-                elif si > 0:
-                    dpooled = ops.conv3d_k3_bwd_data(dout, conv.weight.detach())
-                elif need_x:
-                    gx = ops.conv3d_k3_bwd_data(dout, conv.weight.detach())
+            dh0, link.dh0 = link.dh0, None
+            dw0 = _project_wide(fork, ext, levels, gvols, pts, dh0, ctx.w0p, orders, ready, proj, dPs, dw0)
+        if fork.on and not fork.pipelined:
+            fork.join()
+            feat = None      # (only now: see _Fork.start)
+        grads, gx = _stages_bwd(fork, ext, saved, gvols, ctx.training, need_x)
         if need_x:
-            if pipelined and 0 in level_done:
-                main.wait_event(level_done[0])
+            fork.wait_level(0)
             gx = (gx + gvols[0]).view(ctx.x_shape)
-        if dw0p is None:
-            dw0p = dw0_keep
-        if pipelined:      # the leaves of the side streams (dW0's slices, db0) and everything that reads the arena
-            main.wait_event(keep_done)
-            main.wait_stream(w_stream)
-            if p_stream is not None:
-                main.wait_stream(p_stream)
-            feat = None
+        if fork.pipelined:
+            fork.join()
         if lease is not None:
             lease.release()     # every kernel that touches the arena is enqueued; the next step orders itself behind them
             #                     (also expires the prepared weight planes: the optimizer is about to change the parameters)
-        out = [None, None, None, None, dw0p, db0, gx, gpts]
-        for p in ext._param_list:
-            out.append(grads.get(p))
-        return tuple(out)
-
-
-def _gvol(arena, level, like, zero):
-    """Gradient volume of a level for the backward scatter: from the step arena when there is one."""
-    if arena is None:
-        return torch.zeros_like(like) if zero else torch.empty_like(like)
-    g = arena.get(f"gvol{level}", tuple(like.shape), like.dtype, like.device)
-    return g.zero_() if zero else g
+        return (None, None, None, None, dw0, db0, gx, gpts) + tuple(grads.get(p) for p in ext._param_list)
 
 
 class _PointMLPFn(torch.autograd.Function):
@@ -607,44 +640,31 @@ class _PointMLPFn(torch.autograd.Function):
         gradient returned for it is the one wrt fc_0's pre-activation (h0's ReLU mask applied), the contract of
         _EncoderGatherFn's fused backward."""
         ctx.headless = w0p is None
-        if ctx.headless:
-            h0 = feat
-            h1 = ops.linear_fwd(h0, w1, b1, relu=True)
-            h2 = ops.linear_fwd(h1, w2, b2, relu=True)
-            logits = ops.fc_out_fwd(h2, wo, bo, row_map)
-            ctx.save_for_backward(w1, w2, wo, h0, h1, h2)
-            ctx.row_map = row_map
-            return logits
-        h0 = ops.linear_fwd(feat, w0p, b0, relu=True)
+        h0 = feat if ctx.headless else ops.linear_fwd(feat, w0p, b0, relu=True)
         h1 = ops.linear_fwd(h0, w1, b1, relu=True)
         h2 = ops.linear_fwd(h1, w2, b2, relu=True)
         logits = ops.fc_out_fwd(h2, wo, bo, row_map)
-        ctx.save_for_backward(feat, w0p, w1, w2, wo, h0, h1, h2)
+        ctx.save_for_backward(*(() if ctx.headless else (feat, w0p)), w1, w2, wo, h0, h1, h2)
         ctx.row_map = row_map
         ctx.link = link
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        if ctx.headless:
-            w1, w2, wo, h0, h1, h2 = ctx.saved_tensors
-            dh2, dwo, dbo = ops.fc_out_bwd(h2, wo, dlogits.contiguous(), ctx.row_map)
-            dw2, db2 = ops.linear_bwd_weight(dh2, h1)
-            dh1 = ops.linear_bwd_data(dh2, w2, mask=h1)
-            dw1, db1 = ops.linear_bwd_weight(dh1, h0)
-            dz0 = ops.linear_bwd_data(dh1, w1, mask=h0)
-            return dz0, None, None, None, dw1, db1, dw2, db2, dwo, dbo, None
-        feat, w0p, w1, w2, wo, h0, h1, h2 = ctx.saved_tensors
+        *head, w1, w2, wo, h0, h1, h2 = ctx.saved_tensors
         dh2, dwo, dbo = ops.fc_out_bwd(h2, wo, dlogits.contiguous(), ctx.row_map)   # dh2 already masked by h2 > 0
         dw2, db2 = ops.linear_bwd_weight(dh2, h1)
         dh1 = ops.linear_bwd_data(dh2, w2, mask=h1)
         dw1, db1 = ops.linear_bwd_weight(dh1, h0)
-        dh0 = ops.linear_bwd_data(dh1, w1, mask=h0)
-        link = ctx.link
+        dh0 = ops.linear_bwd_data(dh1, w1, mask=h0)      # wrt fc_0's pre-activation: what the headless form returns
+        tail = (dw1, db1, dw2, db2, dwo, dbo, None)
+        if ctx.headless:
+            return (dh0, None, None, None) + tail
+        (feat, w0p), link = head, ctx.link
         if link is None:
             dw0, db0 = ops.linear_bwd_weight(dh0, feat)
             dfeat = ops.linear_bwd_data(dh0, w0p) if ctx.needs_input_grad[0] else None
-            return dfeat, None, dw0, db0, dw1, db1, dw2, db2, dwo, dbo, None
+            return (dfeat, None, dw0, db0) + tail
         # projected wide levels: dX0 / dW0 only over the columns that stay (K 2592 -> 800); the encoder's backward gets dh0
         link.dh0 = dh0
         dw0 = torch.zeros_like(w0p)
@@ -657,7 +677,7 @@ class _PointMLPFn(torch.autograd.Function):
             if (a, b) in link.raw and not link.need_level0:
                 continue                          # raw-grid columns: their gradient is only needed for d(loss)/d(input)
             ops.linear_bwd_data(dh0, w0p[:, a:b], out=dfeat[:, a:b])
-        return dfeat, None, dw0, db0, dw1, db1, dw2, db2, dwo, dbo, None
+        return (dfeat, None, dw0, db0) + tail
 
 
 class _PermuteColumnsFn(torch.autograd.Function):
@@ -698,7 +718,6 @@ class _ExtractorBase(nn.Module):
         self._points_ready = None
 
     def __deepcopy__(self, memo):
-        import copy
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         new.__setstate__(copy.deepcopy(self.__getstate__(), memo))
@@ -735,28 +754,8 @@ class _ExtractorBase(nn.Module):
         model/ifnet.py:220-226).  Uses the module's current mode for BatchNorm (eval -> running stats)."""
         if not x.is_cuda:
             raise RuntimeError("IF-Net HIP path needs GPU tensors (no CPU fallback)")
-        B = x.shape[0]
-        D, H, W = x.shape[2:]
-        inp = x.float().contiguous().view(B, D, H, W, 1)
-        levels = [inp]
-        nst = len(self._stages)
-        for si, (convs, bn) in enumerate(self._stages):
-            if _stage1_applies(si, convs, inp):
-                conv = convs[0]
-                y, pooled = ops.stage1_fwd(inp, conv.weight.detach(), conv.bias.detach(), bn.weight.detach(), bn.bias.detach(),
-                                           bn.running_mean, bn.running_var, self.training, eps=bn.eps, momentum=bn.momentum,
-                                           want_pool=(si + 1 < nst))[:2]
-                levels.append(y)
-                inp = pooled
-                continue
-            cur = inp
-            for conv in convs:
-                cur = ops.conv3d_k3_fwd(cur, conv.weight.detach(), conv.bias.detach(), relu=True)
-            y, pooled, _, _, _ = ops.bn_forward(cur, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                                self.training, eps=bn.eps, momentum=bn.momentum, want_pool=(si + 1 < nst))
-            levels.append(y)
-            inp = pooled
-        return levels
+        B, _, D, H, W = x.shape
+        return _run_stages(self, x.float().contiguous().view(B, D, H, W, 1), self.training, for_backward=False)[0]
 
     @torch.no_grad()
     def feature_rows_from_levels(self, levels, points, order=None):
@@ -821,6 +820,12 @@ class IFNetFeatureExtractor(_ExtractorBase):
         self._finish_init(32)
 
 
+def _check_prepared_for(vols, levels):
+    """A prepare_query() descriptor holds ITS pyramid (slab table, volume pointers): a different `levels` would be ignored."""
+    if len(vols) != len(levels) or any(a.data_ptr() != b.data_ptr() or a.shape != b.shape for a, b in zip(vols, levels)):
+        raise RuntimeError("IFNet.query: `prepared` was made for another pyramid than `levels` (prepare_query again)")
+
+
 class IFNet(nn.Module):
     def __init__(self, hidden_dim=256, net_res=128):
         super().__init__()
@@ -873,7 +878,7 @@ class IFNet(nn.Module):
             prep.begin()
             # forward planes first, with their own event: the forward pass waits for those only, the backward planes (as many
             # launches again) are made while it runs
-            for which in (("fwd", "bwd") if PREPARE_FORWARD_FIRST else ("both",)):
+            for which in ("fwd", "bwd"):
                 for convs, _ in ext._stages:
                     for conv in convs:
                         if conv.weight.shape[1] > 1:
@@ -911,8 +916,7 @@ class IFNet(nn.Module):
                                                                                 self.fc_0.out_channels):
             prepared = ops.gather_fc0_bf16_prepare(levels, ext._layout, ext._disp, ext._align, self._fc0_internal())
         if prepared is not None:      # fused gather -> fc_0 on bf16 storage: the bf16 feature rows never reach HBM
-            if any(a.data_ptr() != b.data_ptr() or a.shape != b.shape for a, b in zip(prepared["vols"], levels)):
-                raise RuntimeError("IFNet.query: `prepared` was made for another pyramid than `levels` (prepare_query again)")
+            _check_prepared_for(prepared["vols"], levels)
             h = ops.gather_fc0_bf16_run(prepared, points, self.fc_0.bias, relu=True)
         else:
             rows = ops.gather_fwd_bf16(levels, points, ext._layout, ext._disp, ext._align)
@@ -953,10 +957,7 @@ class IFNet(nn.Module):
             return self._query_bf16(levels, points, row_map, prepared)
         ext = self.ifnet_feature_extractor
         if prepared is not None:
-            # the prepared descriptor holds ITS pyramid (slab table, volume pointers): a different `levels` would be ignored
-            if len(prepared.vols) != len(levels) or any(a.data_ptr() != b.data_ptr() or a.shape != b.shape
-                                                        for a, b in zip(prepared.vols, levels)):
-                raise RuntimeError("IFNet.query: `prepared` was made for another pyramid than `levels` (prepare_query again)")
+            _check_prepared_for(prepared.vols, levels)
             h, _ = ops.gather_fc0_run(prepared, points, self.fc_0.bias)
         elif FUSE_FC0 and ops.gather_fc0_supported(levels, points, ext._layout, ext._disp, ext._align, self.fc_0.out_channels):
             h, _ = ops.gather_fc0_fwd(levels, points, ext._layout, ext._disp, ext._align, self._fc0_internal(), self.fc_0.bias)
@@ -1008,24 +1009,19 @@ class IFNet(nn.Module):
         if (PROJECT_WIDE_LEVELS and torch.is_grad_enabled() and w0p.requires_grad and not points.requires_grad
                 and self.fc_0.out_channels == 256 and SCATTER_FORM != "atomic"
                 and not (ops.GATHER_FLAGS & ops._lib.GATHER_DETERMINISTIC)):
-            D, H, W = x.shape[2:]
             wide = [l for l, c in enumerate(ext._layout.channels) if c == 128 and
-                    ops.project_bwd_supported(B, N, (max(D >> (l - 1), 1), max(H >> (l - 1), 1), max(W >> (l - 1), 1)))]
+                    ops.project_bwd_supported(B, N, _level_dims(*x.shape[2:], l))]
             if wide and B * N * ext._layout.row_stride < 2 ** 31:
                 link = _ProjLink(wide, ext._layout)
+        tail = (self.fc_1.weight.squeeze(2), self.fc_1.bias, self.fc_2.weight.squeeze(2), self.fc_2.bias,
+                self.fc_out.weight.reshape(-1), self.fc_out.bias)
         if (FUSE_FC0 and not points.requires_grad and B * N * ext._layout.row_stride < 2 ** 31
                 and _fc0_fusable(ext._layout.channels, B, x.shape[2:], self.fc_0.out_channels)):
             h0 = ext.feature_rows(x, points, link, w0p, self.fc_0.bias, lease=lease)
-            logits = _PointMLPFn.apply(h0, row_map, None, None,
-                                       self.fc_1.weight.squeeze(2), self.fc_1.bias,
-                                       self.fc_2.weight.squeeze(2), self.fc_2.bias,
-                                       self.fc_out.weight.reshape(-1), self.fc_out.bias, None)
-            return logits.view(B, N)
-        rows = ext.feature_rows(x, points, link, w0p if link is not None else None, lease=lease)
-        logits = _PointMLPFn.apply(rows, row_map, w0p, self.fc_0.bias,
-                                   self.fc_1.weight.squeeze(2), self.fc_1.bias,
-                                   self.fc_2.weight.squeeze(2), self.fc_2.bias,
-                                   self.fc_out.weight.reshape(-1), self.fc_out.bias, link)
+            logits = _PointMLPFn.apply(h0, row_map, None, None, *tail, None)       # headless: fc_0 ran inside the gather
+        else:
+            rows = ext.feature_rows(x, points, link, w0p if link is not None else None, lease=lease)
+            logits = _PointMLPFn.apply(rows, row_map, w0p, self.fc_0.bias, *tail, link)
         return logits.view(B, N)
 
 

@@ -10,8 +10,6 @@ as four parity-class problems; the weight gradient through a gather loader in th
 plain-FMA kernels), BatchNorm in the 3-D encoder's kernels on (B,1,H,W,C) views; activations are channels-last inside.  The explicit
 patch-matrix path of rounds 2-3 (_ConvBlockFn) is kept for A/B (SVR_UNET_IGEMM=0) and for the bf16x3 / exact-f32 backward modes.
 backend="stock": the layers as stock PyTorch-ROCm ops (MIOpen), kept for A/B measurements (15-50 ms per config-5 step)."""
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -19,7 +17,6 @@ import torch.nn.functional as F
 from .. import ops
 
 
-PREPARE_MANY = os.environ.get("SVR_UNET_PREP_MANY", "1") != "0"    # "0": every block prepares its own planes (A/B)
 SMALL_M = 1024      # output pixels (times batch) up to which a layer's forward product runs as a split-reduction GEMM
 
 
@@ -180,7 +177,7 @@ class _UNetBase(nn.Module):
             raise RuntimeError("UNet HIP path needs GPU tensors (no CPU fallback; backend='stock' runs stock torch ops)")
         x = input.float().permute(0, 2, 3, 1).contiguous()                       # NCHW -> channels-last
         planes = {}
-        if _igemm_on() and PREPARE_MANY:    # the weight planes of all layers in three launches (instead of four per layer)
+        if _igemm_on():    # the weight planes of all layers in three launches (instead of four per layer)
             grad = torch.is_grad_enabled()
             names = [f"conv{i}" for i in range(1, len(self.ENC) + 1)] + [name for name, _, _, _ in self.DEC]
             items = [(getattr(self, nm).weight, 2 if nm.startswith("conv") else 1,
