@@ -724,6 +724,40 @@ int svr_cast_to_f32(const void *in, int32_t dtype, float *out, int64_t n, void *
 int svr_subsample_rows(const void *rows, int32_t dtype, int64_t n_rows, int32_t cols, const int64_t *idx, int64_t n_idx,
                        float *out, int32_t *bad_flag, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Raw views (data_processing/distance_to_depth.py, process_sample.py:17-21, dataset/scene_net_data.py:77-84).
+ *
+ * OpenEXR subset, host side (plain C++ + zlib; errors through svr_last_error):
+ *   read: single-part scanline files; compression NONE (0), ZIPS (2), ZIP (3); pixel types UINT (0), HALF (1),
+ *   FLOAT (2); any channel count (the file's alphabetical order); lineOrder 0 / 1; any data-window origin; blocks stored
+ *   raw because deflate did not shrink them.  Refused by name: tiled / multi-part / deep files, subsampled channels, every
+ *   other compression.  A truncated file or an offset beyond it is SVR_E_IO, never a read outside the file's bytes.
+ *   svr_exr_info: width, height, origin[2] = the data window's (x, y) minimum, the channel count, compression, lineOrder;
+ *     names (optional) receives the channel names, each NUL terminated, back to back (names_bytes of room);
+ *     pixel_types (optional) one code per channel; both need max_channels >= the channel count.
+ *   svr_exr_read_channel: one channel as float32 (HALF widened, UINT converted), (H, W) row major, top scanline of the
+ *     data window first, into `out` (host, n = W * H values; pinned memory is fine).  Unknown name: SVR_E_NOTFOUND.
+ *   svr_exr_write: data = (n_channels, H, W) float32 planes in the order of `names` (NUL terminated, back to back) ->
+ *     an uncompressed FLOAT scanline file, data window (0,0)-(W-1,H-1), channels sorted by name.
+ *
+ * Device side (raw_sample.hip):
+ *   svr_distance_to_depth: depth = sqrt(d*d / ((r*r + c*c) / (f*f) + 1)) over (B, H, W), r = row - H/2, c = col - W/2
+ *     (integer division; the reference centres on these integers, not on cx / cy).  r*r + c*c is an integer converted to
+ *     float32; every float32 operation is rounded on its own, in this order; the square root is correctly rounded.
+ *   svr_depth_grid_mark: one (H, W) map, a distance map (is_distance = 1: the rule above with `focal` first) or a depth
+ *     map -> the un-normalised grid-space coordinate of svr_unproject_fwd (same device function, same 12 consts) ->
+ *     round half to even -> grid[i0][i1][i2] = 1 (grid: D0*D1*D2 uint8, zeroed by the caller; plain stores of 1).
+ *     A pixel whose rounded index leaves [0, D) on any axis (NaN / inf included; indices in [-D, 0) are NOT wrapped) is
+ *     not written and adds 1 to *out_of_range (device int32, zeroed by the caller).  coords (optional): (H*W, 3) float32.
+ * ------------------------------------------------------------------------------------- */
+int svr_exr_info(const char *path, int32_t *width, int32_t *height, int32_t *origin /*[2]*/, int32_t *n_channels, char *names,
+                 int64_t names_bytes, int32_t *pixel_types, int32_t max_channels, int32_t *compression, int32_t *line_order);
+int svr_exr_read_channel(const char *path, const char *name, float *out, int64_t n);
+int svr_exr_write(const char *path, const float *data, int32_t H, int32_t W, const char *names, int32_t n_channels);
+int svr_distance_to_depth(const float *distance, float *depth, int32_t B, int32_t H, int32_t W, float focal, void *stream);
+int svr_depth_grid_mark(const float *map, int32_t is_distance, float focal, int32_t H, int32_t W, const float *consts /*[12]*/,
+                        uint8_t *grid, int32_t D0, int32_t D1, int32_t D2, int32_t *out_of_range, float *coords, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

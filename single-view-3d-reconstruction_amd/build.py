@@ -32,6 +32,8 @@ SOURCES = {
     "marching_cubes.hip": ["-ffp-contract=off"],
     "mesh_eval.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
+    "exr_io.cpp": [],
+    "raw_sample.hip": ["-ffp-contract=off"],
     "conv2d.hip": [],
     "conv2d_igemm.hip": [],
 }

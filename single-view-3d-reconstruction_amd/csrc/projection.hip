@@ -11,24 +11,19 @@
 // so the base-voxel arithmetic ((p+0.5)*(dims-1), floor) rounds exactly like torch's separate ops
 // and the integer voxel indices are bit-exact.
 #include "common.h"
+#include "unproject.h"
 
 using namespace svr;
 
 namespace {
-
-struct UnprojConsts {
-  float f, cx, cy, s00, t0, s11, t1, s22, t2, d0, d1, d2;
-};
 
 __global__ void unproject_fwd_kernel(const float *__restrict__ depth, float *__restrict__ pc, int64_t total, int Hi,
                                      int Wi, UnprojConsts c, int normalize) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   int u = (int)(i % Wi), v = (int)((i / Wi) % Hi);
-  float z = depth[i];
-  float X = ((float)u * z - c.cx * z) / c.f;
-  float Y = -(((float)v * z - c.cy * z) / c.f);
-  float gx = c.s00 * X + c.t0, gy = c.s11 * Y + c.t1, gz = c.s22 * z + c.t2;
+  float gx, gy, gz;
+  unproject_point(depth[i], u, v, c, gx, gy, gz);
   if (normalize) {
     gx = (gx - c.d0 / 2.f) / c.d0;
     gy = (gy - c.d1 / 2.f) / c.d1;
@@ -188,8 +183,6 @@ __global__ __launch_bounds__(256) void blur_taps_grad_kernel(const float *__rest
   }
 }
 
-UnprojConsts load_consts(const float *c) { return UnprojConsts{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11]}; }
-
 int axis_geometry(int D0, int D1, int D2, int axis, int *len, int64_t *stride) {
   SVR_CHECK(axis >= 0 && axis <= 2, SVR_E_BADARG, "blur: axis %d", axis);
   *len = axis == 0 ? D0 : (axis == 1 ? D1 : D2);
@@ -205,7 +198,7 @@ extern "C" int svr_unproject_fwd(const float *depth, float *pc, int32_t B, int32
   int64_t total = (int64_t)B * Hi * Wi;
   if (total <= 0) return SVR_OK;
   hipLaunchKernelGGL(unproject_fwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, depth, pc,
-                     total, Hi, Wi, load_consts(consts), normalize);
+                     total, Hi, Wi, unproj_consts(consts), normalize);
   return launch_status("unproject_fwd");
 }
 
@@ -216,7 +209,7 @@ extern "C" int svr_unproject_bwd(const float *depth, const float *gpc, float *gd
   int64_t total = (int64_t)B * Hi * Wi;
   if (total <= 0) return SVR_OK;
   hipLaunchKernelGGL(unproject_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, gpc,
-                     gdepth, total, Hi, Wi, load_consts(consts), normalize);
+                     gdepth, total, Hi, Wi, unproj_consts(consts), normalize);
   return launch_status("unproject_bwd");
 }
 

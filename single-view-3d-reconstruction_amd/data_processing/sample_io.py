@@ -1,5 +1,5 @@
 """Native readers for the sample wire formats: thin numpy-level wrappers over the C ABI's host
-functions (svr_df_*, svr_npz_member_*: C++ + zlib inside libsvr_hip.so; no GPU involved) and the device-side helpers
+functions (svr_df_*, svr_npz_member_*, svr_exr_*: C++ + zlib inside libsvr_hip.so; no GPU involved) and the device-side helpers
 (transpose / cast / row subset).  `out=` lets the caller pass a pinned buffer so the H2D copy can be asynchronous."""
 import ctypes as C
 import os
@@ -54,6 +54,47 @@ def npz_load(path, member, out=None):
     check(_lib.lib().svr_npz_member_read(_path(path), member.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes),
           "npz_member_read")
     return out.reshape(shape, order="F" if fortran else "C")
+
+
+EXR_PIXEL_TYPES = {0: "UINT", 1: "HALF", 2: "FLOAT"}
+EXR_COMPRESSIONS = {0: "NONE", 2: "ZIPS", 3: "ZIP"}
+
+
+def exr_info(path):
+    """Header of a single-part scanline OpenEXR file (the subset of include/svr_hip.h): {"width", "height", "origin": the
+    data window's (x, y) minimum, "channels": [(name, "UINT" | "HALF" | "FLOAT")] in the file's order, "compression":
+    "NONE" | "ZIPS" | "ZIP", "line_order"}.  Anything outside the subset raises with the reason."""
+    w, h, n, comp, lo = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    origin = (C.c_int32 * 2)()
+    names = C.create_string_buffer(1 << 16)
+    types = (C.c_int32 * 1024)()
+    check(_lib.lib().svr_exr_info(_path(path), C.byref(w), C.byref(h), origin, C.byref(n), names, len(names), types, 1024,
+                                  C.byref(comp), C.byref(lo)), "exr_info")
+    nm = names.raw.split(b"\0")[:n.value]
+    return {"width": w.value, "height": h.value, "origin": (origin[0], origin[1]),
+            "channels": [(nm[i].decode(), EXR_PIXEL_TYPES[types[i]]) for i in range(n.value)],
+            "compression": EXR_COMPRESSIONS[comp.value], "line_order": lo.value}
+
+
+def exr_read(path, channel="R", out=None):
+    """One channel as an (H, W) float32 array, top scanline first (pyexr.open(path).get(channel)[:, :, 0]); `out`: a
+    float32 numpy array of H * W values, e.g. the numpy view of a pinned tensor."""
+    info = exr_info(path)
+    H, W = info["height"], info["width"]
+    if out is None:
+        out = np.empty(H * W, dtype=np.float32)
+    assert out.dtype == np.float32 and out.size == H * W and out.flags["C_CONTIGUOUS"]
+    check(_lib.lib().svr_exr_read_channel(_path(path), channel.encode(), out.ctypes.data_as(C.c_void_p), H * W), "exr_read_channel")
+    return out.reshape(H, W)
+
+
+def exr_write(path, channels):
+    """{name: (H, W) array} -> an uncompressed FLOAT scanline file (what visualize_depthmap's .exr output needs)."""
+    names = list(channels)
+    planes = np.ascontiguousarray(np.stack([np.asarray(channels[k], dtype=np.float32) for k in names]))
+    assert planes.ndim == 3, "exr_write: every channel is an (H, W) array"
+    check(_lib.lib().svr_exr_write(_path(path), planes.ctypes.data_as(C.c_void_p), planes.shape[1], planes.shape[2],
+                                   b"\0".join(k.encode() for k in names) + b"\0", len(names)), "exr_write")
 
 
 # ---- device side -------------------------------------------------------------------------------------------------
