@@ -758,6 +758,53 @@ int svr_distance_to_depth(const float *distance, float *depth, int32_t B, int32_
 int svr_depth_grid_mark(const float *map, int32_t is_distance, float focal, int32_t H, int32_t W, const float *consts /*[12]*/,
                         uint8_t *grid, int32_t D0, int32_t D1, int32_t D2, int32_t *out_of_range, float *coords, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Stage visualisation of the scene trainer (replaces util/visualize.py:10-20,28-49: to_point_list + trimesh's multibox,
+ * numpy + PIL + pyexr; called by trainer/trainer_scene_net.py:170-188).  Errors, ownership and streams as for svr_mc_*.
+ *
+ * Voxel-box mesher.  field: (X, Y, Z) float32, C order, on the device; output: the welded boundary surface of the union
+ * of unit cubes centred on the occupied indices, in the field's index space (x along axis 0, as marching cubes).
+ *   - voxel (i, j, k) is occupied iff (double)v >= threshold (NaN: not occupied) and is the cube [i-1/2, i+1/2] x
+ *     [j-1/2, j+1/2] x [k-1/2, k+1/2]; a cube face is emitted iff the voxel across it is unoccupied or outside the lattice
+ *     (multibox's triangle set minus the faces shared by two boxes);
+ *   - vertices: points (a, b, c) of the (X+1)(Y+1)(Z+1) corner lattice at (a-1/2, b-1/2, c-1/2); a corner is emitted once
+ *     iff an emitted face touches it (the 8 voxels around it, outside = empty, are neither all empty nor all occupied);
+ *     ordered by the corner's C-order index;
+ *   - faces: by voxel (C order), then direction -x, +x, -y, +y, -z, +z; each a quad q0 q1 q2 q3, counter-clockwise from
+ *     outside, as the triangles (q0, q1, q2), (q0, q2, q3); corner offsets (x y z) from the voxel's minimum corner:
+ *       -x: 000 001 011 010   +x: 100 110 111 101   -y: 000 100 101 001
+ *       +y: 010 011 111 110   -z: 000 010 110 100   +z: 001 101 111 011
+ *   svr_voxel_mesh_workspace_bytes: device workspace (negative = SVR_E_BADSHAPE: a corner lattice of 2^31 points or more).
+ *   svr_voxel_mesh_count: classify + scan; writes the device int64 totals[2] = {V, F} (F triangles).  The caller reads
+ *                  them back, checks V, F < 2^31 and allocates verts (V, 3) float32 and faces (F, 3) int32.
+ *   svr_voxel_mesh_emit: fills verts / faces from the same workspace (after svr_voxel_mesh_count on the stream).  An
+ *                  extent of 0 gives an empty mesh.
+ *
+ * Depth-map image planes (map: (H, W) float32 on the device):
+ *   svr_depth_minmax: stats[4] (device uint32; [0] = ~key(min), [1] = key(max), [2] = 1 if any value is NaN / inf (such
+ *     values take no part in min / max), [3] unused; key(v) = the float's bits with the sign bit set for v >= 0 and all
+ *     bits flipped for v < 0, whose unsigned order is the floats' order).
+ *   svr_depth_planes: plane_f32[r][c] = d = map[r][flip ? W-1-c : c]; plane_u8[r][c] = (uint8)(255.0f / max * (d - min)):
+ *     float32 division, subtraction and product, each rounded on its own, then truncation toward zero (a value past 255
+ *     keeps its low 8 bits).  min / max are read from `stats` on the device.
+ *
+ * Host only:
+ *   svr_write_png_gray8: data (H, W) uint8 -> a PNG file: signature, IHDR (bit depth 8, colour type 0, no interlace), one
+ *     zlib-deflated IDAT with filter type 0 on every scanline, IEND, CRC-32 on every chunk.
+ *   svr_write_obj_points: pts (n, 3) float32 -> one line `v %f %f %f %f %f %f` per point: the coordinates + 0.5 (added in
+ *     float32, then widened) and the colour 1 1 1 (visualize_point_list, util/visualize.py:14-20).  n == 0: an empty file.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_voxel_mesh_workspace_bytes(int32_t X, int32_t Y, int32_t Z);
+int svr_voxel_mesh_count(const float *field, int32_t X, int32_t Y, int32_t Z, double threshold, void *ws, int64_t ws_bytes,
+                         int64_t *totals, void *stream);
+int svr_voxel_mesh_emit(const float *field, int32_t X, int32_t Y, int32_t Z, double threshold, void *ws, float *verts,
+                        int32_t *faces, void *stream);
+int svr_depth_minmax(const float *map, int64_t n, uint32_t *stats /*[4]*/, void *stream);
+int svr_depth_planes(const float *map, int32_t H, int32_t W, int32_t flip, const uint32_t *stats, float *plane_f32,
+                     uint8_t *plane_u8, void *stream);
+int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W);
+int svr_write_obj_points(const char *path, const float *pts, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,13 @@ SIGNATURES = {
     "svr_scale_clamp01_bwd": (C.c_int, [P, P, P, I64, F32, P]),
     "svr_blur_axis_fwd": (C.c_int, [P, P, P, I32, I32, I32, I32, I32, I32, P]),
     "svr_blur_axis_bwd": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, P]),
+    "svr_voxel_mesh_workspace_bytes": (I64, [I32, I32, I32]),
+    "svr_voxel_mesh_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
+    "svr_voxel_mesh_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),
+    "svr_depth_minmax": (C.c_int, [P, I64, P, P]),
+    "svr_depth_planes": (C.c_int, [P, I32, I32, I32, P, P, P, P]),
+    "svr_write_png_gray8": (C.c_int, [C.c_char_p, P, I32, I32]),
+    "svr_write_obj_points": (C.c_int, [C.c_char_p, P, I64]),
 }
 
 _lib = None

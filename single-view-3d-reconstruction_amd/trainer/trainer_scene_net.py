@@ -11,18 +11,26 @@ The UNet is stock PyTorch-ROCm ops; unprojection, splat, blur, e
 MLP and the BCE run in the HIP kernels.  `subsample_points != 0` (:91-99,108-114): the projected point cloud is
 queried too and labelled against the sample's mesh ON THE DEVICE (..data_processing.mesh_occupancies.determine_occupancy,
 SURVEY §8 f3) -- the reference copies it to the host and runs trimesh + Cython + numpy per step.
+
+``validation_step`` / ``test_step`` / ``visualize_intermediates`` (:121-143,170-188) write every stage of a view -- the
+predicted depth map (.png + .exr), its voxelisation (.obj of boxes) and the predicted mesh (.obj) -- into an `output_dir`
+the caller names (the reference's runs/<experiment>/vis/<global_step // 100>: there is no Lightning here).  Grid, lattice
+and depth map stay on the device; meshes and image planes are what crosses to the host.
 """
+from pathlib import Path
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from ..model.ifnet import IFNet
+from ..model.ifnet import IFNet, implicit_to_mesh
 from ..model.projection import project
 from ..model.unet import UNetMini, Unet
 from ..data_processing.mesh_occupancies import determine_occupancy
+from ..util.visualize import visualize_depthmap, visualize_grid
 
 
 class _BCELogitsMeanFn(torch.autograd.Function):
@@ -43,7 +51,7 @@ class _BCELogitsMeanFn(torch.autograd.Function):
 def default_hparams(**kw):
     h = dict(lr=1e-4, kernel_size=[3, 3, 3], sigma=[1.5, 1.5, 1.5], scale_factor=1, resize_input=True, skip_unet=False,
              subsample_points=0, no_depth_sup=False, min_z=0.1953997164964676, max_z=7.0, net_res=128,
-             reference_occupancy_quirk=True, miopen_benchmark=True)
+             reference_occupancy_quirk=True, miopen_benchmark=True, visualize=False, inf_res=1)
     h.update(kw)
     return SimpleNamespace(**h)
 
@@ -138,3 +146,43 @@ class SceneNetTrainer(nn.Module):
         occupancies = self._occupancies(batch, point_cloud)
         loss = self.losses_and_logging(batch, depthmap, logits, occupancies, "train")
         return {"loss": loss}
+
+    def validation_step(self, batch, batch_idx, output_dir=None):
+        """trainer_scene_net.py:121-137: the training step's forward and loss without gradients, logged as val_*; with
+        ``hparams.visualize`` the intermediates go to `output_dir`.  The module's train / eval mode is the caller's (as
+        under Lightning, which switches to eval around validation)."""
+        with torch.no_grad():
+            logits, depthmap, point_cloud = self.forward(batch)
+            occupancies = self._occupancies(batch, point_cloud)
+            if getattr(self.hparams, "visualize", False):
+                if output_dir is None:
+                    raise ValueError("validation_step: hparams.visualize needs an output_dir")
+                self.visualize_intermediates(batch, depthmap, point_cloud, output_dir)
+            loss = self.losses_and_logging(batch, depthmap, logits, occupancies, "val")
+        return {"val_loss": loss}
+
+    def test_step(self, batch, batch_idx, output_dir):
+        """trainer_scene_net.py:139-143 (the reference's --test mode): forward, then every intermediate of every item."""
+        with torch.no_grad():
+            _, depthmap, point_cloud = self.forward(batch)
+            self.visualize_intermediates(batch, depthmap, point_cloud, output_dir)
+        return {"loss": 0}
+
+    def visualize_intermediates(self, batch, depthmap, point_cloud, output_dir):
+        """trainer_scene_net.py:170-188.  Per item, with base = "_".join(name.split("/")[-3:]):
+        ``<base>_voxelized.obj`` (visualize_grid of the re-projected point cloud's occupancy), ``<base>_predicted.obj``
+        (implicit_to_mesh at threshold_p = 0.5 on self.dims, res_increase = hparams.inf_res) and ``<base>_depthmap.png`` /
+        ``.exr`` (columns flipped, as the reference)."""
+        out = Path(output_dir)
+        out.mkdir(exist_ok=True, parents=True)
+        dims = self.dims.cpu().numpy().astype(np.int32)
+        inf_res = int(getattr(self.hparams, "inf_res", 1))
+        with torch.no_grad():
+            voxel_occupancy = self.project(point_cloud)
+            for i in range(len(batch["name"])):
+                base = "_".join(batch["name"][i].split("/")[-3:])
+                vox = voxel_occupancy[i]
+                visualize_grid(vox.reshape(vox.shape[-3:]), out / f"{base}_voxelized.obj")
+                implicit_to_mesh(self.ifnet, vox.reshape(1, 1, *vox.shape[-3:]), dims, 0.5, out / f"{base}_predicted.obj",
+                                 res_increase=inf_res)
+                visualize_depthmap(depthmap[i], out / f"{base}_depthmap", flip=True)
