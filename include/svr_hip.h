@@ -131,9 +131,19 @@ int svr_gather_pull_plan(const float *points, int32_t B, int32_t N, int32_t D, i
 int svr_gather_item_order(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W,
                           int32_t align_corners, float displacement, int32_t with_j /* 1: order by (cell, j) */,
                           int32_t *items, void *workspace, void *stream);
+/* The x-BLOCK order of the projected scatter's atomic form: items sorted by
+ *   (sample, z, y, x / block, j, x % block)        (x, y, z = base cell + 1; block in [1, W + 1])
+ * so that inside a block of `block` x-adjacent cells the runs of ONE displacement follow each other and
+ * svr_gather_project_bwd hands the shared face of two neighbours over in registers instead of adding it to dP twice.
+ * block = 1 is exactly svr_gather_item_order(with_j = 1).  The scatter's result does not depend on the order (it finds
+ * its runs from the points), only its speed does.  Same workspace, same key width limits as svr_gather_item_order.   */
+int svr_gather_item_order_xblock(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W,
+                                 int32_t align_corners, float displacement, int32_t block, int32_t *items,
+                                 void *workspace, void *stream);
 /* Backward-only projection of a wide level (gather.hip, gather_bwd_proj_kernel): the scatter commutes with fc_0's
  * product, so the level's 7*C feature columns need neither dX nor dW of the point MLP over all points:
  *   dP[b][v][j][0:256] += w(item, v) * dh[(b*N+n)][0:256]   for every item (n, j) of svr_gather_item_order(with_j = 1)
+ * or svr_gather_item_order_xblock (fewer float atomics; any permutation of the item ids gives the same sums)
  * (dP: (B, D*H*W, 7, 256) float32, zero-initialised by the caller; dh: the gradient wrt fc_0's pre-activation, row
  * stride lddh >= 256).  The caller finishes with two GEMMs over VOXELS: dvol = dP W0_l, dW0_l = dP^T vol.       */
 int svr_gather_project_bwd(const float *points, const float *dh, int64_t lddh, int32_t B, int32_t N, int32_t D, int32_t H,

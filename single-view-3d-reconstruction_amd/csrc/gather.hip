@@ -569,6 +569,13 @@ __device__ __forceinline__ void gather_bwd_items_body(const LevelArgs L, const f
     }
     flush(cur1, b1, acc1, skip);
   };
+  // Broadcast of one item's geometry from the lane that computed it.  With CW = 64 the run group is the whole wave, the
+  // value is wave-uniform and the lane index a loop counter: v_readlane_b32 puts it in an SGPR (no ds_bpermute, no VGPR)
+  auto bcast = [&](int v, int src) -> int {
+    if constexpr (CW == 64) return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src));
+    else return __shfl(v, src);
+  };
+  auto bcastf = [&](float v, int src) -> float { return __int_as_float(bcast(__float_as_int(v), src)); };
   constexpr int UNR = 4;   // items per block of loads; two blocks in flight (the dh rows come from the Infinity Cache / HBM: latency bound)
   for (int rep = 0; rep < REPS; ++rep) {
     const int64_t i0 = base_i + (int64_t)rep * PG;
@@ -608,7 +615,7 @@ __device__ __forceinline__ void gather_bwd_items_body(const LevelArgs L, const f
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
         const int t = blk * UNR + u, s = t >= CW ? 1 : 0;
-        const int go = __shfl(s ? goff[1] : goff[0], grp * CW + t - s * CW);
+        const int go = bcast(s ? goff[1] : goff[0], grp * CW + t - s * CW);
 #pragma unroll
         for (int p = 0; p < CPL; ++p) gq[u * CPL + p] = gfeat[(t < cnt ? go : 0) + cg * CW * CPL + ch + p * CW];  // unconditional loads
       }
@@ -617,22 +624,34 @@ __device__ __forceinline__ void gather_bwd_items_body(const LevelArgs L, const f
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
         const int t = blk * UNR + u, s = t >= CW ? 1 : 0, src = grp * CW + t - s * CW;
-        const int kraw = __shfl(s ? key[1] : key[0], src);
-        const int bqu = __shfl(s ? bb[1] : bb[0], src);
-        const float xq = __shfl(s ? fx[1] : fx[0], src), yq = __shfl(s ? fy[1] : fy[0], src),
-                    zq = __shfl(s ? fz[1] : fz[0], src);
+        const int kraw = bcast(s ? key[1] : key[0], src);
+        const int bqu = bcast(s ? bb[1] : bb[0], src);
+        const float xq = bcastf(s ? fx[1] : fx[0], src), yq = bcastf(s ? fy[1] : fy[0], src),
+                    zq = bcastf(s ? fz[1] : fz[0], src);
         const int kk = t < cnt ? kraw : -1;
         if (kk < 0) continue;  // item touches no voxel (or padding slot)
         if constexpr (PROJ) {
-          // items arrive sorted by (sample, cell, displacement): a run never comes back, one open run is enough (and the
-          // next run is another displacement of the same cell -- another slice of dP -- so there is nothing to hand over)
+          // items arrive sorted so that a run never comes back: one open run is enough.  Under the x-block order
+          // (svr_gather_item_order_xblock) the next run is often the +x neighbour cell of the same (sample, displacement):
+          // the 4 corners of the shared face stay in registers as the new run's -x face and only the old run's -x face is
+          // flushed.  (The x field is the low 10 bits and x <= W < 1022: + 1 never carries into y.)  Any other successor --
+          // every one of the (cell, j) order, where it is another displacement of the same cell -- flushes all 8 corners.
+          // The two-pass form never hands over: its partial-sum slots are per run.
           if (kk != cur0 || bqu != b0) {
-            flush(cur0, b0, acc0, 0);
+            const bool hand = !STORE && cur0 >= 0 && bqu == b0 && kk == cur0 + 1;   // wave-uniform
+            flush(cur0, b0, acc0, hand ? 0xAA : 0);
+            if (hand) {
 #pragma unroll
-            for (int k = 0; k < 8 * CPL; ++k) acc0[k] = 0.f;
+              for (int k = 0; k < 8; k += 2)
+#pragma unroll
+                for (int p = 0; p < CPL; ++p) { acc0[k * CPL + p] = acc0[(k + 1) * CPL + p]; acc0[(k + 1) * CPL + p] = 0.f; }
+            } else {
+#pragma unroll
+              for (int k = 0; k < 8 * CPL; ++k) acc0[k] = 0.f;
+            }
             cur0 = kk;
             b0 = bqu;
-            if constexpr (STORE) slot0 = __shfl(s ? sid[1] : sid[0], src);
+            if constexpr (STORE) slot0 = bcast(s ? sid[1] : sid[0], src);
           }
         } else if (kk != cur0 || bqu != b0) {
           if (kk == cur1 && bqu == b1) {  // hit on the older run: make it the most recent
@@ -710,7 +729,8 @@ __host__ __device__ inline int items_cpl(int C) { return C >= 32 ? 2 : 1; }
 //     dvol_l[v][c]     = sum_{j,n} dP_l[v][j][n] W0[n][(l,j,c)]      (a GEMM over voxels: 32 768 x 1792 x 128 at level 4)
 //     dW0[n][(l,j,c)]  = sum_v dP_l[v][j][n] vol_l[v][c]             (ditto)
 // so neither dX0 nor dW0 of the point MLP has to touch the level's 896 columns over 400 000 points (K 2592 -> 800 with
-// both 128-channel levels projected).  The forward pass is unchanged.  Items arrive sorted by (sample, cell, j).
+// both 128-channel levels projected).  The forward pass is unchanged.  Items arrive in the x-block order of
+// svr_gather_item_order_xblock (block length 1 = sorted by (sample, cell, j)); any order gives the same sums.
 __global__ __launch_bounds__(256) void gather_bwd_proj_kernel(LevelArgs L, const float *__restrict__ points,
                                                               const float *__restrict__ dh, int64_t T, int N, int lddh,
                                                               float disp, int ac, int64_t waves) {
@@ -897,7 +917,7 @@ __device__ __forceinline__ bool pull_cell(const float *pt, int j, float disp, in
 
 __global__ __launch_bounds__(256) void pull_key_kernel(const float *__restrict__ points, uint32_t *__restrict__ keys,
                                                        int32_t *__restrict__ vals, int64_t total, int N, int D, int H,
-                                                       int W, float disp, int ac, uint32_t sentinel, int with_j) {
+                                                       int W, float disp, int ac, uint32_t sentinel, int kblk) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // item = pn * 7 + j
   if (i >= total) return;
   const int64_t pn = i / 7;
@@ -906,7 +926,13 @@ __global__ __launch_bounds__(256) void pull_key_kernel(const float *__restrict__
   float fx, fy, fz;
   const float p3[3] = {points[pn * 3], points[pn * 3 + 1], points[pn * 3 + 2]};
   const bool ok = pull_cell(p3, j, disp, D, H, W, ac, (int)(pn / N), key, fx, fy, fz);
-  keys[i] = ok ? (with_j ? key * 8u + (uint32_t)j : key) : sentinel;   // with_j: (cell, displacement) order
+  // kblk = 0: cell order.  kblk = K >= 1: (row, x block of K cells, displacement, x inside the block) -- the x-block order
+  // of svr_gather_item_order_xblock; K = 1 is key * 8 + j, the (cell, displacement) order
+  if (ok && kblk > 0) {
+    const uint32_t w1 = (uint32_t)W + 1u, K = (uint32_t)kblk, row = key / w1, x = key - row * w1;
+    key = ((row * ((w1 + K - 1u) / K) + x / K) * 8u + (uint32_t)j) * K + x % K;
+  }
+  keys[i] = ok ? key : sentinel;
   vals[i] = (int32_t)i;
 }
 
@@ -1284,14 +1310,17 @@ extern "C" int svr_gather_pull_plan(const float *points, int32_t B, int32_t N, i
   return svr::launch_status("pull_plan");
 }
 
-extern "C" int svr_gather_item_order(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W,
-                                     int32_t align_corners, float displacement, int32_t with_j, int32_t *items,
-                                     void *workspace, void *stream) {
+namespace {
+// kblk = 0: items by cell; K >= 1: by (row, x block of K cells, displacement, x inside the block)
+int item_order_impl(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W, int32_t align_corners,
+                    float displacement, int32_t kblk, int32_t *items, void *workspace, void *stream) {
   const int64_t T = (int64_t)7 * B * N;
   SVR_CHECK(B >= 0 && N >= 0 && D > 0 && H > 0 && W > 0, SVR_E_BADSHAPE, "item_order: B=%d N=%d dims %dx%dx%d", B, N, D, H, W);
+  SVR_CHECK(kblk >= 0 && kblk <= W + 1, SVR_E_BADARG, "item_order: block length %d outside [1, W + 1 = %d]", kblk, W + 1);
   if (T == 0) return SVR_OK;
   SVR_CHECK(points && items && workspace, SVR_E_BADARG, "item_order: null pointer");
-  const int64_t cells = pull_cells(B, D, H, W), nkeys = with_j ? cells * 8 : cells;
+  const int64_t cells = pull_cells(B, D, H, W);
+  const int64_t nkeys = kblk ? (int64_t)B * (D + 1) * (H + 1) * svr::cdiv((int64_t)W + 1, (int64_t)kblk) * 8 * kblk : cells;
   SVR_CHECK(nkeys < (1LL << 31) - 1 && T < (1LL << 31), SVR_E_UNSUPPORTED, "item_order: %ld keys / %ld items exceed 32 bits",
             (long)nkeys, (long)T);
   hipStream_t s = (hipStream_t)stream;
@@ -1304,11 +1333,25 @@ extern "C" int svr_gather_item_order(const float *points, int32_t B, int32_t N, 
   w += al256(T * 4);
   const int bits = pull_key_bits(nkeys);
   hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys_in, vals_in, T, N, D, H,
-                     W, displacement, align_corners, (uint32_t)nkeys, with_j ? 1 : 0);
+                     W, displacement, align_corners, (uint32_t)nkeys, kblk);
   hipError_t e = svr::sort_pairs_u32((void *)w, svr::sort_pairs_u32_temp_bytes(T, bits), keys_in, keys_out, vals_in, items, T,
                                      bits, s);
   SVR_CHECK(e == hipSuccess, (int)e, "item_order: radix sort failed: %s", hipGetErrorString(e));
   return svr::launch_status("item_order");
+}
+}  // namespace
+
+extern "C" int svr_gather_item_order(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W,
+                                     int32_t align_corners, float displacement, int32_t with_j, int32_t *items,
+                                     void *workspace, void *stream) {
+  return item_order_impl(points, B, N, D, H, W, align_corners, displacement, with_j ? 1 : 0, items, workspace, stream);
+}
+
+extern "C" int svr_gather_item_order_xblock(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W,
+                                            int32_t align_corners, float displacement, int32_t block, int32_t *items,
+                                            void *workspace, void *stream) {
+  SVR_CHECK(block >= 1, SVR_E_BADARG, "item_order_xblock: block length %d < 1", block);
+  return item_order_impl(points, B, N, D, H, W, align_corners, displacement, block, items, workspace, stream);
 }
 
 extern "C" int svr_gather_project_bwd(const float *points, const float *dh, int64_t lddh, int32_t B, int32_t N, int32_t D,

@@ -144,7 +144,8 @@ def _level_orders_async(pts, D, H, W, n_levels, align, layout=None, disp=None, p
                     orders[l] = ops.project_plan(pts, dhw, disp, align)      # two-pass form: no float atomics
                     orders[l].record_stream(main)
                 else:
-                    orders[l] = ops.item_order(pts, dhw, disp, align, with_j=True, arena=arena, tag=tag)
+                    # atomic form: x-block order, so that x-neighbour runs hand their shared face over in registers
+                    orders[l] = ops.item_order(pts, dhw, disp, align, arena=arena, tag=tag, x_block=ops.proj_x_block(N, dhw))
                     if arena is None:
                         orders[l].record_stream(main)
                 launched = True

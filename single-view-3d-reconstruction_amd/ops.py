@@ -176,17 +176,41 @@ def pull_plan(points, dims, C, col, row_stride, displacement, align_corners=Fals
     return plan
 
 
-def item_order(points, dims, displacement, align_corners=False, with_j=False, arena=None, tag=""):
+def item_order(points, dims, displacement, align_corners=False, with_j=False, arena=None, tag="", x_block=None):
     """(7*B*N,) int32 item ids pn*7+j sorted by (sample, base cell of the displaced sample[, displacement j]) in a
-    volume of `dims`."""
+    volume of `dims`.  x_block = K (1 .. W + 1): the x-block order of the projected scatter's atomic form, (sample, z, y,
+    block of K x-adjacent cells, j, x inside the block); K = 1 is the with_j order."""
     _f32(points)
     B, N, _ = points.shape
     l = _lib.lib()
     items = _alloc(arena, tag + "items", (max(7 * B * N, 1),), torch.int32, points.device)
     ws = _alloc(arena, "plan_ws", (l.svr_gather_pull_plan_workspace(B, N),), torch.uint8, points.device)
+    if x_block is not None:
+        check(l.svr_gather_item_order_xblock(_p(points), B, N, dims[0], dims[1], dims[2], int(align_corners), displacement,
+                                             int(x_block), _p(items), _p(ws), _stream()), "gather_item_order_xblock")
+        return items
     check(l.svr_gather_item_order(_p(points), B, N, dims[0], dims[1], dims[2], int(align_corners), displacement, int(with_j),
                                   _p(items), _p(ws), _stream()), "gather_item_order")
     return items
+
+
+PROJ_WAVE_CHUNK = 256      # items one wave of gather_bwd_proj_kernel walks (2 x 64 lanes x kProjReps)
+PROJ_BLOCK_SHARE = 2.25    # see proj_x_block
+
+
+def proj_x_block(N, dims):
+    """Block length K of the x-block item order for the atomic projected scatter of one level.
+
+    A face is handed over only between two runs that sit in the same wave's chunk of PROJ_WAVE_CHUNK items, and a block
+    puts K runs of about r = N / (D*H*W) items in a row for every displacement.  Longer blocks hand more faces over, but
+    move the 7 displacements of a point (which read the same dh row) further apart, so a (block, j) row of runs is
+    allowed 1 / PROJ_BLOCK_SHARE of a chunk:  K = floor(PROJ_WAVE_CHUNK / (PROJ_BLOCK_SHARE * r)), at least 1 (the plain
+    (cell, j) order: runs that fill a third of a chunk each leave little to hand over), at most W + 1.
+    PROJ_BLOCK_SHARE was fitted on ONE workload -- the benched step, 50 000 uniform points per sample, where K = 9
+    measured best among {1, 3, 4, 6, 9} at 16^3 (r = 12; tools/exp/bench_proj.py, profiles/proj_handover_bench_proj.txt)
+    and K = 1 is kept at 8^3 (r = 98, where no K gains more than 5 %) -- not on a range of shapes."""
+    r = N / float(dims[0] * dims[1] * dims[2])
+    return max(1, min(dims[2] + 1, int(PROJ_WAVE_CHUNK / (PROJ_BLOCK_SHARE * max(r, 1e-9)))))
 
 
 def project_bwd_supported(B, N, dims, lddh=256):

@@ -1,4 +1,5 @@
-"""Micro-benchmark of the projected backward scatter (gather_bwd_proj_kernel) at the config-3 shape."""
+"""Micro-benchmark of the projected backward scatter (gather_bwd_proj_kernel) at the config-3 shape: the two-pass form,
+and the atomic form under the x-block item order for the block lengths K the rule ops.proj_x_block was fitted on."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -30,3 +31,12 @@ for S in (16, 8):
     slots = int(plan.sidx[-1])
     print(f"S={S}: plan {t_p:.3f} ms, two-pass scatter {t2:.3f} ms, {slots} slots of {plan.slots}, "
           f"max dev {float((a - b).abs().max() / a.abs().max()):.2e}")
+    # atomic form, x-block order (K = 1 is the (cell, j) order above): order + scatter, and the deviation from K = 1
+    for K in (1, 3, 4, 6, 9):
+        it = ops.item_order(pts, (S, S, S), 0.0722, False, x_block=K)
+        t_o = timeit(lambda: ops.item_order(pts, (S, S, S), 0.0722, False, x_block=K))
+        t = timeit(lambda: ops.gather_project_bwd(pts, dh, (S, S, S), it, 0.0722, False))
+        c = ops.gather_project_bwd(pts, dh, (S, S, S), it, 0.0722, False)
+        print(f"S={S} K={K}: item order {t_o:.3f} ms, projected scatter (incl. dP memset) {t:.3f} ms, "
+              f"max dev from K=1 {float((c - a).abs().max() / a.abs().max()):.2e}"
+              + (f"   <- ops.proj_x_block({N}, {S}^3)" if K == ops.proj_x_block(N, (S, S, S)) else ""))
