@@ -815,6 +815,33 @@ int svr_depth_planes(const float *map, int32_t H, int32_t W, int32_t flip, const
 int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W);
 int svr_write_obj_points(const char *path, const float *pts, int64_t n);
 
+/* ---------------------------------------------------------------------------------------
+ * Depth head of the UNet regressor (replaces trainer/trainer_unet.py:43-61: F.interpolate(size=S, bilinear) -> crop of
+ * rows r0:r1 -> sigmoid -> renormalise -> F.mse_loss, and their autograd).  raw: (B, 1, Hs, Ws) float32, contiguous.
+ *   S > 0 : y = F.interpolate(raw, size=S, mode='bilinear', align_corners=False)[:, :, r0:r1, :], (B, 1, r1-r0, S).  Per
+ *           axis, in float32, every operation rounded on its own:  scale = (float)in / (float)S;
+ *           src = max(scale * (dst + 0.5f) - 0.5f, 0);  i0 = (int)src;  i1 = i0 + (i0 < in-1);  l1 = src - i0;  l0 = 1 - l1;
+ *           y = l0y*(l0x*a00 + l1x*a01) + l1y*(l0x*a10 + l1x*a11).  Rows outside r0:r1 are never computed.
+ *   S == 0: y = raw (r0, r1 ignored), output (B, 1, Hs, Ws).
+ *   depth = min(sigmoid(y) * (float)(max_z - min_z) + (float)min_z, (float)max_z)      (the bound only takes back a last
+ *           rounding past max_z).
+ * svr_depth_head_fwd: writes depth.  target (may be NULL; depth's shape): loss[0] = mean((depth - target)^2), summed in
+ *   float64: one partial per block in `workspace` (svr_depth_head_workspace(B, Ho, Wo) bytes, Ho x Wo the output's plane;
+ *   it need not be zeroed), added in a fixed order.  gdst (may be NULL; needs target; depth's shape) receives
+ *   d loss / d y = 2/n * (depth - target) * (max_z - min_z) * s * (1 - s); with S == 0 that is d loss / d raw.
+ * svr_depth_head_bwd (S > 0): draw (B, 1, Hs, Ws) = the transposed interpolation of gdst, in gather form: every source
+ *   pixel sums, in a fixed order, the cropped destination pixels whose taps touch it (found with the forward's own index
+ *   function).  No atomics: the same bits on every run; a source pixel that no cropped destination pixel touches gets
+ *   an exact 0.  draw is overwritten (it need not be zeroed).
+ * At most three launches for a training step (forward, loss sum, backward); no synchronisation, no allocation.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_depth_head_workspace(int32_t B, int32_t Ho, int32_t Wo);
+int svr_depth_head_fwd(const float *raw, const float *target, float *depth, float *loss, float *gdst, int32_t B, int32_t Hs,
+                       int32_t Ws, int32_t S, int32_t r0, int32_t r1, double min_z, double max_z, void *workspace,
+                       void *stream);
+int svr_depth_head_bwd(const float *gdst, float *draw, int32_t B, int32_t Hs, int32_t Ws, int32_t S, int32_t r0, int32_t r1,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,9 @@ SIGNATURES = {
     "svr_depth_planes": (C.c_int, [P, I32, I32, I32, P, P, P, P]),
     "svr_write_png_gray8": (C.c_int, [C.c_char_p, P, I32, I32]),
     "svr_write_obj_points": (C.c_int, [C.c_char_p, P, I64]),
+    "svr_depth_head_workspace": (I64, [I32, I32, I32]),
+    "svr_depth_head_fwd": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, C.c_double, C.c_double, P, P]),
+    "svr_depth_head_bwd": (C.c_int, [P, P, I32, I32, I32, I32, I32, I32, P]),
 }
 
 _lib = None

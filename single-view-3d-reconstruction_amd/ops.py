@@ -1489,3 +1489,75 @@ def conv2d_bwd_weight(src0, src1, k, stride, act, dy, Cout, want_bias=True):
     check(_lib.lib().svr_conv2d_bwd_weight(C.byref(d), _p(dy), _amax_any(dy).data_ptr(), Cout, _p(dw), _p(db), _p(ws), _stream()),
           "conv2d_bwd_weight")
     return dw, db
+
+
+# ------------------------------------------------------------------------------------------
+# depth head of the UNet regressor (depth_head.hip)
+# ------------------------------------------------------------------------------------------
+def _depth_head_shape(raw, size, rows):
+    if raw.dim() != 4 or raw.shape[1] != 1:
+        raise ValueError(f"depth_head: raw is (B, 1, Hs, Ws), got {tuple(raw.shape)}")
+    B, _, Hs, Ws = raw.shape
+    S = int(size or 0)
+    r0, r1 = (int(rows[0]), int(rows[1])) if S else (0, 0)
+    return B, Hs, Ws, S, r0, r1, ((B, 1, r1 - r0, S) if S else (B, 1, Hs, Ws))
+
+
+def depth_head_fwd(raw, target, size, rows, min_z, max_z, want_grad):
+    """-> depth, loss (1,) or None, gdst (d loss / d y on the output's pixels) or None: one or two launches."""
+    _f32(raw, target)
+    B, Hs, Ws, S, r0, r1, shape = _depth_head_shape(raw, size, rows)
+    if target is not None and tuple(target.shape) != shape:
+        raise ValueError(f"depth_head: target {tuple(target.shape)} for a depth map {shape}")
+    l = _lib.lib()
+    depth = torch.empty(shape, device=raw.device, dtype=torch.float32)
+    loss = gdst = ws = None
+    if target is not None:
+        loss = torch.empty(1, device=raw.device, dtype=torch.float32)
+        ws = torch.empty(int(l.svr_depth_head_workspace(B, shape[2], shape[3])) // 8, device=raw.device, dtype=torch.float64)
+        gdst = torch.empty(shape, device=raw.device, dtype=torch.float32) if want_grad else None
+    check(l.svr_depth_head_fwd(_p(raw), _p(target), _p(depth), _p(loss), _p(gdst), B, Hs, Ws, S, r0, r1, float(min_z),
+                               float(max_z), _p(ws), _stream()), "depth_head_fwd")
+    return depth, loss, gdst
+
+
+def depth_head_bwd(gdst, raw_shape, size, rows):
+    """d loss / d raw from d loss / d y: the transposed interpolation (identity mode: gdst itself)."""
+    B, _, Hs, Ws = raw_shape
+    S = int(size or 0)
+    if not S:
+        return gdst
+    draw = torch.empty(tuple(raw_shape), device=gdst.device, dtype=torch.float32)
+    check(_lib.lib().svr_depth_head_bwd(_p(gdst), _p(draw), B, Hs, Ws, S, int(rows[0]), int(rows[1]), _stream()), "depth_head_bwd")
+    return draw
+
+
+class _DepthHeadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, raw, target, size, rows, min_z, max_z):
+        raw = raw.contiguous()
+        want = ctx.needs_input_grad[0]
+        depth, loss, gdst = depth_head_fwd(raw, target.contiguous(), size, rows, min_z, max_z, want)
+        if want:                     # d raw for unit upstream gradient, left by the forward
+            ctx.save_for_backward(depth_head_bwd(gdst, raw.shape, size, rows))
+        ctx.mark_non_differentiable(depth)
+        return depth, loss.squeeze(0)
+
+    @staticmethod
+    def backward(ctx, _gdepth, gloss):
+        (draw,) = ctx.saved_tensors
+        return draw * gloss, None, None, None, None, None
+
+
+def depth_head(raw, target=None, size=320, rows=(40, 280), min_z=0.1953997164964676, max_z=7.0):
+    """The UNet regressor's head (trainer/trainer_unet.py:43-61) in the kernels of depth_head.hip:
+
+        depth = sigmoid(F.interpolate(raw, size=size, mode='bilinear')[:, :, rows[0]:rows[1], :]) * (max_z - min_z) + min_z
+        loss  = F.mse_loss(depth, target)                                         (None without a target)
+
+    raw: (B, 1, Hs, Ws) float32 (a permuted view is copied); size=0 / None: no resize (UNetMini on un-resized input).
+    Returns (depth, loss).  The loss is differentiable in `raw`; `depth` is not (marked non-differentiable)."""
+    if target is None:
+        depth, _, _ = depth_head_fwd(raw.detach().contiguous(), None, size, rows, min_z, max_z, False)
+        return depth, None
+    return _DepthHeadFn.apply(raw, target, size, rows, min_z, max_z)

@@ -186,3 +186,15 @@ class SceneNetTrainer(nn.Module):
                 implicit_to_mesh(self.ifnet, vox.reshape(1, 1, *vox.shape[-3:]), dims, 0.5, out / f"{base}_predicted.obj",
                                  res_increase=inf_res)
                 visualize_depthmap(depthmap[i], out / f"{base}_depthmap", flip=True)
+
+
+def use_pretrained_unet(args, path=None):
+    """trainer_scene_net.py:204-212 (``--pretrain_unet``): a SceneNetTrainer(args) whose `unet.*` entries come from the
+    checkpoint at `path` (default ``args.pretrain_unet``; written by trainer_unet.train_unet or by the reference).  Only the
+    entries whose key contains 'unet' are taken; ``load_state_dict(strict=False)`` leaves everything else as constructed."""
+    from .checkpoint import load_checkpoint
+    model = SceneNetTrainer(args)
+    pretrained_dict = load_checkpoint(path if path is not None else args.pretrain_unet)["state_dict"]
+    pretrained_dict = {k: v for k, v in pretrained_dict.items() if "unet" in k}
+    model.load_state_dict(pretrained_dict, strict=False)
+    return model
