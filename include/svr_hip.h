@@ -733,6 +733,26 @@ int svr_df_to_grid(const float *payload, float *out /*(X,Y,Z) C order*/, int32_t
 int svr_cast_to_f32(const void *in, int32_t dtype, float *out, int64_t n, void *stream);
 int svr_subsample_rows(const void *rows, int32_t dtype, int64_t n_rows, int32_t cols, const int64_t *idx, int64_t n_idx,
                        float *out, int32_t *bad_flag, void *stream);
+/* svr_subsample_rows_batched: the row subsets of a whole collated batch in one launch.  `segments` (DEVICE, n_segments
+ *   entries) describes one (item, sigma, array) each: out[out_offset + i * cols + c] = (float)rows[idx[idx_offset + i] * cols + c]
+ *   for i < n_idx, c < cols; dtype is SVR_DT_F32 / F64 / BOOL / U8 as in svr_subsample_rows, a row outside [0, n_rows)
+ *   writes 0 and sets *bad_flag (may be NULL).  `elem_prefix` (DEVICE, n_segments + 1 int64): elem_prefix[0] = 0,
+ *   elem_prefix[s + 1] = elem_prefix[s] + n_idx[s] * cols[s]; `total` = elem_prefix[n_segments] (the HOST's copy: it sizes the
+ *   launch).  `idx` is the shared int64 index buffer, `out` the shared float32 output; the caller guarantees that every
+ *   segment's index and output range lies inside them and that output ranges do not overlap.  The struct is six 8-byte
+ *   words, so table, prefix and indices can travel in ONE int64 host buffer and one copy.  n_segments <= 0 or total <= 0:
+ *   no-op. */
+typedef struct svr_row_segment {
+  const void *rows;
+  int64_t n_rows;
+  int64_t idx_offset;
+  int64_t n_idx;
+  int64_t out_offset;
+  int32_t dtype;
+  int32_t cols;
+} svr_row_segment;
+int svr_subsample_rows_batched(const svr_row_segment *segments, const int64_t *elem_prefix, int32_t n_segments, int64_t total,
+                               const int64_t *idx, float *out, int32_t *bad_flag, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Raw views (data_processing/distance_to_depth.py, process_sample.py:17-21, dataset/scene_net_data.py:77-84).

@@ -166,6 +166,7 @@ SIGNATURES = {
     "svr_df_to_grid": (C.c_int, [P, P, I32, I32, I32, P]),
     "svr_cast_to_f32": (C.c_int, [P, I32, P, I64, P]),
     "svr_subsample_rows": (C.c_int, [P, I32, I64, I32, P, I64, P, P, P]),
+    "svr_subsample_rows_batched": (C.c_int, [P, P, I32, I64, P, P, P, P]),
     "svr_exr_info": (C.c_int, [C.c_char_p, P, P, P, P, P, I64, P, I32, P, P]),
     "svr_exr_read_channel": (C.c_int, [C.c_char_p, C.c_char_p, P, I64]),
     "svr_exr_write": (C.c_int, [C.c_char_p, P, I32, I32, C.c_char_p, I32]),

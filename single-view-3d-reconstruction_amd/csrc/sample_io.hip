@@ -264,6 +264,41 @@ __global__ __launch_bounds__(256) void subsample_rows_kernel(const T *__restrict
   out[i] = as_f32(rows[r * cols + i % cols]);
 }
 
+// Batched row subset: every (item, sigma, array) of a collated batch is one svr_row_segment; the segments' output elements
+// are numbered back to back (elem_prefix), one thread per element, 256 per block.  A block finds the segment of its FIRST
+// element with one block-uniform bisection of elem_prefix (scalar loads, the same for all 256 lanes); a lane then only walks
+// forward over the segments that begin inside its block.  Stores are coalesced within a segment (consecutive lanes,
+// consecutive floats); the row reads are scattered by the indices.
+__global__ __launch_bounds__(256) void subsample_rows_batched_kernel(const svr_row_segment *__restrict__ seg,
+                                                                     const int64_t *__restrict__ elem_prefix, int n_seg, int64_t total,
+                                                                     const int64_t *__restrict__ idx, float *__restrict__ out,
+                                                                     int *__restrict__ bad) {
+  const int64_t first = (int64_t)blockIdx.x * 256, i = first + threadIdx.x;
+  if (i >= total) return;
+  int lo = 0, hi = n_seg - 1;  // the last segment with elem_prefix[s] <= first (elem_prefix[0] = 0)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (elem_prefix[mid] <= first) lo = mid; else hi = mid - 1;
+  }
+  int s = lo;
+  while (i >= elem_prefix[s + 1]) ++s;  // i < total = elem_prefix[n_seg]: stops at n_seg - 1 at the latest
+  const svr_row_segment sg = seg[s];
+  const int64_t e = i - elem_prefix[s];
+  const int64_t r = idx[sg.idx_offset + e / sg.cols];
+  float *dst = out + sg.out_offset + e;
+  if (r < 0 || r >= sg.n_rows) {
+    if (bad) atomicExch(bad, 1);
+    *dst = 0.f;
+    return;
+  }
+  const int64_t at = r * sg.cols + e % sg.cols;
+  switch (sg.dtype) {
+    case SVR_DT_F64: *dst = as_f32(((const double *)sg.rows)[at]); break;
+    case SVR_DT_F32: *dst = ((const float *)sg.rows)[at]; break;
+    default: *dst = as_f32(((const uint8_t *)sg.rows)[at]); break;  // SVR_DT_BOOL / SVR_DT_U8 (the launcher's contract)
+  }
+}
+
 }  // namespace
 
 extern "C" int svr_df_dims(const char *path, int64_t *dims) {
@@ -384,4 +419,14 @@ extern "C" int svr_subsample_rows(const void *rows, int32_t dtype, int64_t n_row
     default: SVR_CHECK(false, SVR_E_UNSUPPORTED, "subsample_rows: dtype %d", dtype);
   }
   return launch_status("subsample_rows");
+}
+
+extern "C" int svr_subsample_rows_batched(const svr_row_segment *segments, const int64_t *elem_prefix, int32_t n_segments,
+                                          int64_t total, const int64_t *idx, float *out, int32_t *bad_flag, void *stream) {
+  if (n_segments <= 0 || total <= 0) return SVR_OK;
+  SVR_CHECK(segments && elem_prefix && idx && out, SVR_E_BADARG, "subsample_rows_batched: null pointer");
+  SVR_CHECK(cdiv(total, 256) < (int64_t)1 << 31, SVR_E_BADARG, "subsample_rows_batched: %ld elements exceed one launch", (long)total);
+  hipLaunchKernelGGL(subsample_rows_batched_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, segments,
+                     elem_prefix, n_segments, total, idx, out, bad_flag);
+  return launch_status("subsample_rows_batched");
 }

@@ -129,3 +129,62 @@ def subsample_rows(rows, idx):
                                         C.c_void_p(idx.data_ptr()), idx.numel(), C.c_void_p(out.data_ptr()),
                                         C.c_void_p(bad.data_ptr()), _stream()), "subsample_rows")
     return out, bad
+
+
+ROW_SEGMENT_WORDS = 6      # sizeof(svr_row_segment) / 8: rows, n_rows, idx_offset, n_idx, out_offset, (dtype | cols << 32)
+
+
+def pack_row_segments(segments, n_index, n_out, pin=True):
+    """The host side of svr_subsample_rows_batched: ONE int64 buffer ``[elem_prefix (S + 1) | svr_row_segment table (6 S) |
+    indices (n_index)]`` (pinned by default), so that prefix, table and indices cross in a single copy.
+
+    `segments`: S tuples ``(rows, idx_offset, n_idx, out_offset)``; `rows` a contiguous device tensor (n_rows, cols) or
+    (n_rows,) of float32 / float64 / bool / uint8, the offsets in elements of the shared index buffer (`n_index` entries)
+    and of the shared float32 output (`n_out` entries).  Every range is checked here, on the host: the kernel trusts the
+    table.  Returns ``(buffer, indices, total)``: `indices` is the numpy view of the buffer's index part, for the caller to
+    fill; `total` the number of output elements."""
+    S = len(segments)
+    buf = torch.empty((S + 1) + ROW_SEGMENT_WORDS * S + n_index, dtype=torch.int64, pin_memory=pin)
+    a = buf.numpy()
+    table = a[S + 1:S + 1 + ROW_SEGMENT_WORDS * S].reshape(S, ROW_SEGMENT_WORDS)
+    total, taken = 0, []
+    a[0] = 0
+    for s, (rows, idx_offset, n_idx, out_offset) in enumerate(segments):
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.is_contiguous() and rows.dim() in (1, 2)):
+            raise ValueError("subsample_rows_batched: rows must be a contiguous (n_rows, cols) or (n_rows,) device tensor")
+        if rows.dtype not in (torch.float32, torch.float64, torch.bool, torch.uint8):
+            raise ValueError(f"subsample_rows_batched: dtype {rows.dtype}")
+        cols = 1 if rows.dim() == 1 else int(rows.shape[1])
+        n_rows, n_idx, idx_offset, out_offset = int(rows.shape[0]), int(n_idx), int(idx_offset), int(out_offset)
+        if n_idx < 0 or (n_idx > 0 and (cols <= 0 or n_rows <= 0)):
+            raise ValueError("subsample_rows_batched: empty source")
+        if idx_offset < 0 or idx_offset + n_idx > n_index or out_offset < 0 or out_offset + n_idx * cols > n_out:
+            raise ValueError(f"subsample_rows_batched: segment {s} reaches outside the index buffer or the output")
+        if n_idx:
+            taken.append((out_offset, out_offset + n_idx * cols))
+        table[s] = (rows.data_ptr(), n_rows, idx_offset, n_idx, out_offset, _CODE[rows.dtype] | (max(cols, 1) << 32))
+        total += n_idx * cols
+        a[s + 1] = total
+    taken.sort()
+    if any(taken[i][1] > taken[i + 1][0] for i in range(len(taken) - 1)):
+        raise ValueError("subsample_rows_batched: output ranges overlap")
+    return buf, a[S + 1 + ROW_SEGMENT_WORDS * S:], total
+
+
+def subsample_rows_batched(packed, n_segments, total, out, bad=None):
+    """One launch for every segment of `packed` (the DEVICE copy of pack_row_segments' buffer, which also fixed `total`):
+    out[out_offset + i * cols + c] = float32(rows[idx[idx_offset + i], c]).  `out`: the contiguous float32 device tensor the
+    table was checked against; `bad` (optional int32 (1,) device tensor) is set to 1 by a row outside [0, n_rows), which
+    writes 0.  No segments or no indices: nothing is launched."""
+    if n_segments <= 0 or total <= 0:
+        return out
+    if not (packed.is_cuda and packed.dtype == torch.int64 and packed.is_contiguous() and out.is_cuda
+            and out.dtype == torch.float32 and out.is_contiguous()):
+        raise RuntimeError("subsample_rows_batched needs a device int64 table and a contiguous float32 device output")
+    base = packed.data_ptr()
+    table = base + 8 * (n_segments + 1)
+    check(_lib.lib().svr_subsample_rows_batched(C.c_void_p(table), C.c_void_p(base), n_segments, total,
+                                                C.c_void_p(table + 8 * ROW_SEGMENT_WORDS * n_segments),
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(bad.data_ptr()) if bad is not None else None,
+                                                _stream()), "subsample_rows_batched")
+    return out

@@ -157,3 +157,55 @@ class DeviceSampleLoader:
         for k in ("grid", "points", "input", "occupancies", "target"):
             out[k] = torch.stack([s[k] for s in samples])
         return out
+
+
+class BatchedSampleLoader(DeviceSampleLoader):
+    """DeviceSampleLoader for a loop that must not stall: ``batch(indices)`` returns the same dictionary from the same numpy
+    draws (item by item, '0.10' then '0.01'), but the draws go into one pinned int64 buffer next to the segment table, cross
+    in one asynchronous copy, and one svr_subsample_rows_batched launch writes `points`, `grid` (B, 2n, 3) and `occupancies`
+    (B, 2n) in place.  ``get`` uploads each draw from pageable memory: that copy blocks the host until the stream has
+    drained, once per item and sigma, which cost the fit loop 4.7 ms on a 15.2 ms step."""
+
+    ARRAYS = ("points", "grid_coords", "occupancies")
+
+    def _resident(self, idx):
+        """The decoded sample, handed over to the caller's stream (the first half of ``get``)."""
+        item = self.ds.data[idx]
+        s = self.cache.get(item) if self.cache is not None else None
+        if s is None:
+            s = self._decode(self.ds.sample_folder(idx))
+            if self.cache is not None:
+                self.cache[item] = s
+        cur = torch.cuda.current_stream()
+        cur.wait_event(s["_ready"])
+        for t in s.values():
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(cur)
+        if s.get("_staging") is not None and s["_ready"].query():
+            s["_staging"] = None
+        return item, s
+
+    def batch(self, indices, generator=None):
+        if generator is not None:                       # device-side draws: the per-item path
+            return super().batch(indices, generator)
+        B, n = len(indices), int(self.ds.num_points)
+        samples = [self._resident(int(i)) for i in indices]
+        out = torch.empty(B * 2 * n * 7, device=self.device, dtype=torch.float32)
+        base = {"points": 0, "grid_coords": B * 2 * n * 3, "occupancies": B * 2 * n * 6}
+        segments = []
+        for b, (_, s) in enumerate(samples):
+            for k, sigma in enumerate(SIGMAS):
+                at = (b * 2 + k) * n
+                for key in self.ARRAYS:
+                    segments.append((s[(sigma, key)], at, n, base[key] + at * (1 if key == "occupancies" else 3)))
+        packed, draws, total = sample_io.pack_row_segments(segments, B * 2 * n, out.numel())
+        for b, (_, s) in enumerate(samples):
+            for k, sigma in enumerate(SIGMAS):
+                at = (b * 2 + k) * n
+                draws[at:at + n] = np.random.randint(0, s[(sigma, "points")].shape[0], n)
+        sample_io.subsample_rows_batched(packed.to(self.device, non_blocking=True), len(segments), total, out)
+        return {"name": [item for item, _ in samples], "grid": out[base["grid_coords"]:base["occupancies"]].view(B, 2 * n, 3),
+                "points": out[:base["grid_coords"]].view(B, 2 * n, 3),
+                "input": torch.stack([s["input"].unsqueeze(0) for _, s in samples]),
+                "occupancies": out[base["occupancies"]:].view(B, 2 * n),
+                "target": torch.stack([s["target"].unsqueeze(0) for _, s in samples])}

@@ -16,7 +16,10 @@ dict: 'name', 'mesh' (path of raw/.../mesh.obj), 'rgb', 'points', 'occupancies',
       written (PIL's bilinear filter is what Resize applies to a PIL image, antialiasing included, but no test proves it).
 
 The reference reads data/splits and data/intrinsics.txt relative to the working directory; `splits_root` and
-`intrinsics_path` say where they are."""
+`intrinsics_path` say where they are.
+
+``DeviceSceneLoader(dataset)`` serves the same items as collated device batches without the per-item host work: see the
+class."""
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -102,3 +105,113 @@ class scene_net_data(torch.utils.data.Dataset):
             "occupancies": sample_occupancies.to(self.device),
             "depthmap_target": depthmap_target.to(self.device),
         }
+
+
+class DeviceSceneLoader:
+    """GPU-resident views for SceneNetTrainer: the scene counterpart of implicit_dataset.DeviceSampleLoader, around a
+    ``scene_net_data`` dataset (precision 32 only).
+
+    A view is decoded on first touch -- PNG + transform, the EXR's channel R, both occupancy files' `points` / `occupancies`
+    in their stored dtype -- into pinned staging and copied on a side stream; with ``cache=True`` the transformed `rgb`, the
+    `depthmap_target` and the four occupancy arrays stay on the device (about 6 MB per view at 110 k points), so a later visit
+    reads no file.  ``batch(indices)`` draws like a DataLoader over the dataset would -- item by item, '0.10' then '0.01',
+    one ``np.random.randint(0, n_rows, num_points)`` each -- straight into one pinned int64 buffer that also carries the
+    segment table, and issues one H2D copy, one svr_subsample_rows_batched launch that writes `points` (B, 2n, 3) and
+    `occupancies` (B, 2n) in place, and one stack each for `rgb` and `depthmap_target`.  The result is the dictionary
+    ``default_collate`` makes of the dataset's items, bit for bit under the same numpy random state.
+
+    ``bad_rows()`` reads (synchronising) whether any launch saw a row outside its source: with indices drawn here it cannot."""
+
+    ARRAYS = ("points", "occupancies")
+
+    def __init__(self, dataset, device=None, cache=True):
+        if dataset.dtype != torch.float32:
+            raise ValueError("DeviceSceneLoader supports precision == 32 only")
+        self.ds = dataset
+        self.device = torch.device(device) if device is not None else dataset.device
+        self.cache = {} if cache else None
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.bad = torch.zeros(1, device=self.device, dtype=torch.int32)
+
+    def __len__(self):
+        return len(self.ds)
+
+    def _folders(self, item):
+        ds = self.ds
+        return ds.dataset_path / "raw" / ds.splitsdir / item, ds.dataset_path / "processed" / ds.splitsdir / item
+
+    def _decode(self, item):
+        raw, processed = self._folders(item)
+        s, keep = {"mesh": str(raw / "mesh.obj")}, []
+        with Image.open(raw / "rgb.png") as image:
+            rgb = rgb_transform(image, self.ds.W, self.ds.resize_input)
+        with torch.cuda.stream(self.copy_stream):
+            stage = torch.empty(rgb.shape, dtype=torch.float32, pin_memory=True).copy_(rgb)
+            s["rgb"] = stage.to(self.device, non_blocking=True)
+            keep.append(stage)
+            info = sample_io.exr_info(raw / "distance.exr")
+            stage = torch.empty(info["height"] * info["width"], dtype=torch.float32, pin_memory=True)
+            sample_io.exr_read(raw / "distance.exr", "R", out=stage.numpy())
+            distance = stage.to(self.device, non_blocking=True).view(info["height"], info["width"])
+            s["depthmap_target"] = self.ds.to_depth(distance)
+            keep.append(stage)
+            for sigma in SIGMAS:
+                f = processed / f"occupancy_{sigma}.npz"
+                for key in self.ARRAYS:
+                    dtype, shape, fortran = sample_io.npz_member_info(f, key)
+                    if fortran:                             # the kernel indexes the flat payload as C order
+                        raise ValueError(f"{f}[{key}]: fortran_order arrays are not supported by DeviceSceneLoader")
+                    stage = torch.empty(int(np.prod(shape)), dtype=torch.from_numpy(np.empty(0, dtype)).dtype, pin_memory=True)
+                    sample_io.npz_load(f, key, out=stage.numpy())
+                    s[(sigma, key)] = stage.to(self.device, non_blocking=True).view(shape)
+                    keep.append(stage)
+                if s[(sigma, "points")].shape[0] != s[(sigma, "occupancies")].shape[0]:
+                    raise ValueError(f"{f}: points and occupancies differ in length")
+            done = torch.cuda.Event()
+            done.record(self.copy_stream)
+        s["_ready"], s["_staging"] = done, keep              # the pinned buffers live until the copies have finished
+        return s
+
+    def _sample(self, idx):
+        item = self.ds.data[idx]
+        s = self.cache.get(item) if self.cache is not None else None
+        if s is None:
+            s = self._decode(item)
+            if self.cache is not None:
+                self.cache[item] = s
+        cur = torch.cuda.current_stream()
+        cur.wait_event(s["_ready"])
+        # allocated under copy_stream, read by the caller's stream: see DeviceSampleLoader.get
+        for t in s.values():
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(cur)
+        if s.get("_staging") is not None and s["_ready"].query():
+            s["_staging"] = None
+        return item, s
+
+    def batch(self, indices):
+        indices = [int(i) for i in indices]
+        B, n = len(indices), int(self.ds.num_points)
+        samples = [self._sample(i) for i in indices]
+        # one float32 block behind both outputs: points (B, 2n, 3) then occupancies (B, 2n)
+        out = torch.empty(B * 2 * n * 4, device=self.device, dtype=torch.float32)
+        occ_base = B * 2 * n * 3
+        segments = []
+        for b, (_, s) in enumerate(samples):
+            for k, sigma in enumerate(SIGMAS):
+                at = (b * 2 + k) * n
+                segments.append((s[(sigma, "points")], at, n, at * 3))
+                segments.append((s[(sigma, "occupancies")], at, n, occ_base + at))
+        packed, draws, total = sample_io.pack_row_segments(segments, B * 2 * n, out.numel())
+        for b, (_, s) in enumerate(samples):                 # the dataset's draws, in the dataset's order
+            for k, sigma in enumerate(SIGMAS):
+                at = (b * 2 + k) * n
+                draws[at:at + n] = np.random.randint(0, s[(sigma, "points")].shape[0], n)
+        sample_io.subsample_rows_batched(packed.to(self.device, non_blocking=True), len(segments), total, out, self.bad)
+        return {"name": [item for item, _ in samples], "mesh": [s["mesh"] for _, s in samples],
+                "rgb": torch.stack([s["rgb"] for _, s in samples]),
+                "points": out[:occ_base].view(B, 2 * n, 3), "occupancies": out[occ_base:].view(B, 2 * n),
+                "depthmap_target": torch.stack([s["depthmap_target"] for _, s in samples])}
+
+    def bad_rows(self):
+        return bool(self.bad.item())

@@ -9,6 +9,11 @@ PyTorch-Lightning (a third-party loop, out of scope): ``ImplicitRefinementTraine
 
 so a Lightning ``Trainer`` (or the data-parallel loop in ..dp) can drive it unchanged.  ``validation_step(batch,
 batch_idx, output_dir)`` writes the predicted and target meshes as .obj (:49-56).
+
+``train_dataloader`` / ``val_dataloader``: torch DataLoaders with the reference's shuffle / drop_last over the samples of a
+``BatchedSampleLoader`` (a ``DeviceSampleLoader``: device tensors, so main-process loaders: num_workers=0, nothing to pin).  ``train_implicit_refinement
+(args, steps=None, output_root='runs')`` stands in for ``Trainer.fit`` (:59-66) on the loop of trainer/fit.py: every
+``save_epoch``-th epoch's checkpoint is kept; ``python -m svr_amd.trainer.trainer_ifnet`` runs it on util/arguments.py's flags.
 """
 from pathlib import Path
 from types import SimpleNamespace
@@ -18,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..dataset.implicit_dataset import BatchedSampleLoader, ImplicitDataset
 from ..model.ifnet import IFNet, implicit_to_mesh
 from ..util.visualize import visualize_sdf
 
@@ -48,9 +54,31 @@ class ImplicitRefinementTrainer(nn.Module):
         self.hparams = kwargs
         self.ifnet = IFNet(net_res=net_res or getattr(kwargs, "net_res", 128))
 
+    def dataset(self, split):
+        h = self.hparams
+        return ImplicitDataset(split, h.datasetdir, h.num_points, h.splitsdir, splits_root=getattr(h, "splits_root", "data/splits"))
+
+    def device_loader(self, split):
+        return BatchedSampleLoader(self.dataset(split))
+
     def configure_optimizers(self):
         opt_g = torch.optim.Adam(self.ifnet.parameters(), lr=self.hparams.lr)
         return [opt_g], []
+
+    def train_dataloader(self):
+        from .fit import DeviceItems
+        return torch.utils.data.DataLoader(DeviceItems(self.device_loader("train")), batch_size=self.hparams.batch_size,
+                                           shuffle=True, num_workers=0, drop_last=True)
+
+    def val_dataloader(self):
+        from .fit import DeviceItems
+        return torch.utils.data.DataLoader(DeviceItems(self.device_loader("val")), batch_size=self.hparams.batch_size,
+                                           shuffle=False, num_workers=0, drop_last=False)
+
+    def test_dataloader(self):
+        from .fit import DeviceItems
+        return torch.utils.data.DataLoader(DeviceItems(self.device_loader("test")), batch_size=self.hparams.batch_size,
+                                           shuffle=False, num_workers=0, drop_last=False)
 
     def forward(self, batch):
         return self.ifnet(batch["input"], batch["points"])
@@ -77,3 +105,27 @@ class ImplicitRefinementTrainer(nn.Module):
             target = batch["target"][i]
             visualize_sdf(target.reshape(target.shape[-3:]).to(x.device), out / f"{name}_gt.obj", level=1)
         return {"loss": 0}
+
+
+def train_implicit_refinement(args, steps=None, output_root="runs"):
+    """Fit loop (trainer_ifnet.py:59-66).  Reads from `args`, beside the trainer's hyper-parameters and the dataset's
+    (datasetdir, splitsdir, num_points, optional splits_root): seed (< 0: none), experiment, batch_size, sanity_steps,
+    max_epoch, val_check_interval, val_check_percent, save_epoch, resume, optional log_every (50).  `steps` caps the number
+    of optimizer steps.  Validation output goes to <output_root>/<experiment>/vis/<global_step // 1000>, checkpoints to
+    <output_root>/<experiment>/epoch=<n>.ckpt and last.ckpt.  Returns {'model', 'checkpoint' (the last one
+    written), 'best_val_loss' (None: nothing is monitored), 'global_step', 'history', 'optimizer', 'driver',
+    'last_checkpoint'}."""
+    from . import fit as F
+    F.init_distributed(getattr(args, "gpu", None))
+    F.seed_everything(getattr(args, "seed", -1))
+    model = ImplicitRefinementTrainer(args).cuda()
+    loop = F.FitLoop(model, args, model.device_loader("train"), model.device_loader("val"),
+                     F.EveryEpoch(getattr(args, "save_epoch", 1)), vis_div=1000, interval_cap=1.0, output_root=output_root)
+    if getattr(args, "resume", None) is not None:
+        loop.resume(args.resume)
+    return loop.fit(steps)
+
+
+if __name__ == "__main__":
+    from ..util import arguments
+    train_implicit_refinement(arguments.parse_arguments())

@@ -16,7 +16,14 @@ SURVEY §8 f3) -- the reference copies it to the host and runs trimesh + Cython 
 predicted depth map (.png + .exr), its voxelisation (.obj of boxes) and the predicted mesh (.obj) -- into an `output_dir`
 the caller names (the reference's runs/<experiment>/vis/<global_step // 100>: there is no Lightning here).  Grid, lattice
 and depth map stay on the device; meshes and image planes are what crosses to the host.
+
+``train_dataloader`` / ``val_dataloader`` / ``test_dataloader`` (:57-67): main-process DataLoaders over ``scene_net_data``
+(its items are device tensors).  ``train_scene_net(args, steps=None, output_root='runs')`` stands in for the reference's
+``Trainer(...).fit`` / ``.test`` (:215-242) on the loop of trainer/fit.py with ``DeviceSceneLoader`` batches: the best two
+checkpoints by mean val_ce_loss plus last.ckpt, ``resume``, ``pretrain_unet`` and the ``test`` mode.
+``python -m svr_amd.trainer.trainer_scene_net`` runs it on util/arguments.py's flags.
 """
+import argparse
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -26,6 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..dataset.scene_net_data import DeviceSceneLoader, scene_net_data
 from ..model.ifnet import IFNet, implicit_to_mesh
 from ..model.projection import project
 from ..model.unet import UNetMini, Unet
@@ -86,6 +94,26 @@ class SceneNetTrainer(nn.Module):
         groups += [{"params": self.project.parameters(), "lr": 10 * h.lr}, {"params": self.ifnet.parameters()}]
         return [torch.optim.Adam(groups, lr=h.lr)], []
 
+    def dataset(self, split):
+        h = self.hparams
+        return scene_net_data(split, h.datasetdir, h.num_points, h.splitsdir, h, splits_root=getattr(h, "splits_root", "data/splits"),
+                              intrinsics_path=getattr(h, "intrinsics_path", None))
+
+    def device_loader(self, split):
+        return DeviceSceneLoader(self.dataset(split))
+
+    def train_dataloader(self):
+        return torch.utils.data.DataLoader(self.dataset("train"), batch_size=self.hparams.batch_size, shuffle=True, num_workers=0,
+                                           drop_last=True)
+
+    def val_dataloader(self):
+        return torch.utils.data.DataLoader(self.dataset("val"), batch_size=self.hparams.batch_size, shuffle=False, num_workers=0,
+                                           drop_last=False)
+
+    def test_dataloader(self):
+        return torch.utils.data.DataLoader(self.dataset("test"), batch_size=self.hparams.batch_size, shuffle=False, num_workers=0,
+                                           drop_last=False)
+
     def forward(self, batch):
         h = self.hparams
         if self.unet is not None:
@@ -93,7 +121,9 @@ class SceneNetTrainer(nn.Module):
             if h.resize_input:
                 logits = F.interpolate(raw, size=320, mode="bilinear")[:, :, 40:280, :].squeeze(1)
             else:
-                logits = raw
+                # UNetMini's (B, 1, 240, 320): one map per item, like the resized branch.  (The reference keeps the channel
+                # axis here, :77, and its mse_loss then broadcasts (B, 1, H, W) against the (B, H, W) target to B x B pairs.)
+                logits = raw.squeeze(1)
             depth = torch.sigmoid(logits) * (h.max_z - h.min_z) + h.min_z
         else:
             depth = batch["depthmap_target"]
@@ -198,3 +228,59 @@ def use_pretrained_unet(args, path=None):
     pretrained_dict = {k: v for k, v in pretrained_dict.items() if "unet" in k}
     model.load_state_dict(pretrained_dict, strict=False)
     return model
+
+
+def run_scene_net_test(args, output_root="runs"):
+    """The reference's ``--test`` (:233-240): the trainer is built from the hyper-parameters of the checkpoint ``args.test``,
+    with inf_res, scale_factor and skip_unet taken from `args`; ``test_step`` runs over the test split in eval mode and
+    writes every view's intermediates to <output_root>/<args.experiment>/vis/<checkpoint's global_step // 100>.  Nothing is
+    trained."""
+    from . import fit as F
+    from .checkpoint import load_checkpoint
+    ck = load_checkpoint(args.test)
+    hparams = argparse.Namespace(**ck["hyper_parameters"])
+    hparams.inf_res, hparams.scale_factor, hparams.skip_unet = args.inf_res, args.scale_factor, args.skip_unet
+    model = SceneNetTrainer(hparams)
+    state = {k: v for k, v in ck["state_dict"].items() if model.unet is not None or not k.startswith("unet.")}
+    model.load_state_dict(state)
+    model = model.cuda().eval()
+    global_step = int(ck.get("global_step", 0))
+    out = Path(output_root) / getattr(args, "experiment", hparams.experiment) / "vis" / f"{global_step // 100:05d}"
+    loader = model.device_loader("test")
+    for i, indices in enumerate(F.epoch_batches(len(loader), int(hparams.batch_size), shuffle=False, drop_last=False)):
+        model.test_step(loader.batch(indices), i, out)
+    return {"model": model, "checkpoint": str(args.test), "best_val_loss": None, "global_step": global_step, "history": {},
+            "output_dir": str(out)}
+
+
+def train_scene_net(args, steps=None, output_root="runs"):
+    """Fit loop (trainer_scene_net.py:215-242).  Reads from `args`, beside the trainer's hyper-parameters and the dataset's
+    (datasetdir, splitsdir, num_points, W, resize_input, precision, optional splits_root / intrinsics_path): seed (< 0:
+    none), experiment, batch_size, sanity_steps, max_epoch, val_check_interval (capped at half an epoch, :228),
+    val_check_percent, save_epoch, resume, pretrain_unet, test, optional log_every (50).  `steps` caps the number of
+    optimizer steps.  Validation output (``visualize``) goes to <output_root>/<experiment>/vis/<global_step // 100>;
+    <output_root>/<experiment>/ holds the best two by mean val_ce_loss (epoch=<n>-step=<s>.ckpt) and last.ckpt.  ``args.test`` set: ``run_scene_net_test`` instead.
+    Returns {'model', 'checkpoint' (the best one), 'best_val_loss' (its mean val_ce_loss), 'global_step', 'history',
+    'optimizer', 'driver', 'last_checkpoint'}."""
+    from . import fit as F
+    F.init_distributed(getattr(args, "gpu", None))
+    F.seed_everything(getattr(args, "seed", -1))
+    if int(getattr(args, "precision", 32)) != 32:
+        raise ValueError("train_scene_net supports precision == 32 only")
+    if getattr(args, "test", None) is not None:
+        return run_scene_net_test(args, output_root)
+    if getattr(args, "resume", None) is None and getattr(args, "pretrain_unet", None) is not None:
+        model = use_pretrained_unet(args)
+    else:
+        model = SceneNetTrainer(args)
+    model = model.cuda()
+    loop = F.FitLoop(model, args, model.device_loader("train"), model.device_loader("val"),
+                     F.TopK(2, "val_ce_loss", getattr(args, "save_epoch", 1)), vis_div=100, interval_cap=0.5, output_root=output_root)
+    if getattr(args, "resume", None) is not None:
+        loop.resume(args.resume)
+    return loop.fit(steps)
+
+
+if __name__ == "__main__":
+    from ..util import arguments
+    train_scene_net(arguments.parse_arguments())
