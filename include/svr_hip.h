@@ -662,6 +662,54 @@ int svr_mc_case_table(int8_t *out);
 int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf);
 
 /* ---------------------------------------------------------------------------------------
+ * Block-sparse evaluation of the occupancy lattice in front of svr_mc_* (not a reference op: a coarse-to-fine
+ * extractor in the manner of MISE; driven by util/sparse_grid.py, restated in numpy by tests/sparse_lattice_oracle.py).
+ * The network is queried only in blocks the surface passes through; the field handed to svr_mc_* stays a dense
+ * (X, Y, Z) float32 array.  Errors, ownership and streams as for svr_mc_*.
+ *   - lattice (X, Y, Z), every extent >= 2, fewer than 2^31 points; block edge s >= 2 cells (else SVR_E_BADSHAPE).
+ *     Per axis with n points: nb = ceil((n-1)/s) blocks; coarse indices c[i] = min(i*s, n-1), i = 0..nb; lattice
+ *     index i is owned by block min(i / s, nb-1) (the last block also owns index n-1).  Blocks, coarse points and the
+ *     owned points of a block are all numbered in C order (z fastest);
+ *   - inside(v) := (double)v < level (NaN: outside), the rule of svr_mc_*;
+ *   - coordinates: tx, ty, tz are device tables of X, Y, Z float32 (torch.linspace(-0.5, 0.5, n), the tensors
+ *     make_3d_grid expands); the kernels copy table entries and never compute a coordinate;
+ *   - 1. C = f at the (nbx+1)(nby+1)(nbz+1) coarse points; 2. fill: every lattice point takes C at the minimum
+ *     corner of its owner block; 3. round 1 selects the blocks whose 8 corner flags inside(C) are not all equal;
+ *     4. a round lists the selected blocks in C order of block index, lists their owned points block by block,
+ *     has f evaluated on that list, stores the values into the field and sets the blocks' state to the round
+ *     number (>= 1; 0 = never evaluated); 5. leak check, over the blocks of this round only: every lattice edge
+ *     (p, q) along an axis with p in such a block, q in a block with state 0 and inside(field[p]) !=
+ *     inside(field[q]) selects q's block for the next round and counts once; 6. rounds repeat until one selects
+ *     nothing; after `max_rounds` rounds the caller selects every block with state 0 (all = 1), which ends leak-free.
+ *     At exit no edge with differing sides has an unevaluated endpoint.
+ *   svr_sl_workspace_bytes: device workspace (negative = SVR_E_BADSHAPE).
+ *   svr_sl_coarse_points:  pts (coarse points, 3) float32.
+ *   svr_sl_fill_seed:      coarse (coarse points) float32 -> field (X, Y, Z), state (nbx, nby, nbz) uint8 = 0, and the
+ *                          selection of round 1 in the workspace.
+ *   svr_sl_select:         consumes the pending selection (all = 1: every block with state 0 instead): one exclusive
+ *                          scan of the per-block owned-point counts; the block list and each block's first row go to
+ *                          the workspace; totals[0] = listed blocks, totals[1] = listed points (device int64[3]).
+ *                          The caller reads totals back, once per round, to size the point list.
+ *   svr_sl_block_points:   pts (totals[1], 3) float32, the owned points of the n_blocks listed blocks.
+ *   svr_sl_scatter:        vals (totals[1]) float32 -> field; state of the listed blocks = round (1..255).
+ *   svr_sl_leak_check:     step 5 for the listed blocks: marks the next selection, totals[2] = counted edges (read
+ *                          back with the next round's totals).
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_sl_workspace_bytes(int32_t X, int32_t Y, int32_t Z, int32_t s);
+int svr_sl_coarse_points(const float *tx, const float *ty, const float *tz, int32_t X, int32_t Y, int32_t Z, int32_t s,
+                         float *pts, void *stream);
+int svr_sl_fill_seed(const float *coarse, int32_t X, int32_t Y, int32_t Z, int32_t s, double level, float *field,
+                     uint8_t *state, void *ws, int64_t ws_bytes, void *stream);
+int svr_sl_select(int32_t X, int32_t Y, int32_t Z, int32_t s, int32_t all, const uint8_t *state, void *ws, int64_t *totals,
+                  void *stream);
+int svr_sl_block_points(const float *tx, const float *ty, const float *tz, int32_t X, int32_t Y, int32_t Z, int32_t s,
+                        const void *ws, int64_t n_blocks, float *pts, void *stream);
+int svr_sl_scatter(const float *vals, int32_t X, int32_t Y, int32_t Z, int32_t s, const void *ws, int64_t n_blocks,
+                   int32_t round, float *field, uint8_t *state, void *stream);
+int svr_sl_leak_check(const float *field, int32_t X, int32_t Y, int32_t Z, int32_t s, double level, const uint8_t *state,
+                      void *ws, int64_t n_blocks, int64_t *totals, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mesh evaluation: IoU, Chamfer-L2, normal consistency (replaces what util/evaluate.py:9-119 takes from trimesh --
  * mesh.sample, face_normals -- and from pykdtree's KDTree.query, and the sampler of data_processing/
  * mesh_occupancies.py:9-22).  Every rule below is restated in numpy by tests/eval_oracle.py; one rounding per

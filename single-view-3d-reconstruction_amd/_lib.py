@@ -159,6 +159,13 @@ SIGNATURES = {
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),
     "svr_mc_case_table": (C.c_int, [P]),
     "svr_write_obj": (C.c_int, [C.c_char_p, P, I64, P, I64]),
+    "svr_sl_workspace_bytes": (I64, [I32, I32, I32, I32]),
+    "svr_sl_coarse_points": (C.c_int, [P, P, P, I32, I32, I32, I32, P, P]),
+    "svr_sl_fill_seed": (C.c_int, [P, I32, I32, I32, I32, C.c_double, P, P, P, I64, P]),
+    "svr_sl_select": (C.c_int, [I32, I32, I32, I32, I32, P, P, P, P]),
+    "svr_sl_block_points": (C.c_int, [P, P, P, I32, I32, I32, I32, P, I64, P, P]),
+    "svr_sl_scatter": (C.c_int, [P, I32, I32, I32, I32, P, I64, I32, P, P, P]),
+    "svr_sl_leak_check": (C.c_int, [P, I32, I32, I32, I32, C.c_double, P, P, I64, P, P]),
     "svr_df_dims": (C.c_int, [C.c_char_p, P]),
     "svr_df_read": (C.c_int, [C.c_char_p, P, I64]),
     "svr_npz_member_info": (C.c_int, [C.c_char_p, C.c_char_p, P, P, P, P]),

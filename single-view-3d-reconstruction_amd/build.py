@@ -30,6 +30,7 @@ SOURCES = {
     "bf16_path.hip": ["-ffp-contract=off"],
     "mesh_occupancy.hip": ["-ffp-contract=off"],
     "marching_cubes.hip": ["-ffp-contract=off"],
+    "sparse_lattice.hip": ["-ffp-contract=off"],
     "voxel_mesh.hip": ["-ffp-contract=off"],
     "mesh_eval.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],

@@ -1063,13 +1063,62 @@ def evaluate_network_on_grid(network, x, resolution, res_increase=1, points_batc
     return evaluate_network_on_grid_device(network, x, resolution, res_increase, points_batch_size, storage).cpu().numpy()
 
 
-def implicit_to_mesh(network, x, resolution, threshold_p, output_path, res_increase=1):
+def _inference_block(value):
+    """0 (dense) or a block edge >= 2; anything else is refused."""
+    try:
+        b = int(value)
+    except (TypeError, ValueError):
+        b = -1
+    if b != 0 and b < 2:
+        raise ValueError(f"inference block must be 0 (dense) or an integer >= 2, got {value!r}")
+    return b
+
+
+# Block edge of the sparse lattice evaluation behind implicit_to_mesh (util/sparse_grid.py, DESIGN.md section 15); 0 = the
+# dense evaluation.  Both trainers' validation / test steps reach the sparse path through this attribute.
+INFERENCE_BLOCK = _inference_block(os.environ.get("SVR_INF_BLOCK", "0"))
+
+
+def evaluate_network_on_grid_sparse(network, x, resolution, threshold_p, res_increase=1, block=8, points_batch_size=2048 * 16,
+                                    max_rounds=32, storage="f32", profile=False):
+    """1 - occupancy probability on the lattice of evaluate_network_on_grid_device, with the network queried only in the
+    blocks of `block` cells that the level set `threshold_p` passes through (util.sparse_grid.sparse_lattice_field).
+    Returns its SparseLatticeField: `.field` (X, Y, Z) is what implicit_to_mesh hands to marching_cubes; an evaluated
+    point holds 1 - sigmoid(query) from the same ops as the dense path, every other point a value on its block's side of
+    the level.  encode / prepare_query are used as the dense path uses them."""
+    from ..util.sparse_grid import sparse_lattice_field
+    if not x.is_cuda:
+        raise RuntimeError("IF-Net HIP path needs GPU tensors (no CPU fallback)")
+    r = [int(s) * res_increase for s in resolution]
+    with torch.no_grad():
+        levels = network.encode(x, storage) if storage != "f32" else network.encode(x)
+        prep = network.prepare_query(levels, points_batch_size)
+
+        def fn(pts):
+            pi = pts.unsqueeze(0)
+            z = network.query(levels, pi, prepared=prep) if prep is not None else network.query(levels, pi)
+            return 1 - torch.sigmoid(z).squeeze(0)
+
+        return sparse_lattice_field(fn, r, threshold_p, block, points_batch_size, max_rounds, device=x.device, profile=profile)
+
+
+def implicit_to_mesh(network, x, resolution, threshold_p, output_path, res_increase=1, block=None):
     """The reference's implicit_to_mesh (model/ifnet.py:232-234): the mesh of the occupancy lattice at probability
     `threshold_p`, written to `output_path` as .obj.  Computes what
     ``visualize_sdf(1 - evaluate_network_on_grid(...), output_path, level=threshold_p)`` computes (1 - p in float32, as
     the reference's numpy does), but the lattice never leaves the device: only the mesh crosses to the host.
-    Returns (vertices (V,3) float32, faces (F,3) int32) as device tensors."""
+    Returns (vertices (V,3) float32, faces (F,3) int32) as device tensors.
+
+    block: None takes INFERENCE_BLOCK; 0 is the dense evaluation above; an integer >= 2 queries the network only in the
+    blocks of that many cells the surface passes through (evaluate_network_on_grid_sparse: the same mesh unless a surface
+    component hides between the coarse points)."""
     from ..util.visualize import export_obj, marching_cubes
+    block = INFERENCE_BLOCK if block is None else _inference_block(block)
+    if block:
+        sdf = evaluate_network_on_grid_sparse(network, x, resolution, threshold_p, res_increase, block).field
+        vertices, faces = marching_cubes(sdf, threshold_p)
+        export_obj(vertices, faces, output_path)
+        return vertices, faces
     value_grid = evaluate_network_on_grid_device(network, x, resolution, res_increase)
     vertices, faces = marching_cubes(1 - value_grid, threshold_p)
     export_obj(vertices, faces, output_path)
