@@ -6,6 +6,13 @@ non-GPU tensor.  (The CPU oracle lives under oracle/ and is test infrastructure 
 import ctypes as C
 import os
 
+import numpy as np
+# torch is imported here, ahead of any CDLL in lib(): it must load ITS HIP runtime first.  libsvr_hip.so only names
+# libamdhip64 by SONAME, and if the system copy gets mapped before torch's, the process ends up with two runtimes (kernels
+# launched by one on memory owned by the other: "no ROCm-capable device" from rocPRIM).  stream() / ptr() / to_device() below
+# need the module on every call, so it is not imported lazily.
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsvr_hip.so")
 
@@ -210,10 +217,6 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the HIP path.")
-        # torch must load ITS HIP runtime first: libsvr_hip.so only names libamdhip64 by SONAME, and if the
-        # system copy gets mapped before torch's, the process ends up with two runtimes (kernels launched by one
-        # on memory owned by the other: "no ROCm-capable device" from rocPRIM).
-        import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(l, name)          # AttributeError here = header/library mismatch
@@ -231,3 +234,35 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib().svr_last_error()
         raise RuntimeError(f"libsvr_hip {what} failed (rc={rc}): {msg.decode(errors='replace') if msg else ''}")
+
+
+# ---- what every binding module passes to the library ------------------------------------------------------------------
+def stream():
+    """The current HIP stream as the library's `void *stream`."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t):
+    """Device pointer of a contiguous GPU tensor; None -> NULL."""
+    if t is None:
+        return C.c_void_p(0)
+    if not t.is_cuda:
+        raise RuntimeError("svr_amd ops need GPU tensors (the HIP path has no CPU fallback)")
+    if not t.is_contiguous():
+        raise RuntimeError("svr_amd ops need contiguous tensors")
+    return C.c_void_p(t.data_ptr())
+
+
+def to_device(a, what, dtype=None, device=None):
+    """The input convention of the data-processing / evaluation entry points: a numpy array (or anything np.asarray
+    takes) is uploaded and the caller hands numpy back, a device tensor stays on the device, a CPU tensor is refused.
+    -> (contiguous device tensor [cast to `dtype`], came_from_numpy)."""
+    as_numpy = not torch.is_tensor(a)
+    if as_numpy:        # (a float target type is cast on the host: numpy takes every source type, and rounds like the device)
+        a = np.ascontiguousarray(np.asarray(a), dtype={torch.float32: np.float32, torch.float64: np.float64}.get(dtype))
+        a = torch.from_numpy(a).to(device if device is not None else "cuda")
+    elif not a.is_cuda:
+        raise RuntimeError(f"{what} HIP path needs GPU tensors (no CPU fallback)")
+    if dtype is not None and a.dtype != dtype:
+        a = a.to(dtype)
+    return a.contiguous(), as_numpy

@@ -18,11 +18,10 @@ reader) -> depth with the intrinsic's focal length -> grid space.  ``depth_grid`
 one kernel from the map to the marked uint8 grid and the count of pixels that fall outside it."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from .. import _lib, ops
-from .._lib import check
+from .._lib import check, ptr, stream, to_device
 from ..model.projection import _camera_to_grid, project
 from . import sample_io
 
@@ -33,18 +32,11 @@ def get_intrinsic(intrinsic_path=None):
     return project.get_intrinsic(intrinsic_path)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _device_map(a, what):
-    if not torch.is_tensor(a):
-        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.float32)).cuda()
-    elif not a.is_cuda:
-        raise RuntimeError(f"{what} HIP path needs GPU tensors (no CPU fallback)")
+    a, _ = to_device(a, what, torch.float32)
     if a.dim() not in (2, 3):
         raise ValueError(f"{what}: expected (H, W) or (B, H, W), got {tuple(a.shape)}")
-    return a.to(torch.float32).contiguous()
+    return a
 
 
 def _grid_consts(intrinsic, down_scale_factor, dims=(0, 0, 0)):
@@ -63,8 +55,8 @@ class FromDistanceToDepth:
         d = _device_map(distance_image, "FromDistanceToDepth")
         out = torch.empty_like(d)
         B = 1 if d.dim() == 2 else d.shape[0]
-        check(_lib.lib().svr_distance_to_depth(C.c_void_p(d.data_ptr()), C.c_void_p(out.data_ptr()), B, d.shape[-2], d.shape[-1],
-                                               self.focal_length, _stream()), "distance_to_depth")
+        check(_lib.lib().svr_distance_to_depth(ptr(d), ptr(out), B, d.shape[-2], d.shape[-1], self.focal_length, stream()),
+              "distance_to_depth")
         return out
 
 
@@ -95,7 +87,6 @@ def depth_grid(image, dims, intrinsic_path=None, down_scale_factor=1, is_distanc
     grid = torch.zeros(D0, D1, D2, device=m.device, dtype=torch.uint8)
     count = torch.zeros(1, device=m.device, dtype=torch.int32)
     coords = torch.empty(m.numel(), 3, device=m.device, dtype=torch.float32) if return_coords else None
-    check(_lib.lib().svr_depth_grid_mark(C.c_void_p(m.data_ptr()), int(is_distance), float(K[0, 0]), m.shape[0], m.shape[1], consts,
-                                         C.c_void_p(grid.data_ptr()), D0, D1, D2, C.c_void_p(count.data_ptr()),
-                                         C.c_void_p(coords.data_ptr()) if return_coords else None, _stream()), "depth_grid_mark")
+    check(_lib.lib().svr_depth_grid_mark(ptr(m), int(is_distance), float(K[0, 0]), m.shape[0], m.shape[1], consts, ptr(grid),
+                                         D0, D1, D2, ptr(count), ptr(coords), stream()), "depth_grid_mark")
     return (grid, count, coords) if return_coords else (grid, count)

@@ -13,11 +13,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from ..._lib import check
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ..._lib import check, ptr, stream, to_device
 
 
 class MeshIntersector:
@@ -48,25 +44,20 @@ class MeshIntersector:
         self.n_entries = int(entries)
 
     def query(self, points):
-        as_numpy = not torch.is_tensor(points)
-        if as_numpy:
-            arr = np.ascontiguousarray(points)
-            if arr.dtype not in (np.float32, np.float64):
-                arr = arr.astype(np.float64)
-            points = torch.from_numpy(arr).to(self._tri.device)
-        if not points.is_cuda:
-            raise RuntimeError("check_mesh_contains HIP path needs GPU tensors (no CPU fallback)")
+        if not torch.is_tensor(points):
+            points = np.asarray(points)
+            if points.dtype not in (np.float32, np.float64):
+                points = points.astype(np.float64)                  # on the host: numpy takes every source type
+        points, as_numpy = to_device(points, "check_mesh_contains", device=self._tri.device)
         if points.dtype not in (torch.float32, torch.float64):
             points = points.double()
         pts = points.reshape(-1, 3).contiguous()
         n = pts.shape[0]
         contains = torch.empty(n, device=pts.device, dtype=torch.uint8)
         holes = torch.empty(n, device=pts.device, dtype=torch.uint8)
-        check(_lib.lib().svr_mesh_contains(C.c_void_p(pts.data_ptr()), int(pts.dtype == torch.float64), n,
-                                           C.c_void_p(self._tri.data_ptr()), C.c_void_p(self._cell_start.data_ptr()),
-                                           C.c_void_p(self._tri_ids.data_ptr()), self.resolution,
-                                           self._st.ctypes.data_as(C.c_void_p), C.c_void_p(contains.data_ptr()),
-                                           C.c_void_p(holes.data_ptr()), _stream()), "mesh_contains")
+        check(_lib.lib().svr_mesh_contains(ptr(pts), int(pts.dtype == torch.float64), n, ptr(self._tri), ptr(self._cell_start),
+                                           ptr(self._tri_ids), self.resolution, self._st.ctypes.data_as(C.c_void_p),
+                                           ptr(contains), ptr(holes), stream()), "mesh_contains")
         contains, holes = contains.bool(), holes.bool()
         if as_numpy:
             return contains.cpu().numpy(), holes.cpu().numpy()

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._lib import check
+from .._lib import check, ptr, stream
 
 _NP = {0: np.float32, 1: np.float64, 2: np.bool_, 3: np.uint8, 4: np.int32, 5: np.int64}
 _CODE = {torch.float32: 0, torch.float64: 1, torch.bool: 2, torch.uint8: 3, torch.int32: 4, torch.int64: 5}
@@ -98,23 +98,18 @@ def exr_write(path, channels):
 
 
 # ---- device side -------------------------------------------------------------------------------------------------
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def df_to_grid(payload, dims):
     """device float32 payload (x fastest) -> (X, Y, Z) C-order float32 tensor."""
     X, Y, Z = dims
     out = torch.empty(X, Y, Z, device=payload.device, dtype=torch.float32)
-    check(_lib.lib().svr_df_to_grid(C.c_void_p(payload.data_ptr()), C.c_void_p(out.data_ptr()), X, Y, Z, _stream()), "df_to_grid")
+    check(_lib.lib().svr_df_to_grid(ptr(payload), ptr(out), X, Y, Z, stream()), "df_to_grid")
     return out
 
 
 def cast_to_f32(t):
     t = t.contiguous()
     out = torch.empty(t.shape, device=t.device, dtype=torch.float32)
-    check(_lib.lib().svr_cast_to_f32(C.c_void_p(t.data_ptr()), _CODE[t.dtype], C.c_void_p(out.data_ptr()), t.numel(), _stream()),
-          "cast_to_f32")
+    check(_lib.lib().svr_cast_to_f32(ptr(t), _CODE[t.dtype], ptr(out), t.numel(), stream()), "cast_to_f32")
     return out
 
 
@@ -125,9 +120,8 @@ def subsample_rows(rows, idx):
     idx = idx.to(device=rows.device, dtype=torch.int64).contiguous()
     out = torch.empty((idx.numel(),) if rows.dim() == 1 else (idx.numel(), cols), device=rows.device, dtype=torch.float32)
     bad = torch.zeros(1, device=rows.device, dtype=torch.int32)
-    check(_lib.lib().svr_subsample_rows(C.c_void_p(rows.data_ptr()), _CODE[rows.dtype], rows.shape[0], cols,
-                                        C.c_void_p(idx.data_ptr()), idx.numel(), C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(bad.data_ptr()), _stream()), "subsample_rows")
+    check(_lib.lib().svr_subsample_rows(ptr(rows), _CODE[rows.dtype], rows.shape[0], cols, ptr(idx), idx.numel(), ptr(out),
+                                        ptr(bad), stream()), "subsample_rows")
     return out, bad
 
 
@@ -185,6 +179,5 @@ def subsample_rows_batched(packed, n_segments, total, out, bad=None):
     table = base + 8 * (n_segments + 1)
     check(_lib.lib().svr_subsample_rows_batched(C.c_void_p(table), C.c_void_p(base), n_segments, total,
                                                 C.c_void_p(table + 8 * ROW_SEGMENT_WORDS * n_segments),
-                                                C.c_void_p(out.data_ptr()), C.c_void_p(bad.data_ptr()) if bad is not None else None,
-                                                _stream()), "subsample_rows_batched")
+                                                ptr(out), ptr(bad), stream()), "subsample_rows_batched")
     return out

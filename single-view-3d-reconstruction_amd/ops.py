@@ -8,20 +8,16 @@ import torch
 from . import _lib
 from .arena import alloc as _alloc
 from ._lib import EPI_BIAS, EPI_BIAS_RELU, EPI_MASK, EPI_NONE, GatherDesc, check  # noqa: F401
+from ._lib import ptr as _p, stream as _stream
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
+def _rp(t):
+    """Address of a row-strided 2-D GPU operand whose leading dimension is passed beside it (None -> NULL); _p wants contiguity."""
     if t is None:
-        return C.c_void_p(0)
+        return None
     if not t.is_cuda:
         raise RuntimeError("svr_amd ops need GPU tensors (the HIP path has no CPU fallback)")
-    if not t.is_contiguous():
-        raise RuntimeError("svr_amd ops need contiguous tensors")
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def _f32(*ts):
@@ -267,14 +263,14 @@ def gather_project_bwd(points, dh, dims, items, displacement, align_corners=Fals
         partials = _proj_partials.get(key)
         if partials is None or partials.numel() < plan.slots * 8 * 256:
             partials = _proj_partials[key] = torch.empty(plan.slots * 8 * 256, device=points.device, dtype=torch.float32)
-        check(_lib.lib().svr_gather_project_bwd2(_p(points), C.c_void_p(dh.data_ptr()), dh.stride(0), B, N, dims[0], dims[1],
+        check(_lib.lib().svr_gather_project_bwd2(_p(points), _rp(dh), dh.stride(0), B, N, dims[0], dims[1],
                                                  dims[2], int(align_corners), displacement, _p(plan.items), _p(plan.sidx),
                                                  _p(plan.first_slot), _p(partials), _p(dP), _stream()), "gather_project_bwd2")
         return dP
     # out: a ZEROED (B, D*H*W, 7, 256) buffer of the caller (the training step zero-fills it on the side stream during the forward)
     dP = out if out is not None else torch.zeros(B, dims[0] * dims[1] * dims[2], 7, 256, device=points.device, dtype=torch.float32)
     assert tuple(dP.shape) == (B, dims[0] * dims[1] * dims[2], 7, 256) and dP.is_contiguous()
-    check(_lib.lib().svr_gather_project_bwd(_p(points), C.c_void_p(dh.data_ptr()), dh.stride(0), B, N, dims[0], dims[1], dims[2],
+    check(_lib.lib().svr_gather_project_bwd(_p(points), _rp(dh), dh.stride(0), B, N, dims[0], dims[1], dims[2],
                                             int(align_corners), displacement, _p(items), _p(dP), _stream()), "gather_project_bwd")
     return dP
 
@@ -377,7 +373,7 @@ def gather_fc0_prepare(vols, layout, displacement, align_corners, w, B, N, keep_
     ws = _alloc(arena, "fc0_ws", (ws_bytes,), torch.uint8, w.device)
     prep = Fc0Prepared(vols, layout, displacement, align_corners, n_out, ws, keep_levels, keep_layout, B, N)
     # (the kept matrix itself is only needed by run; prepare validates its geometry against a dummy aligned address)
-    check(l.svr_gather_fc0_prepare(C.byref(d), C.c_void_p(w.data_ptr()), w.stride(0), n_out, C.c_void_p(256) if prep.mask else None,
+    check(l.svr_gather_fc0_prepare(C.byref(d), _rp(w), w.stride(0), n_out, C.c_void_p(256) if prep.mask else None,
                                    prep.stride if prep.mask else 0, prep.kc, prep.mask, _p(ws), _stream()), "gather_fc0_prepare")
     return prep
 
@@ -514,7 +510,7 @@ def gather_fc0_bf16_prepare(vols, layout, displacement, align_corners, w):
     if ws_bytes <= 0:
         raise RuntimeError("gather_fc0_bf16: unsupported level shapes (see svr_gather_fc0_supported)")
     ws = torch.empty(ws_bytes, device=w.device, dtype=torch.uint8)
-    check(l.svr_gather_fc0_bf16_prepare(C.byref(d), C.c_void_p(w.data_ptr()), w.stride(0), n_out, _p(ws), _stream()),
+    check(l.svr_gather_fc0_bf16_prepare(C.byref(d), _rp(w), w.stride(0), n_out, _p(ws), _stream()),
           "gather_fc0_bf16_prepare")
     return {"vols": vols, "layout": layout, "disp": displacement, "ac": align_corners, "n_out": n_out, "ws": ws}
 
@@ -540,7 +536,7 @@ def linear_fwd_bf16(x, w, bias, relu=True):
     assert w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
     out = torch.empty(M, N, device=x.device, dtype=torch.bfloat16)
     epi = EPI_NONE if bias is None else (EPI_BIAS_RELU if relu else EPI_BIAS)
-    check(_lib.lib().svr_linear_fwd_bf16(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(w.data_ptr()), w.stride(0), _p(bias),
+    check(_lib.lib().svr_linear_fwd_bf16(_rp(x), x.stride(0), _rp(w), w.stride(0), _p(bias),
                                          _p(out), out.stride(0), M, N, K, epi, _stream()), "linear_fwd_bf16")
     return out
 
@@ -715,8 +711,10 @@ def linear_fwd(x, w, bias, relu=True, out=None, mode=None):
 # f32 level like the reference's fp32 backward, the same three matrix instructions per block; gemm_f16x3.hip /
 # gemm_bf16x3.hip), "bf16x3" (3-term bf16 split, ~1.5e-5 relative per product: 4 % faster per step, the default of rounds
 # 1-3; SVR_BACKWARD=bf16x3) or "f32" (exact-f32 MFMA).  The forward never uses them.
-BACKWARD_GEMM = os.environ.get("SVR_BACKWARD", "f16x3s")
 BACKWARD_MODES = ("bf16x3", "f16x3s", "f32")
+BACKWARD_GEMM = os.environ.get("SVR_BACKWARD", "f16x3s")      # read once, here: BACKWARD_CONV / BACKWARD_CONV_WEIGHT start from it
+if BACKWARD_GEMM not in BACKWARD_MODES:      # (a typo used to mean exact f32 everywhere, under whatever label it carried)
+    raise ValueError(f"SVR_BACKWARD={BACKWARD_GEMM!r}: one of {BACKWARD_MODES}")
 
 
 class _AmaxSlots:
@@ -807,8 +805,7 @@ def linear_bwd_data(dy, w, mask=None, out=None, mode=None):
         amax_dx = amax_slot(dy.device)
         check(l.svr_linear_bwd_data_f16x3(C.c_void_p(dy.data_ptr()), dy.stride(0), wptr, w.stride(0),
                                           C.c_void_p(out.data_ptr()), out.stride(0), M, N, K, epi,
-                                          C.c_void_p(mask.data_ptr()) if mask is not None else C.c_void_p(0),
-                                          mask.stride(0) if mask is not None else 0, _p(amax_dy), _p(amax_dx), _p(ws), _stream()),
+                                          _rp(mask), mask.stride(0) if mask is not None else 0, _p(amax_dy), _p(amax_dx), _p(ws), _stream()),
               "linear_bwd_data_f16x3")
         out._svr_amax = amax_dx        # |max| of what was stored: the next layer's scale, no extra pass
         return out
@@ -822,14 +819,12 @@ def linear_bwd_data(dy, w, mask=None, out=None, mode=None):
             ws = torch.empty(l.svr_linear_bwd_data_bf16x3_workspace(N, K), device=dy.device, dtype=torch.uint8)
         check(l.svr_linear_bwd_data_bf16x3(C.c_void_p(dy.data_ptr()), dy.stride(0), wptr, w.stride(0),
                                            C.c_void_p(out.data_ptr()), out.stride(0), M, N, K, epi,
-                                           C.c_void_p(mask.data_ptr()) if mask is not None else C.c_void_p(0),
-                                           mask.stride(0) if mask is not None else 0, _p(ws), _stream()),
+                                           _rp(mask), mask.stride(0) if mask is not None else 0, _p(ws), _stream()),
               "linear_bwd_data_bf16x3")
         return out
     check(_lib.lib().svr_linear_bwd_data(C.c_void_p(dy.data_ptr()), dy.stride(0), C.c_void_p(w.data_ptr()), w.stride(0),
                                          C.c_void_p(out.data_ptr()), out.stride(0), M, N, K, epi,
-                                         C.c_void_p(mask.data_ptr()) if mask is not None else C.c_void_p(0),
-                                         mask.stride(0) if mask is not None else 0, _stream()), "linear_bwd_data")
+                                         _rp(mask), mask.stride(0) if mask is not None else 0, _stream()), "linear_bwd_data")
     return out
 
 
@@ -935,7 +930,7 @@ def conv3d_k3(x, wp, bias=None, relu=False, mask=None):
 
 
 # Arithmetic of the encoder's backward-data convolutions: "bf16x3" (conv3d_bf16.hip) or "f32".
-BACKWARD_CONV = os.environ.get("SVR_BACKWARD", "f16x3s")     # "bf16x3", "f16x3s" (scaled f16 split: f32 level) or "f32"
+BACKWARD_CONV = BACKWARD_GEMM     # "bf16x3", "f16x3s" (scaled f16 split: f32 level) or "f32"
 # ... and of its forward convolutions: "f16x3" (3-product f16 split, f32-level accuracy for |x| < 65504), "bf16x6"
 # (6-product bf16 split, any f32 range) or "f32" (exact-f32 MFMA)
 FORWARD_CONV = "f16x3"
@@ -1052,7 +1047,7 @@ def conv3d_k3_variant(op, B, dims, Ci, Co):
 
 # Arithmetic of the encoder's weight gradients: "bf16x3" (conv3d_bwdw_bf16.hip), "f16x3s" (its scaled f16 form: f32 level)
 # or "f32" (exact-f32 MFMA)
-BACKWARD_CONV_WEIGHT = os.environ.get("SVR_BACKWARD", "f16x3s")
+BACKWARD_CONV_WEIGHT = BACKWARD_GEMM
 
 
 def conv3d_k3_bwd_weight(x, dout, want_bias=True, mode=None, param_layout=False):
@@ -1333,7 +1328,9 @@ class Conv2dPlanes:
     """Split f16 planes of one nn.Conv2d weight (forward and backward-data products) + the word holding max|W|.  Layers with
     1..4 output channels keep the f32 weight itself (`small`: plain-FMA kernels, conv2d.hip)."""
 
-    def __init__(self, weight, stride, want_bwd=True):
+    def __init__(self, weight, stride, want_bwd=True, prepare=True):
+        """prepare=False (conv2d_prepare_many): classify the layer only; a layer that is not `small` then gets its buffer
+        and its planes from the batched launch."""
         _f32(weight)
         w = weight.detach().contiguous()
         self.Cout, self.C, self.k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
@@ -1341,12 +1338,12 @@ class Conv2dPlanes:
         self.small = bool(_lib.lib().svr_conv2d_small_supported(self.Cout, self.C, self.k))
         if self.small:
             self.w, self.has_bwd = w, True
-            return
-        nbytes = 256 + _lib.lib().svr_conv2d_planes_bytes(self.Cout, self.C, self.k)
-        self.buf = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
-        self._amax, self._planes = self.buf.data_ptr(), self.buf.data_ptr() + 256
-        check(_lib.lib().svr_conv2d_prepare(_p(w), self.Cout, self.C, self.k, stride, int(self.has_bwd), self.amax_ptr(),
-                                            self.planes_ptr(), _stream()), "conv2d_prepare")
+        elif prepare:
+            nbytes = 256 + _lib.lib().svr_conv2d_planes_bytes(self.Cout, self.C, self.k)
+            self.buf = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
+            self._amax, self._planes = self.buf.data_ptr(), self.buf.data_ptr() + 256
+            check(_lib.lib().svr_conv2d_prepare(_p(w), self.Cout, self.C, self.k, stride, int(self.has_bwd), self.amax_ptr(),
+                                                self.planes_ptr(), _stream()), "conv2d_prepare")
 
     def amax_ptr(self):
         return self._amax
@@ -1361,16 +1358,9 @@ def conv2d_prepare_many(items):
     l = _lib.lib()
     out, todo = [None] * len(items), []
     for i, (weight, stride, want_bwd) in enumerate(items):
-        _f32(weight)
-        w = weight.detach().contiguous()
-        pl = Conv2dPlanes.__new__(Conv2dPlanes)
-        pl.Cout, pl.C, pl.k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
-        pl.stride, pl.has_bwd = stride, bool(want_bwd)
-        pl.small = bool(l.svr_conv2d_small_supported(pl.Cout, pl.C, pl.k))
-        out[i] = pl
-        if pl.small:
-            pl.w, pl.has_bwd = w, True
-        else:
+        w = weight.detach().contiguous()               # (kept here: the batched launch below reads it)
+        pl = out[i] = Conv2dPlanes(w, stride, want_bwd, prepare=False)
+        if not pl.small:
             todo.append((pl, w))
     for g0 in range(0, len(todo), 16):
         grp = todo[g0:g0 + 16]

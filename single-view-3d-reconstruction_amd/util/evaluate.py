@@ -23,30 +23,10 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._lib import check
+from .._lib import check, ptr as _p, stream as _stream, to_device as _to_device
 
 KEYS = ("completeness", "accuracy", "normals completeness", "normals accuracy", "normals", "completeness2", "accuracy2",
         "chamfer_l2", "iou")
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _to_device(a, what, dtype=None, device=None):
-    """-> (contiguous CUDA tensor, came_from_numpy); CPU tensors are refused."""
-    as_numpy = not torch.is_tensor(a)
-    if as_numpy:
-        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(device if device is not None else "cuda")
-    elif not a.is_cuda:
-        raise RuntimeError(f"{what} HIP path needs GPU tensors (no CPU fallback)")
-    if dtype is not None and a.dtype != dtype:
-        a = a.to(dtype)
-    return a.contiguous(), as_numpy
 
 
 def _points(a, what):
@@ -108,7 +88,7 @@ def distance_p2p(pointcloud_pred, pointcloud_gt, normals_pred, normals_gt, retur
 def _sums(dist, dot, out):
     """out (3,) float64 on the device = sum d, sum d^2, sum dot (NaN without dot), in the library's fixed order."""
     ws = torch.empty(_lib.EVAL_SUMS_WORKSPACE_BYTES, device=dist.device, dtype=torch.uint8)
-    check(_lib.lib().svr_eval_sums(_p(dist), _p(dot) if dot is not None else C.c_void_p(0), int(dist.shape[0]), _p(out), _p(ws),
+    check(_lib.lib().svr_eval_sums(_p(dist), _p(dot), int(dist.shape[0]), _p(out), _p(ws),
                                    int(ws.numel()), _stream()), "eval_sums")
 
 

@@ -13,13 +13,12 @@ of every such extractor).  The result's `field` goes to `marching_cubes` like a 
 The point coordinates are rows of ``make_3d_grid((-0.5,)*3, (0.5,)*3, shape)``, bit for bit: the kernels copy entries
 of the same three linspace tables.  One host read per round (the totals that size the point list)."""
 import contextlib
-import ctypes as C
 from dataclasses import dataclass, field as _dc_field
 
 import torch
 
 from .. import _lib
-from .._lib import check
+from .._lib import check, ptr as _p, stream as _stream
 
 _MAX_ROUNDS = 254          # the block state is a uint8 and the fall-back round comes on top
 
@@ -37,14 +36,6 @@ class SparseLatticeField:
     @property
     def evaluated_fraction(self):
         return self.n_points / self.field.numel()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class _Clock:

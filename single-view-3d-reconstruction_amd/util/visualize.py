@@ -33,45 +33,42 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._lib import check
+from .._lib import check, ptr, stream, to_device
 
 _INT32_LIMIT = 2 ** 31
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def marching_cubes(field, level):
-    as_numpy = not torch.is_tensor(field)
-    if as_numpy:
-        field = torch.from_numpy(np.ascontiguousarray(np.asarray(field), dtype=np.float32)).cuda()
-    elif not field.is_cuda:
-        raise RuntimeError("marching_cubes HIP path needs GPU tensors (no CPU fallback)")
-    if field.dim() != 3:
-        raise ValueError(f"marching_cubes: field must be (X, Y, Z), got {tuple(field.shape)}")
-    f = field.to(torch.float32).contiguous()
-    X, Y, Z = (int(s) for s in f.shape)
+def _count_emit_mesh(field, level, what, arg, lib_name):
+    """The two-launch mesher shared by marching_cubes and voxel_mesh: workspace -> count -> the two totals (the only
+    host synchronisation: they size the outputs) -> emit.  `lib_name`: the three entry points are svr_<lib_name>_workspace_bytes
+    / _count / _emit; `what` / `arg`: the function's and its array argument's name in messages."""
     l = _lib.lib()
-    ws_bytes = int(l.svr_mc_workspace_bytes(X, Y, Z))
+    workspace_bytes, count, emit = (getattr(l, f"svr_{lib_name}_{part}") for part in ("workspace_bytes", "count", "emit"))
+    f, as_numpy = to_device(field, what, torch.float32)
+    if f.dim() != 3:
+        raise ValueError(f"{what}: {arg} must be (X, Y, Z), got {tuple(f.shape)}")
+    X, Y, Z = (int(s) for s in f.shape)
+    ws_bytes = int(workspace_bytes(X, Y, Z))
     if ws_bytes < 0:
-        check(ws_bytes, "mc_workspace_bytes")
+        check(ws_bytes, lib_name + "_workspace_bytes")
     dev = f.device
     ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
     totals = torch.empty(2, device=dev, dtype=torch.int64)
-    fp, wp = C.c_void_p(f.data_ptr()), C.c_void_p(ws.data_ptr())
-    check(l.svr_mc_count(fp, X, Y, Z, float(level), wp, ws_bytes, C.c_void_p(totals.data_ptr()), _stream()), "mc_count")
-    nv, nf = totals.tolist()                       # the only host synchronisation: sizes the outputs
+    check(count(ptr(f), X, Y, Z, float(level), ptr(ws), ws_bytes, ptr(totals), stream()), lib_name + "_count")
+    nv, nf = totals.tolist()
     if nv >= _INT32_LIMIT or nf >= _INT32_LIMIT:
-        raise RuntimeError(f"marching_cubes: {nv} vertices / {nf} faces do not fit int32 face indices")
+        raise RuntimeError(f"{what}: {nv} vertices / {nf} faces do not fit int32 face indices")
     verts = torch.empty((nv, 3), device=dev, dtype=torch.float32)
     faces = torch.empty((nf, 3), device=dev, dtype=torch.int32)
     if nv or nf:
-        check(l.svr_mc_emit(fp, X, Y, Z, float(level), wp, C.c_void_p(verts.data_ptr()), C.c_void_p(faces.data_ptr()),
-                            _stream()), "mc_emit")
+        check(emit(ptr(f), X, Y, Z, float(level), ptr(ws), ptr(verts), ptr(faces), stream()), lib_name + "_emit")
     if as_numpy:
         return verts.cpu().numpy(), faces.cpu().numpy()
     return verts, faces
+
+
+def marching_cubes(field, level):
+    return _count_emit_mesh(field, level, "marching_cubes", "field", "mc")
 
 
 def _host(a, dtype):
@@ -93,36 +90,7 @@ def visualize_sdf(sdf, output_path, level=0.75):
 
 
 def voxel_mesh(grid, threshold=0.5):
-    as_numpy = not torch.is_tensor(grid)
-    if as_numpy:
-        grid = torch.from_numpy(np.ascontiguousarray(np.asarray(grid), dtype=np.float32)).cuda()
-    elif not grid.is_cuda:
-        raise RuntimeError("voxel_mesh HIP path needs GPU tensors (no CPU fallback)")
-    if grid.dim() != 3:
-        raise ValueError(f"voxel_mesh: grid must be (X, Y, Z), got {tuple(grid.shape)}")
-    f = grid.to(torch.float32).contiguous()
-    X, Y, Z = (int(s) for s in f.shape)
-    l = _lib.lib()
-    ws_bytes = int(l.svr_voxel_mesh_workspace_bytes(X, Y, Z))
-    if ws_bytes < 0:
-        check(ws_bytes, "voxel_mesh_workspace_bytes")
-    dev = f.device
-    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-    totals = torch.empty(2, device=dev, dtype=torch.int64)
-    fp, wp = C.c_void_p(f.data_ptr()), C.c_void_p(ws.data_ptr())
-    check(l.svr_voxel_mesh_count(fp, X, Y, Z, float(threshold), wp, ws_bytes, C.c_void_p(totals.data_ptr()), _stream()),
-          "voxel_mesh_count")
-    nv, nf = totals.tolist()                       # the only host synchronisation: sizes the outputs
-    if nv >= _INT32_LIMIT or nf >= _INT32_LIMIT:
-        raise RuntimeError(f"voxel_mesh: {nv} vertices / {nf} faces do not fit int32 face indices")
-    verts = torch.empty((nv, 3), device=dev, dtype=torch.float32)
-    faces = torch.empty((nf, 3), device=dev, dtype=torch.int32)
-    if nv or nf:
-        check(l.svr_voxel_mesh_emit(fp, X, Y, Z, float(threshold), wp, C.c_void_p(verts.data_ptr()),
-                                    C.c_void_p(faces.data_ptr()), _stream()), "voxel_mesh_emit")
-    if as_numpy:
-        return verts.cpu().numpy(), faces.cpu().numpy()
-    return verts, faces
+    return _count_emit_mesh(grid, threshold, "voxel_mesh", "grid", "voxel_mesh")
 
 
 def to_point_list(s):
@@ -165,10 +133,8 @@ def visualize_depthmap(depthmap, output_path, flip=False):
     stats = torch.empty(4, device=d.device, dtype=torch.int32)
     plane_f = torch.empty((H, W), device=d.device, dtype=torch.float32)
     plane_u = torch.empty((H, W), device=d.device, dtype=torch.uint8)
-    dp, sp = C.c_void_p(d.data_ptr()), C.c_void_p(stats.data_ptr())
-    check(l.svr_depth_minmax(dp, H * W, sp, _stream()), "depth_minmax")
-    check(l.svr_depth_planes(dp, H, W, int(bool(flip)), sp, C.c_void_p(plane_f.data_ptr()), C.c_void_p(plane_u.data_ptr()),
-                             _stream()), "depth_planes")
+    check(l.svr_depth_minmax(ptr(d), H * W, ptr(stats), stream()), "depth_minmax")
+    check(l.svr_depth_planes(ptr(d), H, W, int(bool(flip)), ptr(stats), ptr(plane_f), ptr(plane_u), stream()), "depth_planes")
     st = stats.cpu().numpy().view(np.uint32)
     if st[2] != 0:
         raise ValueError("visualize_depthmap: the map holds NaN or inf")
