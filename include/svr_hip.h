@@ -66,7 +66,8 @@ typedef struct svr_level {
                            runs on the coarse levels); overrides `order`             */
   const svr_pull_plan *plan; /* backward only, optional (host pointer, read at call time): scatter this level
                            atomic-free in pull form.  gvol is then OVERWRITTEN (it need not be zeroed) and
-                           `order` is ignored.  C in {16, 32, 64}.                     */
+                           `order` is ignored.  C in {1, 16, 32, 64} (C = 1: the raw grid of level 0,
+                           one scalar per voxel).                                      */
 } svr_level;
 
 typedef struct svr_gather_desc {
@@ -337,6 +338,12 @@ int svr_fc_out_bwd(const float *H, int64_t ldh, const float *w, const float *dlo
  * (dlogits may be NULL).  workspace: B doubles.                                           */
 int svr_bce_logits_sum_mean(const float *logits, const float *targets, float *loss, float *dlogits,
                             int64_t B, int64_t N, float gscale, void *workspace, void *stream);
+/* The same loss and gradient with the sum in a fixed order (no atomics): every block of a sample leaves its float64
+ * partial in workspace[b][block], one thread adds a sample's partials in ascending block order and then the samples in
+ * ascending b.  workspace: svr_bce_ordered_workspace(B) bytes.                                                  */
+int64_t svr_bce_ordered_workspace(int64_t B);
+int svr_bce_logits_sum_mean_ordered(const float *logits, const float *targets, float *loss, float *dlogits,
+                                    int64_t B, int64_t N, float gscale, void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * 3x3x3 convolution, padding 1, channels-last (replaces nn.Conv3d(.,.,3,padding=1) + ReLU
@@ -540,6 +547,37 @@ int svr_blur_axis_fwd(const float *in, const float *taps, float *out, int32_t B,
 int svr_blur_axis_bwd(const float *in, const float *taps, const float *gout, float *gin,
                       double *gtaps, int32_t B, int32_t D0, int32_t D1, int32_t D2, int32_t axis,
                       int32_t K, void *stream);
+
+/* ---- ordered (bit-reproducible) forms of the two reductions above: DESIGN.md section 16 ----
+ *
+ * svr_voxelize_splat_fwd_ordered: the splat without float atomics, in a FIXED SUMMATION ORDER that is a function of
+ * the point array and the shape alone:
+ *   - a point's base voxel (i0, i1, i2), fractions (r0, r1, r2) and validity are those of svr_voxelize_splat_fwd
+ *     (same device function); its weight for corner (k, j, l) is (w0[k] * w1[j]) * w2[l] in float32 with
+ *     w[0] = 1 - r, w[1] = r, as there;
+ *   - voxel (z, y, x) of sample b holds eight partial sums P[k][j][l], k, j, l in {0, 1}: P[k][j][l] is the float32
+ *     sum, starting from +0 and taken SEQUENTIALLY IN ASCENDING POINT INDEX n, of the corner-(k, j, l) weights of the
+ *     valid points of sample b whose base voxel is (z - k, y - j, x - l);
+ *   - acc[b][z][y][x] = ((P000 + P001) + (P010 + P011)) + ((P100 + P101) + (P110 + P111)).
+ * Implementation: the points are keyed by (b, i0 + 1, i1 + 1, i2 + 1) in a (D0+1) x (D1+1) x (D2+1) lattice (invalid
+ * and NaN points: a sentinel key), sorted with the stable 32-bit radix sort, and a pull kernel in which a thread owns
+ * a strip of consecutive x voxels walks the CSR ranges of the contributing cells.  EVERY voxel of acc is written (it
+ * need not be zeroed).  vox (may be NULL, acc's shape) = clamp(8 * acc, 0, 1), svr_scale_clamp01_fwd's arithmetic, from
+ * the same kernel.  base / valid: as svr_voxelize_splat_fwd.  Needs B*(D0+1)*(D1+1)*(D2+1) < 2^31 - 1 and
+ * B*N < 2^31 (SVR_E_UNSUPPORTED otherwise; svr_voxelize_splat_ordered_workspace then returns SVR_E_UNSUPPORTED too).
+ * workspace: svr_voxelize_splat_ordered_workspace(B, N, D0, D1, D2) bytes.                                         */
+int64_t svr_voxelize_splat_ordered_workspace(int32_t B, int32_t N, int32_t D0, int32_t D1, int32_t D2);
+int svr_voxelize_splat_fwd_ordered(const float *pts, float *acc, float *vox, int32_t *base, uint8_t *valid, int32_t B,
+                                   int32_t N, int32_t D0, int32_t D1, int32_t D2, void *workspace, void *stream);
+/* svr_blur_axis_bwd with the tap gradient in a fixed order: the same grid and per-thread float32 grid-stride partials,
+ * the same float64 tree inside a block; the block sums go to workspace[block][K] (float64) and one small kernel adds
+ * them in a fixed order (per tap: lane i of 64 adds blocks i, i + 64, ... in ascending order, then a fixed tree over the
+ * lanes).  gtaps[K] (float64) is WRITTEN (no zero fill).  workspace:
+ * svr_blur_axis_bwd_ordered_workspace(B, D0, D1, D2, K) bytes (only read when gtaps is given).                      */
+int64_t svr_blur_axis_bwd_ordered_workspace(int32_t B, int32_t D0, int32_t D1, int32_t D2, int32_t K);
+int svr_blur_axis_bwd_ordered(const float *in, const float *taps, const float *gout, float *gin, double *gtaps,
+                              int32_t B, int32_t D0, int32_t D1, int32_t D2, int32_t axis, int32_t K, void *workspace,
+                              void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * 2-D convolution blocks of the UNet depth regressor (replaces nn.Conv2d(k4,s2,p1) / nn.Conv2d(k3,s1,p1),

@@ -100,6 +100,8 @@ SIGNATURES = {
     "svr_fc_out_bwd_workspace": (I64, [I64, I64]),
     "svr_fc_out_bwd": (C.c_int, [P, I64, P, P, P, P, I64, P, P, I64, I64, P, P, P]),
     "svr_bce_logits_sum_mean": (C.c_int, [P, P, P, P, I64, I64, F32, P, P]),
+    "svr_bce_ordered_workspace": (I64, [I64]),
+    "svr_bce_logits_sum_mean_ordered": (C.c_int, [P, P, P, P, I64, I64, F32, P, P]),
     "svr_conv3d_pack_weight": (C.c_int, [P, P, P, I32, I32, P]),
     "svr_conv3d_unpack_wgrad": (C.c_int, [P, P, I32, I32, P]),
     "svr_conv3d_k3": (C.c_int, [P, P, P, P, I32, I32, I32, I32, I32, I32, C.c_int, P, P]),
@@ -194,6 +196,10 @@ SIGNATURES = {
     "svr_scale_clamp01_bwd": (C.c_int, [P, P, P, I64, F32, P]),
     "svr_blur_axis_fwd": (C.c_int, [P, P, P, I32, I32, I32, I32, I32, I32, P]),
     "svr_blur_axis_bwd": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, P]),
+    "svr_voxelize_splat_ordered_workspace": (I64, [I32, I32, I32, I32, I32]),
+    "svr_voxelize_splat_fwd_ordered": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, P, P]),
+    "svr_blur_axis_bwd_ordered_workspace": (I64, [I32, I32, I32, I32, I32]),
+    "svr_blur_axis_bwd_ordered": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, P, P]),
     "svr_voxel_mesh_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_voxel_mesh_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_voxel_mesh_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),

@@ -1034,6 +1034,75 @@ __global__ __launch_bounds__(256) void gather_bwd_pull_kernel(float *__restrict_
     if (x0 + i < W) *reinterpret_cast<float4 *>(out + (int64_t)i * C) = acc[i];   // (streaming stores here: no change of the step)
 }
 
+// The same pull scatter for the raw grid of level 0 (C = 1: no float4 of channels to own): a thread owns XS consecutive x
+// voxels of one (b, z, y) row and walks the same four ranges of the same plan; one scalar gradient per item.  Every voxel
+// is written, in sorted (= fixed) order.
+template <int XS>
+__global__ __launch_bounds__(256) void gather_bwd_pull_c1_kernel(float *__restrict__ gvol, const uint32_t *__restrict__ keys,
+                                                                 const PullRec *__restrict__ recs,
+                                                                 const int32_t *__restrict__ cs,
+                                                                 const float *__restrict__ gfeat, int n_items,
+                                                                 int64_t strips, int D, int H, int W) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= strips) return;
+  const int nsx = (W + XS - 1) / XS;
+  const int x0 = (int)(t % nsx) * XS;
+  int64_t q = t / nsx;
+  const int y = (int)(q % H); q /= H;
+  const int z = (int)(q % D);
+  const int64_t b = q / D;
+  const int ncell = min(XS, W - x0) + 1;  // cells x0 .. x0 + ncell - 1 (cell coordinates end at W)
+  uint32_t kbase[4];
+  int lo[4], hi[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int dz = w >> 1, dy = w & 1;
+    kbase[w] = (uint32_t)(((b * (D + 1) + z + dz) * (H + 1) + y + dy) * (W + 1) + x0);
+    lo[w] = cs[kbase[w]];
+    hi[w] = cs[kbase[w] + ncell];
+  }
+  float acc[XS];
+#pragma unroll
+  for (int i = 0; i < XS; ++i) acc[i] = 0.f;
+  const int last = n_items > 0 ? n_items - 1 : 0;
+  while (lo[0] < hi[0] || lo[1] < hi[1] || lo[2] < hi[2] || lo[3] < hi[3]) {
+    uint32_t k[4];
+    PullRec r[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int i = min(lo[w], last);
+      k[w] = keys[i];
+      r[w] = recs[i];
+    }
+    float g[4];
+    bool v[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      v[w] = lo[w] < hi[w];
+      g[w] = gfeat[v[w] ? r[w].goff : 0];
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int dz = w >> 1, dy = w & 1;
+      if (v[w]) {
+        const int o = (int)(k[w] - kbase[w]);  // cell x0 + o: voxel x0 + o gets f, voxel x0 + o - 1 gets 1 - f
+        const float wyz = (dy ? 1.f - r[w].fy : r[w].fy) * (dz ? 1.f - r[w].fz : r[w].fz);
+        const float wa = r[w].fx * wyz, wb = (1.f - r[w].fx) * wyz;
+#pragma unroll
+        for (int i = 0; i < XS; ++i) {
+          const float wt = (o == i) ? wa : ((o == i + 1) ? wb : 0.f);
+          acc[i] += wt * g[w];
+        }
+        ++lo[w];
+      }
+    }
+  }
+  float *out = gvol + ((b * D + z) * H + y) * (int64_t)W + x0;
+#pragma unroll
+  for (int i = 0; i < XS; ++i)
+    if (x0 + i < W) out[i] = acc[i];
+}
+
 // x-strip length of the pull kernel per channel count (measured at config 3: 0.55 / 0.38 / 0.57 ms; strips of 4 / 2 / 2:
 // 0.57 / 0.41 / 0.66, one voxel per thread: 1.29 / 0.60 / 0.66)
 __host__ __device__ inline int pull_xs(int C) { return C == 16 ? 8 : 4; }
@@ -1182,7 +1251,8 @@ extern "C" int svr_gather_trilinear_bwd(const svr_gather_desc *d, const float *p
     if (!gv) continue;
     if (d->level[l].plan && !(d->flags & SVR_GATHER_DETERMINISTIC)) {  // atomic-free pull form: gvol is overwritten
       const svr_pull_plan *P = d->level[l].plan;
-      SVR_CHECK(L.C == 16 || L.C == 32 || L.C == 64, SVR_E_UNSUPPORTED, "gather_bwd: level %d: pull plan with C=%d", l, L.C);
+      SVR_CHECK(L.C == 1 || L.C == 16 || L.C == 32 || L.C == 64, SVR_E_UNSUPPORTED, "gather_bwd: level %d: pull plan with C=%d", l,
+                L.C);
       SVR_CHECK(P->keys && P->recs && P->heads && P->n_items == 7 * BN, SVR_E_BADARG, "gather_bwd: level %d: bad pull plan", l);
       SVR_CHECK(P->n_items < (1LL << 31) && BN * (int64_t)d->row_stride < (1LL << 31), SVR_E_UNSUPPORTED,
                 "gather_bwd: level %d: pull plan needs 32-bit item / gradient offsets", l);
@@ -1197,7 +1267,12 @@ extern "C" int svr_gather_trilinear_bwd(const svr_gather_desc *d, const float *p
   }
       // strips of 8 / 4 / 4 voxels (measured at config 3: 0.55 / 0.38 / 0.57 ms; strips of 4 / 2 / 2: 0.57 / 0.41 / 0.66,
       // one voxel per thread: 1.29 / 0.60 / 0.66)
-      if (L.C == 16) SVR_PULL(16, 8, 4, 4, 4)
+      if (L.C == 1) {  // level 0 (raw grid): strips of 4 scalars, see gather_bwd_pull_c1_kernel
+        const int64_t strips = (int64_t)d->B * L.D * L.H * svr::cdiv(L.W, 4);
+        SVR_CHECK(strips < (1LL << 31), SVR_E_UNSUPPORTED, "gather_bwd: level %d: %ld pull strips", l, (long)strips);
+        hipLaunchKernelGGL((gather_bwd_pull_c1_kernel<4>), dim3((unsigned)svr::cdiv(strips, 256)), dim3(256), 0, s, L.gvol, P->keys,
+                           recs, P->heads, gfeatures, n, strips, L.D, L.H, L.W);
+      } else if (L.C == 16) SVR_PULL(16, 8, 4, 4, 4)
       else if (L.C == 32) SVR_PULL(32, 4, 2, 4, 4)
       else SVR_PULL(64, 4, 2, 2, 4)
 #undef SVR_PULL

@@ -330,6 +330,43 @@ __global__ void bce_final_kernel(const double *__restrict__ persample, float *__
   }
 }
 
+// bce_kernel with the block sums stored (part[b][block], BCE_BLOCKS slots per sample) instead of added atomically
+constexpr int BCE_BLOCKS = 64;
+
+__global__ __launch_bounds__(256) void bce_parts_kernel(const float *__restrict__ z, const float *__restrict__ y,
+                                                        float *__restrict__ dz, double *__restrict__ part, int64_t N,
+                                                        float gscale_over_B) {
+  int b = blockIdx.y;
+  double s = 0.0;
+  for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+    float x = z[b * N + n], t = y[b * N + n];
+    float l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+    s += (double)l;
+    if (dz) dz[b * N + n] = (1.f / (1.f + expf(-x)) - t) * gscale_over_B;
+  }
+  __shared__ double red[256];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[(int64_t)b * BCE_BLOCKS + blockIdx.x] = red[0];
+}
+
+// per sample: its blocks in ascending order; then the samples in ascending order (bce_final_kernel's)
+__global__ void bce_parts_final_kernel(const double *__restrict__ part, float *__restrict__ loss, int64_t B, int blocks) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    double s = 0.0;
+    for (int64_t b = 0; b < B; ++b) {
+      double p = 0.0;
+      for (int i = 0; i < blocks; ++i) p += part[b * BCE_BLOCKS + i];
+      s += p;
+    }
+    loss[0] = (float)(s / (double)B);
+  }
+}
+
 int check_epi(int epilogue, const float *bias, const float *mask) {
   SVR_CHECK(epilogue >= SVR_EPI_NONE && epilogue <= SVR_EPI_MASK, SVR_E_BADARG, "bad epilogue %d", epilogue);
   SVR_CHECK(!(epilogue == SVR_EPI_BIAS || epilogue == SVR_EPI_BIAS_RELU) || bias, SVR_E_BADARG, "epilogue needs bias");
@@ -465,4 +502,20 @@ extern "C" int svr_bce_logits_sum_mean(const float *logits, const float *targets
   hipLaunchKernelGGL(bce_kernel, dim3(gx, (unsigned)B), dim3(256), 0, s, logits, targets, dlogits, (double *)workspace, N, gscale / (float)B);
   hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(64), 0, s, (const double *)workspace, loss, B);
   return launch_status("bce");
+}
+
+extern "C" int64_t svr_bce_ordered_workspace(int64_t B) {
+  return (B > 0 ? B : 1) * BCE_BLOCKS * (int64_t)sizeof(double);
+}
+
+extern "C" int svr_bce_logits_sum_mean_ordered(const float *logits, const float *targets, float *loss, float *dlogits, int64_t B,
+                                               int64_t N, float gscale, void *workspace, void *stream) {
+  SVR_CHECK(logits && targets && loss && workspace, SVR_E_BADARG, "bce_ordered: null pointer");
+  SVR_CHECK(B > 0 && N > 0 && B < 65536, SVR_E_BADSHAPE, "bce_ordered: B=%ld N=%ld", (long)B, (long)N);
+  hipStream_t s = (hipStream_t)stream;
+  int64_t gx64 = cdiv(N, 256); unsigned gx = (unsigned)(gx64 < BCE_BLOCKS ? gx64 : BCE_BLOCKS);
+  hipLaunchKernelGGL(bce_parts_kernel, dim3(gx, (unsigned)B), dim3(256), 0, s, logits, targets, dlogits, (double *)workspace, N,
+                     gscale / (float)B);
+  hipLaunchKernelGGL(bce_parts_final_kernel, dim3(1), dim3(64), 0, s, (const double *)workspace, loss, B, (int)gx);
+  return launch_status("bce_ordered");
 }

@@ -69,9 +69,11 @@ def _get_side_stream(device, which=0):
 # planes pull 1.72/1.81/3.53, items 0.65/0.56/0.49 -- longest walk 13/24/94 against 1409/1669/3282.
 SCATTER_FORM = os.environ.get("SVR_SCATTER_FORM", "auto")
 # Bit-reproducible training step (SVR_DETERMINISTIC=1, or set ifnet.DETERMINISTIC before the step): every scatter of the
-# backward takes an atomic-free form -- pull plans for the levels with C <= 64 whatever the point distribution, the two-pass
-# form for the projected 128-channel levels -- so no float atomic is left in the step and two runs give the same bits
-# (every other reduction of the step already has a fixed order).  Measured on one box, configs[2], uniform points: 17.0 ms
+# backward takes an atomic-free form -- pull plans for the levels with C <= 64 whatever the point distribution (level 0, the
+# one-channel input grid, included when the input takes a gradient: the scene step), the two-pass form for the projected
+# 128-channel levels -- and the BCE adds its block sums in block order, so no float atomic is left in the IF-Net step and two
+# runs give the same bits.  The same switch covers the scene step's projection (ordered splat and blur-tap sums,
+# model/projection.py) and depth head (trainer/trainer_scene_net.py): DESIGN.md section 16.  Measured on one box, configs[2], uniform points: 17.0 ms
 # against 16.2 ms per step (the atomic forms win inside the backward's fork, and level 3's pull form is bound by its longest
 # walk); with surface-clustered points the pull form is several times slower, so it is a mode, not
 # the default.  A level that has no atomic-free form (C = 128 without the projection: the 32-architecture) raises.
@@ -114,12 +116,14 @@ def _level_dims(D, H, W, l):
     return (max(D >> s, 1), max(H >> s, 1), max(W >> s, 1))
 
 
-def _level_orders_async(pts, D, H, W, n_levels, align, layout=None, disp=None, proj_levels=(), arena=None):
+def _level_orders_async(pts, D, H, W, n_levels, align, layout=None, disp=None, proj_levels=(), arena=None, need_level0=False):
     """Backward-scatter preparation that depends only on the points, computed on a side stream beside the encoder;
     returns (orders per level, pull plans per level, ready event).  Level l has the pyramid's resolution
     (D, H, W) >> (l - 1) for l >= 1 (level 0 is the input grid, one channel: neither).  See SCATTER_FORM.
     layout: the layout of the gradient rows the scatter will read (the full FeatureLayout, or the KeptLayout of the fused
-    step).  arena: the step's StepArena -- the plans' arrays then live there (no allocator traffic on the side stream)."""
+    step).  arena: the step's StepArena -- the plans' arrays then live there (no allocator traffic on the side stream).
+    need_level0: the input grid takes a gradient (the scene step: it is the projected voxel occupancy) -- under
+    DETERMINISTIC level 0 (one channel) then gets a pull plan too; otherwise it keeps its float-atomic scatter."""
     B, N = pts.shape[0], pts.shape[1]
     orders = [None] * n_levels
     plans = [None] * n_levels
@@ -135,6 +139,14 @@ def _level_orders_async(pts, D, H, W, n_levels, align, layout=None, disp=None, p
     form = "pull" if DETERMINISTIC else SCATTER_FORM
     fits32 = layout is not None and N > 0 and 7 * B * N < 2 ** 31 and B * N * layout.row_stride < 2 ** 31
     with torch.cuda.stream(side):
+        if DETERMINISTIC and need_level0 and N > 0:
+            dhw = (D, H, W)
+            if not (fits32 and layout.channels[0] == 1 and B * (D + 1) * (H + 1) * (W + 1) < 2 ** 31 - 1):
+                raise RuntimeError(f"IF-Net HIP path, DETERMINISTIC: the input grid's gradient (level 0, {dhw}, batch {B}, {N} points) "
+                                   "exceeds the pull plan's 32-bit cell / item / gradient offsets and has no other atomic-free scatter")
+            plans[0] = ops.pull_plan(pts, dhw, 1, layout.col[0], layout.row_stride, disp, align, arena=arena, tag="L0.")
+            plans[0].record_stream(main)
+            launched = True
         for l in range(1, n_levels):
             dhw = _level_dims(D, H, W, l)
             C = layout.channels[l] if layout is not None else 0
@@ -380,11 +392,12 @@ def _scatter_state(orders, plans, ready, gvols, ext, levels, pts, layout, proj, 
     """What the forward prepared for the scatter, or the same built now: (orders, plans, ready event, gradient volumes)."""
     if orders is None:
         orders, plans, ready = _level_orders_async(pts, *levels[0].shape[1:4], len(levels), ext._align, layout, ext._disp,
-                                                   proj_levels=proj, arena=arena)
+                                                   proj_levels=proj, arena=arena, need_level0=need_x)
     if ops.GATHER_FLAGS & ops._lib.GATHER_DETERMINISTIC:      # the serial test scatter accumulates into zeros
         plans = [None] * len(levels)
         gvols = None
-    g0 = torch.zeros_like(levels[0]) if need_x else None      # the raw grid's: only for d(loss)/d(input)
+    # the raw grid's: only for d(loss)/d(input); a level-0 pull plan (DETERMINISTIC) writes every voxel of it
+    g0 = (torch.empty_like(levels[0]) if plans[0] is not None else torch.zeros_like(levels[0])) if need_x else None
     if gvols is None:
         gvols = _gvols(arena, levels, plans, proj)
     return orders, plans, ready, [g0] + gvols[1:]
@@ -552,7 +565,7 @@ class _EncoderGatherFn(torch.autograd.Function):
         if will_backward and x.is_cuda:
             ctx.level_orders, ctx.level_plans, ctx.orders_ready = _level_orders_async(
                 pts, D, H, W, nlev, ext._align, ctx.klay if ctx.klay is not None else ext._layout, ext._disp,
-                proj_levels=proj, arena=arena)
+                proj_levels=proj, arena=arena, need_level0=bool(ctx.needs_input_grad[6]))
         levels, saved = _run_stages(ext, x_cl, training, for_backward=True)
         if training:      # one multi-tensor launch for the counters of all stages
             torch._foreach_add_([bn.num_batches_tracked for _, bn in ext._stages], 1)

@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from . import ifnet as _ifnet      # _ifnet.DETERMINISTIC (SVR_DETERMINISTIC=1) is read at call time
 
 _FOCAL, _CX, _CY = 277.1281435, 159.5, 119.5
 
@@ -48,14 +49,19 @@ class _UnprojectFn(torch.autograd.Function):
 
 
 class _SplatFn(torch.autograd.Function):
-    """pc_voxels: clamp(8 * trilinear splat, 0, 1) -- projection.py:39-80 incl. the x8 alias quirk."""
+    """pc_voxels: clamp(8 * trilinear splat, 0, 1) -- projection.py:39-80 incl. the x8 alias quirk.
+    Under ifnet.DETERMINISTIC: the ordered splat (fixed summation order, no float atomics; clamp from the same kernel)."""
 
     @staticmethod
     def forward(ctx, pts, dims):
         pts = pts.contiguous()
+        ctx.dims = dims
+        if _ifnet.DETERMINISTIC:
+            acc, _, _, vox = ops.splat_fwd(pts, dims, ordered=True, want_vox=True)      # raises beyond its 32-bit limits
+            ctx.save_for_backward(pts, acc)
+            return vox
         acc, _, _ = ops.splat_fwd(pts, dims)
         ctx.save_for_backward(pts, acc)
-        ctx.dims = dims
         return ops.scale_clamp01(acc, 8.0)
 
     @staticmethod
@@ -76,15 +82,16 @@ class _BlurFn(torch.autograd.Function):
         a2 = ops.blur_axis(a1, taps[1], 1)
         a3 = ops.blur_axis(a2, taps[2], 0)
         ctx.save_for_backward(vox, a1, a2, a3, *taps)
+        ctx.ordered = _ifnet.DETERMINISTIC      # the tap gradients' block sums in block order instead of float64 atomics
         return ops.scale_clamp01(a3, 1.0)
 
     @staticmethod
     def backward(ctx, gout):
         vox, a1, a2, a3, t0, t1, t2 = ctx.saved_tensors
         g3 = ops.scale_clamp01_bwd(a3, gout.contiguous(), 1.0)
-        g2, gt2 = ops.blur_axis_bwd(a2, t2, g3, 0)
-        g1, gt1 = ops.blur_axis_bwd(a1, t1, g2, 1)
-        g0, gt0 = ops.blur_axis_bwd(vox, t0, g1, 2, want_gin=ctx.needs_input_grad[0])
+        g2, gt2 = ops.blur_axis_bwd(a2, t2, g3, 0, ordered=ctx.ordered)
+        g1, gt1 = ops.blur_axis_bwd(a1, t1, g2, 1, ordered=ctx.ordered)
+        g0, gt0 = ops.blur_axis_bwd(vox, t0, g1, 2, want_gin=ctx.needs_input_grad[0], ordered=ctx.ordered)
         return g0, gt0.float(), gt1.float(), gt2.float()
 
 

@@ -882,11 +882,18 @@ def fc_out_bwd(h, w, dlogits, row_map=None):
     return dh, dw, db
 
 
-def bce_logits_sum_mean(logits, targets, want_grad=True, gscale=1.0):
+def bce_logits_sum_mean(logits, targets, want_grad=True, gscale=1.0, ordered=False):
+    """ordered: the per-sample sums in a fixed block order (svr_bce_logits_sum_mean_ordered) instead of float64 atomics."""
     _f32(logits, targets)
     B, N = logits.shape
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
     dz = torch.empty_like(logits) if want_grad else None
+    if ordered:
+        l = _lib.lib()
+        ws = torch.empty(int(l.svr_bce_ordered_workspace(B)) // 8, device=logits.device, dtype=torch.float64)
+        check(l.svr_bce_logits_sum_mean_ordered(_p(logits), _p(targets), _p(loss), _p(dz), B, N, gscale, _p(ws), _stream()),
+              "bce_ordered")
+        return loss, dz
     ws = torch.empty(B, device=logits.device, dtype=torch.float64)
     check(_lib.lib().svr_bce_logits_sum_mean(_p(logits), _p(targets), _p(loss), _p(dz), B, N, gscale, _p(ws), _stream()),
           "bce")
@@ -1235,12 +1242,39 @@ def unproject_bwd(depth, gpc, consts, normalize):
     return gd
 
 
-def splat_fwd(pts, dims, want_indices=False):
+def splat_ordered_supported(B, N, dims):
+    """32-bit keys of the ordered splat: cells of the (D0+1)(D1+1)(D2+1) lattice below 2^31 - 1, points below 2^31."""
+    return B * (dims[0] + 1) * (dims[1] + 1) * (dims[2] + 1) < 2 ** 31 - 1 and B * N < 2 ** 31
+
+
+def splat_fwd(pts, dims, want_indices=False, ordered=False, want_vox=False):
+    """-> acc (B, *dims), base, valid.  ordered: the atomic-free splat in the fixed summation order of include/svr_hip.h
+    (svr_voxelize_splat_fwd_ordered; bit-reproducible, raises beyond its 32-bit limits); with want_vox a fourth result,
+    clamp(8 * acc, 0, 1) from the same kernel."""
     _f32(pts)
     B, N, _ = pts.shape
-    acc = torch.zeros(B, *dims, device=pts.device, dtype=torch.float32)
     base = torch.empty(B, N, 3, device=pts.device, dtype=torch.int32) if want_indices else None
     valid = torch.empty(B, N, device=pts.device, dtype=torch.uint8) if want_indices else None
+    if ordered:
+        dims = tuple(int(d) for d in dims)
+        if not splat_ordered_supported(B, N, dims):
+            raise RuntimeError(f"splat_fwd(ordered=True): B={B}, N={N}, dims={dims} exceed the ordered splat's 32-bit limits "
+                               "(B*(D0+1)(D1+1)(D2+1) < 2^31 - 1 and B*N < 2^31); there is no silent fall-back to atomics")
+        if not pts.is_cuda:
+            raise RuntimeError("svr_amd ops need GPU tensors (the HIP path has no CPU fallback)")
+        l = _lib.lib()
+        nbytes = int(l.svr_voxelize_splat_ordered_workspace(B, N, *dims))
+        if nbytes < 0:
+            raise RuntimeError(f"splat_fwd(ordered=True): unsupported shape B={B}, N={N}, dims={dims}")
+        acc = torch.empty(B, *dims, device=pts.device, dtype=torch.float32)      # every voxel is written
+        vox = torch.empty_like(acc) if want_vox else None
+        ws = torch.empty(nbytes, device=pts.device, dtype=torch.uint8)
+        check(l.svr_voxelize_splat_fwd_ordered(_p(pts), _p(acc), _p(vox), _p(base), _p(valid), B, N, dims[0], dims[1], dims[2],
+                                               _p(ws), _stream()), "splat_fwd_ordered")
+        return (acc, base, valid, vox) if want_vox else (acc, base, valid)
+    if want_vox:
+        raise RuntimeError("splat_fwd: want_vox is an output of the ordered kernel only")
+    acc = torch.zeros(B, *dims, device=pts.device, dtype=torch.float32)
     check(_lib.lib().svr_voxelize_splat_fwd(_p(pts), _p(acc), _p(base), _p(valid), B, N, dims[0], dims[1], dims[2], _stream()),
           "splat_fwd")
     return acc, base, valid
@@ -1273,9 +1307,19 @@ def blur_axis(x, taps, axis):
     return out
 
 
-def blur_axis_bwd(x, taps, gout, axis, want_gin=True, want_gtaps=True):
+def blur_axis_bwd(x, taps, gout, axis, want_gin=True, want_gtaps=True, ordered=False):
+    """ordered: the tap gradient's block sums are added in block order (svr_blur_axis_bwd_ordered) instead of atomically."""
     B, D0, D1, D2 = x.shape
     gin = torch.empty_like(x) if want_gin else None
+    if ordered:
+        l = _lib.lib()
+        K = taps.numel()
+        gt = torch.empty(K, device=x.device, dtype=torch.float64) if want_gtaps else None
+        ws = (torch.empty(int(l.svr_blur_axis_bwd_ordered_workspace(B, D0, D1, D2, K)) // 8, device=x.device, dtype=torch.float64)
+              if want_gtaps else None)
+        check(l.svr_blur_axis_bwd_ordered(_p(x), _p(taps), _p(gout), _p(gin), _p(gt), B, D0, D1, D2, axis, K, _p(ws), _stream()),
+              "blur_bwd_ordered")
+        return gin, gt
     gt = torch.zeros(taps.numel(), device=x.device, dtype=torch.float64) if want_gtaps else None
     check(_lib.lib().svr_blur_axis_bwd(_p(x), _p(taps), _p(gout), _p(gin), _p(gt), B, D0, D1, D2, axis, taps.numel(),
                                        _stream()), "blur_bwd")
@@ -1551,3 +1595,31 @@ def depth_head(raw, target=None, size=320, rows=(40, 280), min_z=0.1953997164964
         depth, _, _ = depth_head_fwd(raw.detach().contiguous(), None, size, rows, min_z, max_z, False)
         return depth, None
     return _DepthHeadFn.apply(raw, target, size, rows, min_z, max_z)
+
+
+class _DepthHeadSceneFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, raw, size, rows, min_z, max_z):
+        raw = raw.contiguous()
+        depth, _, _ = depth_head_fwd(raw, None, size, rows, min_z, max_z, False)
+        ctx.save_for_backward(depth)
+        ctx.raw_shape, ctx.size, ctx.rows, ctx.min_z, ctx.max_z = tuple(raw.shape), size, rows, float(min_z), float(max_z)
+        return depth
+
+    @staticmethod
+    def backward(ctx, gdepth):
+        (depth,) = ctx.saved_tensors
+        lo, hi = ctx.min_z, ctx.max_z
+        # d depth / d y of depth = sigmoid(y) * (hi - lo) + lo, from the depth map itself (elementwise: no order to fix)
+        gy = (gdepth * ((depth - lo) * (hi - depth) / (hi - lo))).contiguous()
+        return depth_head_bwd(gy, ctx.raw_shape, ctx.size, ctx.rows), None, None, None, None
+
+
+def depth_head_scene(raw, size=320, rows=(40, 280), min_z=0.1953997164964676, max_z=7.0):
+    """depth_head's depth map WITH a gradient, for the scene step (the depth map feeds the unprojection there):
+    forward = svr_depth_head_fwd without a target, backward = gy = g_depth * (depth - min_z)(max_z - depth)/(max_z - min_z)
+    and the gather-form transposed interpolation svr_depth_head_bwd -- no atomics, unlike ATen's backward of
+    F.interpolate(mode='bilinear').  size=0 / None: no resize.  Returns depth (B, 1, Ho, Wo)."""
+    if not raw.is_cuda:
+        raise RuntimeError("depth_head_scene HIP path needs GPU tensors (no CPU fallback)")
+    return _DepthHeadSceneFn.apply(raw, size, rows, min_z, max_z)

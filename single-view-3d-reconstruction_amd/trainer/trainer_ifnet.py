@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..dataset.implicit_dataset import BatchedSampleLoader, ImplicitDataset
+from ..model import ifnet as _ifnet      # _ifnet.DETERMINISTIC is read at call time
 from ..model.ifnet import IFNet, implicit_to_mesh
 from ..util.visualize import visualize_sdf
 
@@ -31,7 +32,8 @@ from ..util.visualize import visualize_sdf
 class _BCELogitsSumMeanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets):
-        loss, dz = ops.bce_logits_sum_mean(logits.contiguous(), targets.contiguous().float(), want_grad=True)
+        loss, dz = ops.bce_logits_sum_mean(logits.contiguous(), targets.contiguous().float(), want_grad=True,
+                                           ordered=_ifnet.DETERMINISTIC)
         ctx.save_for_backward(dz)
         return loss.squeeze(0)
 

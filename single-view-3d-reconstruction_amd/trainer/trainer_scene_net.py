@@ -34,6 +34,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..dataset.scene_net_data import DeviceSceneLoader, scene_net_data
+from ..model import ifnet as _ifnet
 from ..model.ifnet import IFNet, implicit_to_mesh
 from ..model.projection import project
 from ..model.unet import UNetMini, Unet
@@ -46,7 +47,7 @@ class _BCELogitsMeanFn(torch.autograd.Function):
     def forward(ctx, logits, targets):
         B, N = logits.shape
         loss, dz = ops.bce_logits_sum_mean(logits.contiguous(), targets.contiguous().float(), want_grad=True,
-                                           gscale=1.0 / N)
+                                           gscale=1.0 / N, ordered=_ifnet.DETERMINISTIC)
         ctx.save_for_backward(dz)
         return loss.squeeze(0) / N
 
@@ -116,7 +117,15 @@ class SceneNetTrainer(nn.Module):
 
     def forward(self, batch):
         h = self.hparams
-        if self.unet is not None:
+        deterministic = _ifnet.DETERMINISTIC          # read at call time, like the IF-Net's own use of it
+        if deterministic:
+            self._check_deterministic(batch)
+        if self.unet is not None and deterministic:
+            # ATen's backward of F.interpolate(mode="bilinear") accumulates with float atomics: the depth head's gather-form
+            # transposed interpolation instead (resize_input False: identity mode, the sigmoid map alone)
+            raw = self.unet(batch["rgb"])
+            depth = ops.depth_head_scene(raw, 320 if h.resize_input else 0, (40, 280), h.min_z, h.max_z).squeeze(1)
+        elif self.unet is not None:
             raw = self.unet(batch["rgb"])
             if h.resize_input:
                 logits = F.interpolate(raw, size=320, mode="bilinear")[:, :, 40:280, :].squeeze(1)
@@ -145,6 +154,20 @@ class SceneNetTrainer(nn.Module):
             points = torch.cat((point_cloud, batch["points"]), dim=1)
         logits_depth = self.ifnet(voxel_occupancy, points)
         return logits_depth, depth, point_cloud
+
+    def _check_deterministic(self, batch):
+        """What ifnet.DETERMINISTIC (SVR_DETERMINISTIC=1) cannot make bit-reproducible raises instead of running with atomics."""
+        h = self.hparams
+        if h.subsample_points != 0:
+            raise RuntimeError("SceneNetTrainer, DETERMINISTIC: subsample_points != 0 queries the projected point cloud, and "
+                               "d(loss)/d(points) of the gather is accumulated with float atomics (no atomic-free form)")
+        if getattr(h, "net_res", 128) == 32:
+            raise RuntimeError("SceneNetTrainer, DETERMINISTIC: net_res=32 has 128-channel levels without an atomic-free scatter")
+        B = int(batch["points"].shape[0])
+        dims = tuple(int(v) for v in self.dims)
+        if not ops.splat_ordered_supported(B, 240 * 320, dims):
+            raise RuntimeError(f"SceneNetTrainer, DETERMINISTIC: batch {B} x grid {dims} exceeds the ordered splat's 32-bit limits "
+                               "(B*(D0+1)(D1+1)(D2+1) < 2^31 - 1, B*N < 2^31)")
 
     def _occupancies(self, batch, point_cloud):
         """trainer_scene_net.py:108-114: ground truth of the extra query points = on-the-fly labelling against the mesh."""
