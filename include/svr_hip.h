@@ -948,6 +948,44 @@ int svr_depth_head_fwd(const float *raw, const float *target, float *depth, floa
 int svr_depth_head_bwd(const float *gdst, float *draw, int32_t B, int32_t Hs, int32_t Ws, int32_t S, int32_t r0, int32_t r1,
                        void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * RGB preprocessing of the scene network's input (replaces the torchvision chain of dataset/scene_net_data.py:30-38 on a
+ * PIL image: SquarePad -> Resize((W, W)) -> ToTensor -> Normalize(0.5, 0.5), and the FLIP_LEFT_RIGHT of
+ * dataset/scenes_dataset.py in front of it), bit for bit what Pillow's 8-bit BILINEAR resize gives.
+ *
+ * Per axis with input size `in` and output size `out` (all in double, every operation rounded on its own):
+ *   scale = in / out;  fs = max(scale, 1);  support = 1.0 * fs;  ss = 1 / fs
+ *   for xx in 0..out-1:  center = (xx + 0.5) * scale
+ *     xmin = max(0, (int)(center - support + 0.5));  xmax = min(in, (int)(center + support + 0.5))
+ *     w[x] = max(0, 1 - |(x + xmin - center + 0.5) * ss|)  for x in 0..xmax-xmin-1;   w[x] /= sum(w)
+ *     k[x] = (int)(w[x] * 2^22 + 0.5)
+ *   out[xx] = clamp((2^21 + sum_x in[xmin + x] * k[x]) >> 22, 0, 255)     per band, int32
+ * Host only:
+ *   svr_rgb_resize_taps: the largest tap count of (in, out), (int)ceil(support) * 2 + 1 (3 when out >= in, 7 for 640 -> 256).
+ *   svr_rgb_resize_table: table (out, K + 2) int32 in HOST memory, row xx = {xmin, xmax - xmin, k[0..K-1]} (unused taps 0);
+ *     K >= svr_rgb_resize_taps(in, out).  The caller uploads it; a table depends on (in, out, K) alone.
+ * svr_rgb_preprocess: src (B, H, W, C) uint8, C 1 or 3.
+ *   Wout > 0: the image (columns mirrored first when `flip`) is padded with hp = (max(H, W) - W) / 2 zero columns and
+ *     vp = (max(H, W) - H) / 2 zero rows on BOTH sides (integer division: an odd difference leaves Hp = H + 2 vp and
+ *     Wp = W + 2 hp different, 5 x 8 -> 7 x 8) and resized to Wout x Wout: columns first with table_x = the table of
+ *     (Wp, Wout) into tmp (B, Hp, Wout, C) uint8, then rows with table_y = the table of (Hp, Wout).  A pass whose sizes
+ *     agree is skipped and needs no table; tmp is needed only when both run.  Kx / Ky: the K of each table.  The padded
+ *     zeros take part in the filter; no padded image is stored.
+ *   Wout == 0: no pad and no resize, the output is H x W (flip still applies).
+ *   out_u8 (B, Ho, Wo, C) uint8 and out_f32 (B, C, Ho, Wo) float32 = norm[byte]; either may be NULL, not both.  norm: 256
+ *     floats in device memory, the value of every byte: filled by the caller with the operations to reproduce
+ *     (u / 255, then (x - 0.5) / 0.5, in float32).
+ *   One or two launches.  Source reads outside the image give 0 and a row's count is capped at K, whatever the tables hold.
+ * svr_grid_to_camera: dst[i][a] = (src[i][a] - t_a) / s_a for (n, 3) float32 points, scale_shift = {s0, t0, s1, t1, s2, t2} in
+ *   host memory: the inverse of the camera -> grid affine  g = s * c + t  of svr_unproject_fwd (consts[3..8]); dst may be src.
+ * ------------------------------------------------------------------------------------- */
+int32_t svr_rgb_resize_taps(int32_t in, int32_t out);
+int svr_rgb_resize_table(int32_t in, int32_t out, int32_t K, int32_t *table);
+int svr_rgb_preprocess(const uint8_t *src, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Wout, int32_t flip,
+                       const int32_t *table_x, int32_t Kx, const int32_t *table_y, int32_t Ky, const float *norm, uint8_t *tmp,
+                       uint8_t *out_u8, float *out_f32, void *stream);
+int svr_grid_to_camera(const float *src, float *dst, int64_t n, const float *scale_shift, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

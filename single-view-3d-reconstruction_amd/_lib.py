@@ -210,6 +210,10 @@ SIGNATURES = {
     "svr_depth_head_workspace": (I64, [I32, I32, I32]),
     "svr_depth_head_fwd": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, C.c_double, C.c_double, P, P]),
     "svr_depth_head_bwd": (C.c_int, [P, P, I32, I32, I32, I32, I32, I32, P]),
+    "svr_rgb_resize_taps": (I32, [I32, I32]),
+    "svr_rgb_resize_table": (C.c_int, [I32, I32, I32, P]),
+    "svr_rgb_preprocess": (C.c_int, [P, I32, I32, I32, I32, I32, I32, P, I32, P, I32, P, P, P, P, P]),
+    "svr_grid_to_camera": (C.c_int, [P, P, I64, C.POINTER(F32), P]),
 }
 
 _lib = None

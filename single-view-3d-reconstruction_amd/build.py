@@ -39,6 +39,7 @@ SOURCES = {
     "conv2d.hip": [],
     "conv2d_igemm.hip": [],
     "depth_head.hip": ["-ffp-contract=off"],
+    "rgb_preprocess.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-std=c++17", "-I" + INCLUDE, "-I" + CSRC,
           # per-kernel register / scratch report into build/<file>.log (resource_usage() parses it: a kernel that starts to

@@ -12,7 +12,9 @@ dict: 'name', 'mesh' (path of raw/.../mesh.obj), 'rgb', 'points', 'occupancies',
   rgb                  : host work, as in the reference.  torchvision is not a dependency, so its transform chain is written
       out: PIL open; SquarePad = constant-0 pad of hp = int((max - w) / 2) columns and vp = int((max - h) / 2) rows on both
       sides; ``Image.resize((W, W), Image.BILINEAR)`` when resize_input; scale to [0, 1], channel first; (x - 0.5) / 0.5.
-      Parity of the resize with torchvision.transforms.Resize is NOT pinned: torchvision is absent where this was
+      The resize's arithmetic IS pinned against Pillow: ops.rgb_preprocess (csrc/rgb_preprocess.hip) restates Pillow's 8-bit
+      bilinear resampler and the tests compare it, and the tables behind it, with ``Image.resize`` byte for byte (DESIGN.md
+      section 17).  Parity with torchvision.transforms.Resize is still NOT pinned: torchvision is absent where this was
       written (PIL's bilinear filter is what Resize applies to a PIL image, antialiasing included, but no test proves it).
 
 The reference reads data/splits and data/intrinsics.txt relative to the working directory; `splits_root` and
@@ -27,6 +29,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .. import ops
 from ..data_processing import sample_io
 from ..data_processing.distance_to_depth import FromDistanceToDepth, get_intrinsic
 from .implicit_dataset import SIGMAS, _split_items
@@ -120,14 +123,19 @@ class DeviceSceneLoader:
     `occupancies` (B, 2n) in place, and one stack each for `rgb` and `depthmap_target`.  The result is the dictionary
     ``default_collate`` makes of the dataset's items, bit for bit under the same numpy random state.
 
+    ``device_rgb=True``: the PNG's raw uint8 pixels (mode L or RGB) are what is staged and copied, and ops.rgb_preprocess runs
+    the transform on the copy stream -- the same `rgb` bit for bit, under a third of the bytes across the bus and no
+    Pillow resize on the host.  Off by default (DESIGN.md section 17 has the measurement).
+
     ``bad_rows()`` reads (synchronising) whether any launch saw a row outside its source: with indices drawn here it cannot."""
 
     ARRAYS = ("points", "occupancies")
 
-    def __init__(self, dataset, device=None, cache=True):
+    def __init__(self, dataset, device=None, cache=True, device_rgb=False):
         if dataset.dtype != torch.float32:
             raise ValueError("DeviceSceneLoader supports precision == 32 only")
         self.ds = dataset
+        self.device_rgb = bool(device_rgb)
         self.device = torch.device(device) if device is not None else dataset.device
         self.cache = {} if cache else None
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -140,15 +148,32 @@ class DeviceSceneLoader:
         ds = self.ds
         return ds.dataset_path / "raw" / ds.splitsdir / item, ds.dataset_path / "processed" / ds.splitsdir / item
 
+    def _decode_rgb(self, path):
+        """rgb.png -> (the transformed image on the device, its pinned staging buffer); the copy (and with device_rgb the
+        transform) is queued on the copy stream."""
+        with Image.open(path) as image:
+            if self.device_rgb:
+                if image.mode not in ("L", "RGB"):
+                    raise ValueError(f"{path}: mode {image.mode}; device_rgb takes 8-bit L or RGB images")
+                pixels = np.asarray(image, dtype=np.uint8)
+                pixels = pixels.reshape(pixels.shape[0], pixels.shape[1], -1)
+            else:
+                rgb = rgb_transform(image, self.ds.W, self.ds.resize_input)
+        with torch.cuda.stream(self.copy_stream):
+            if self.device_rgb:                              # the raw bytes cross, the transform runs behind the copy
+                stage = torch.empty(pixels.shape, dtype=torch.uint8, pin_memory=True)
+                stage.numpy()[...] = pixels
+                return ops.rgb_preprocess(stage.to(self.device, non_blocking=True).unsqueeze(0), self.ds.W,
+                                          self.ds.resize_input)[0], stage
+            stage = torch.empty(rgb.shape, dtype=torch.float32, pin_memory=True).copy_(rgb)
+            return stage.to(self.device, non_blocking=True), stage
+
     def _decode(self, item):
         raw, processed = self._folders(item)
         s, keep = {"mesh": str(raw / "mesh.obj")}, []
-        with Image.open(raw / "rgb.png") as image:
-            rgb = rgb_transform(image, self.ds.W, self.ds.resize_input)
+        s["rgb"], stage = self._decode_rgb(raw / "rgb.png")
+        keep.append(stage)
         with torch.cuda.stream(self.copy_stream):
-            stage = torch.empty(rgb.shape, dtype=torch.float32, pin_memory=True).copy_(rgb)
-            s["rgb"] = stage.to(self.device, non_blocking=True)
-            keep.append(stage)
             info = sample_io.exr_info(raw / "distance.exr")
             stage = torch.empty(info["height"] * info["width"], dtype=torch.float32, pin_memory=True)
             sample_io.exr_read(raw / "distance.exr", "R", out=stage.numpy())

@@ -1115,6 +1115,17 @@ def evaluate_network_on_grid_sparse(network, x, resolution, threshold_p, res_inc
         return sparse_lattice_field(fn, r, threshold_p, block, points_batch_size, max_rounds, device=x.device, profile=profile)
 
 
+def implicit_to_vertices(network, x, resolution, threshold_p, res_increase=1, block=None):
+    """implicit_to_mesh without the file: (vertices (V,3) float32, faces (F,3) int32) as device tensors."""
+    from ..util.visualize import marching_cubes
+    block = INFERENCE_BLOCK if block is None else _inference_block(block)
+    if block:
+        sdf = evaluate_network_on_grid_sparse(network, x, resolution, threshold_p, res_increase, block).field
+        return marching_cubes(sdf, threshold_p)
+    value_grid = evaluate_network_on_grid_device(network, x, resolution, res_increase)
+    return marching_cubes(1 - value_grid, threshold_p)
+
+
 def implicit_to_mesh(network, x, resolution, threshold_p, output_path, res_increase=1, block=None):
     """The reference's implicit_to_mesh (model/ifnet.py:232-234): the mesh of the occupancy lattice at probability
     `threshold_p`, written to `output_path` as .obj.  Computes what
@@ -1125,14 +1136,7 @@ def implicit_to_mesh(network, x, resolution, threshold_p, output_path, res_incre
     block: None takes INFERENCE_BLOCK; 0 is the dense evaluation above; an integer >= 2 queries the network only in the
     blocks of that many cells the surface passes through (evaluate_network_on_grid_sparse: the same mesh unless a surface
     component hides between the coarse points)."""
-    from ..util.visualize import export_obj, marching_cubes
-    block = INFERENCE_BLOCK if block is None else _inference_block(block)
-    if block:
-        sdf = evaluate_network_on_grid_sparse(network, x, resolution, threshold_p, res_increase, block).field
-        vertices, faces = marching_cubes(sdf, threshold_p)
-        export_obj(vertices, faces, output_path)
-        return vertices, faces
-    value_grid = evaluate_network_on_grid_device(network, x, resolution, res_increase)
-    vertices, faces = marching_cubes(1 - value_grid, threshold_p)
+    from ..util.visualize import export_obj
+    vertices, faces = implicit_to_vertices(network, x, resolution, threshold_p, res_increase, block)
     export_obj(vertices, faces, output_path)
     return vertices, faces

@@ -1623,3 +1623,97 @@ def depth_head_scene(raw, size=320, rows=(40, 280), min_z=0.1953997164964676, ma
     if not raw.is_cuda:
         raise RuntimeError("depth_head_scene HIP path needs GPU tensors (no CPU fallback)")
     return _DepthHeadSceneFn.apply(raw, size, rows, min_z, max_z)
+
+
+# ------------------------------------------------------------------------------------------
+# RGB preprocessing (rgb_preprocess.hip): SquarePad -> Pillow's 8-bit bilinear resize -> ToTensor -> Normalize(0.5, 0.5)
+# ------------------------------------------------------------------------------------------
+_rgb_tables = {}      # (in, out, device) -> (device int32 (out, K + 2), K); like project._consts: built once per size
+_rgb_norm = {}        # device -> (256,) float32
+
+
+def rgb_resize_table(n_in, n_out):
+    """Pillow's coefficient table of one axis, from the library's host code (double): int32 (n_out, K + 2) numpy array, row
+    xx = [xmin, tap count, K taps in 22-bit fixed point]."""
+    import numpy as np
+    l = _lib.lib()
+    K = int(l.svr_rgb_resize_taps(int(n_in), int(n_out)))
+    if K < 0:
+        check(K, "rgb_resize_taps")
+    table = np.empty((int(n_out), K + 2), dtype=np.int32)
+    check(l.svr_rgb_resize_table(int(n_in), int(n_out), K, table.ctypes.data_as(C.c_void_p)), "rgb_resize_table")
+    return table
+
+
+def _rgb_table(n_in, n_out, device):
+    key = (int(n_in), int(n_out), device)
+    hit = _rgb_tables.get(key)
+    if hit is None:
+        t = rgb_resize_table(n_in, n_out)
+        hit = _rgb_tables[key] = (torch.from_numpy(t).to(device), t.shape[1] - 2)
+    return hit
+
+
+def _rgb_norm_table(device):
+    t = _rgb_norm.get(device)
+    if t is None:
+        # ToTensor's and Normalize's own float32 operations, on the host like rgb_transform, once per byte value
+        x = torch.arange(256, dtype=torch.uint8).float().div(255)
+        t = _rgb_norm[device] = ((x - 0.5) / 0.5).to(device)
+    return t
+
+
+def rgb_preprocess(images_u8, W=256, resize_input=True, flip=False, return_u8=False):
+    """dataset.scene_net_data.rgb_transform on the device, for a batch of equal-sized images.
+
+    images_u8: (B, H, W, C) uint8 GPU tensor, C 1 or 3 (raw pixels, rows of interleaved bands as PIL stores them).
+    resize_input: SquarePad with zeros, then Pillow's ``Image.resize((W, W), Image.BILINEAR)`` (antialiased, two 8-bit
+    passes) bit for bit; otherwise only the layout change.  flip: ``Image.FLIP_LEFT_RIGHT`` in front of the pad.
+    -> (B, C, Ho, Wo) float32, ``(x / 255 - 0.5) / 0.5`` as torch rounds it; with return_u8 also the resized bytes
+    (B, Ho, Wo, C) uint8.  The per-axis tables and the byte -> float table are cached on the device."""
+    if not torch.is_tensor(images_u8) or not images_u8.is_cuda:
+        raise RuntimeError("rgb_preprocess HIP path needs GPU tensors (no CPU fallback)")
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
+        raise ValueError(f"rgb_preprocess: expected (B, H, W, C) uint8, got {tuple(images_u8.shape)} {images_u8.dtype}")
+    src = images_u8.contiguous()
+    B, H, Wi, Cn = (int(s) for s in src.shape)
+    if Cn not in (1, 3):
+        raise ValueError(f"rgb_preprocess: {Cn} bands (1 or 3)")
+    if min(B, H, Wi) < 1:
+        raise ValueError(f"rgb_preprocess: empty batch {tuple(src.shape)}")
+    dev = src.device
+    tx = ty = tmp = None
+    Kx = Ky = 0
+    if resize_input:
+        Wout = int(W)
+        if Wout < 1:
+            raise ValueError(f"rgb_preprocess: W={W}")
+        m = max(H, Wi)
+        Hp, Wp = H + 2 * ((m - H) // 2), Wi + 2 * ((m - Wi) // 2)
+        if Wp != Wout:
+            tx, Kx = _rgb_table(Wp, Wout, dev)
+        if Hp != Wout:
+            ty, Ky = _rgb_table(Hp, Wout, dev)
+        if tx is not None and ty is not None:
+            tmp = torch.empty((B, Hp, Wout, Cn), device=dev, dtype=torch.uint8)
+        Ho = Wo = Wout
+    else:
+        Wout, Ho, Wo = 0, H, Wi
+    out = torch.empty((B, Cn, Ho, Wo), device=dev, dtype=torch.float32)
+    u8 = torch.empty((B, Ho, Wo, Cn), device=dev, dtype=torch.uint8) if return_u8 else None
+    check(_lib.lib().svr_rgb_preprocess(_p(src), B, H, Wi, Cn, Wout, int(bool(flip)), _p(tx), Kx, _p(ty), Ky,
+                                        _p(_rgb_norm_table(dev)), _p(tmp), _p(u8), _p(out), _stream()), "rgb_preprocess")
+    return (out, u8) if return_u8 else out
+
+
+def grid_to_camera(points, scale_shift):
+    """(n, 3) float32 grid-space points -> camera space: (p - t) / s per axis, scale_shift = (s0, t0, s1, t1, s2, t2): the
+    inverse of the affine behind `unproject` (consts[3:9])."""
+    _f32(points)
+    pts = points.contiguous()
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"grid_to_camera: expected (n, 3), got {tuple(pts.shape)}")
+    out = torch.empty_like(pts)
+    k = (C.c_float * 6)(*[float(v) for v in scale_shift])
+    check(_lib.lib().svr_grid_to_camera(_p(pts), _p(out), pts.shape[0], k, _stream()), "grid_to_camera")
+    return out

@@ -1,0 +1,202 @@
+"""Images in, meshes out: inference with a trained scene network, without a dataset tree.
+
+``Reconstructor(model)`` wraps a ``SceneNetTrainer`` (moved to ``.cuda().eval()``);
+``Reconstructor.from_checkpoint(path, inf_res=None, scale_factor=None, skip_unet=None, block=None)`` builds the trainer from
+the checkpoint's hyper-parameters, with the overrides ``run_scene_net_test`` applies (None keeps the checkpoint's value).
+
+``reconstruct(images, flip=False)``: a path, a PIL image, a uint8 (H, W, 3) array or tensor, or a list of those.  Any other
+Pillow mode is converted with ``.convert("RGB")`` on the host.  Equal-sized images run as one batch.  Under ``no_grad``:
+ops.rgb_preprocess (the dataset's transform on the device: SquarePad + Pillow's bilinear resize when the model was trained
+with resize_input, the flip in front of it, the normalisation) -> UNet -> depth head -> project.depthmap_to_gridspace
+(normalize=True) -> project() -> per view the IF-Net lattice on ``model.dims`` at ``res_increase = inf_res`` and marching
+cubes (ifnet.implicit_to_vertices; `block` as in implicit_to_mesh).  The depth and voxel stages are the trainer's own
+(``SceneNetTrainer._predict_depth`` / ``_voxels_from_depth``), so the tensors are the ones ``forward`` computes; the IF-Net
+is never queried on training points and no batch dictionary exists.  One input gives one ``Reconstruction``, a list a list.
+
+``reconstruct_depth(depth)``: the same from a (B, 240, 320) depth tensor (device tensor or numpy array) or from the path
+of a distance ``.exr`` (channel R, then FromDistanceToDepth): what a ``skip_unet`` model uses.
+
+``Reconstruction``: `depth` (240, 320), `point_cloud` (76800, 3, normalised grid space), `voxel_occupancy` (1, *dims),
+`vertices` (V, 3) float32 and `faces` (F, 3) int32, all on the device.  ``save(prefix, space="grid")`` writes
+``<prefix>_predicted.obj``, ``<prefix>_voxelized.obj`` (nothing when no voxel is occupied) and ``<prefix>_depthmap.png`` /
+``.exr`` as ``SceneNetTrainer.visualize_intermediates`` does (depth columns flipped) and returns the paths.  `space` is the
+predicted mesh's: "grid" = lattice index space as ``--test`` writes it; "normalized" = what
+``convert_to_scaled_obj.normalize_meshes`` makes of that file (byte for byte); "camera" = metric camera coordinates, the
+inverse of ``projection._camera_to_grid(intrinsic, scale_factor)`` (vertices / inf_res first when inf_res > 1: the lattice
+index is inf_res times the grid coordinate), in csrc/rgb_preprocess.hip's svr_grid_to_camera.
+
+``python -m svr_amd.reconstruct --checkpoint C (--rgb a.png [b.png ...] | --distance d.exr) --out DIR [--inf_res n]
+[--block s] [--space grid|normalized|camera] [--flip]`` prints one line per view: the written paths, vertex and face counts."""
+import argparse
+import os
+from pathlib import Path
+
+import numpy as np
+import torch
+from PIL import Image
+
+from . import ops
+from .data_processing import sample_io
+from .data_processing.distance_to_depth import FromDistanceToDepth, get_intrinsic
+from .model.ifnet import implicit_to_vertices
+from .util.visualize import export_obj, visualize_depthmap, visualize_grid
+
+SPACES = ("grid", "normalized", "camera")
+
+
+class Reconstruction:
+    """One view's result (module docstring)."""
+
+    def __init__(self, depth, point_cloud, voxel_occupancy, vertices, faces, scale_factor, inf_res, scale_shift):
+        self.depth, self.point_cloud, self.voxel_occupancy = depth, point_cloud, voxel_occupancy
+        self.vertices, self.faces = vertices, faces
+        self._scale_factor, self._inf_res, self._scale_shift = scale_factor, int(inf_res), scale_shift
+
+    def vertices_in(self, space):
+        """The predicted mesh's vertices in `space`: a device tensor ("grid", "camera") or a float32 numpy array ("normalized":
+        normalize_meshes' float64 formula, rounded once)."""
+        if space == "grid":
+            return self.vertices
+        if space == "normalized":
+            dims = np.array([139, 104, 112], dtype=np.float64) / np.round(self._scale_factor).astype(np.int64)
+            # normalize_meshes starts from the FILE: the float64 nearest to each vertex's 9-digit decimal, not the widened float32
+            v = self.vertices.cpu().numpy()
+            v = np.char.mod("%.9g", v.reshape(-1)).astype(np.float64).reshape(v.shape)
+            return ((v - dims / 2) / dims).astype(np.float32)
+        if space == "camera":
+            v = self.vertices if self._inf_res == 1 else self.vertices / float(self._inf_res)
+            return ops.grid_to_camera(v, self._scale_shift)
+        raise ValueError(f"space must be one of {SPACES}, got {space!r}")
+
+    def save(self, prefix, space="grid"):
+        vertices = self.vertices_in(space)
+        prefix = os.fspath(prefix)
+        if os.path.dirname(prefix):
+            os.makedirs(os.path.dirname(prefix), exist_ok=True)
+        paths = {"predicted": prefix + "_predicted.obj", "voxelized": prefix + "_voxelized.obj",
+                 "depthmap_png": prefix + "_depthmap.png", "depthmap_exr": prefix + "_depthmap.exr"}
+        vox = self.voxel_occupancy
+        visualize_grid(vox.reshape(vox.shape[-3:]), paths["voxelized"])
+        export_obj(vertices, self.faces, paths["predicted"])
+        visualize_depthmap(self.depth, prefix + "_depthmap", flip=True)
+        if not os.path.exists(paths["voxelized"]):
+            del paths["voxelized"]
+        return paths
+
+
+def _pixels(image):
+    """One input of reconstruct() -> (H, W, 3) uint8, a numpy array or a device tensor."""
+    if isinstance(image, (str, os.PathLike)):
+        with Image.open(image) as im:
+            return np.array(im.convert("RGB"), dtype=np.uint8)
+    if isinstance(image, Image.Image):
+        return np.array(image.convert("RGB"), dtype=np.uint8)
+    a = image if torch.is_tensor(image) else np.asarray(image)
+    if a.dtype != (torch.uint8 if torch.is_tensor(a) else np.uint8) or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"reconstruct: an image array must be (H, W, 3) uint8, got {tuple(a.shape)} {a.dtype}")
+    return a
+
+
+class Reconstructor:
+    def __init__(self, model, block=None):
+        self.model = model.cuda().eval()
+        self.block = block
+
+    @classmethod
+    def from_checkpoint(cls, path, inf_res=None, scale_factor=None, skip_unet=None, block=None):
+        from .trainer.checkpoint import load_checkpoint
+        from .trainer.trainer_scene_net import SceneNetTrainer
+        ck = load_checkpoint(path)
+        hparams = argparse.Namespace(**ck["hyper_parameters"])
+        for name, value in (("inf_res", inf_res), ("scale_factor", scale_factor), ("skip_unet", skip_unet)):
+            if value is not None:
+                setattr(hparams, name, value)
+        model = SceneNetTrainer(hparams)
+        model.load_state_dict({k: v for k, v in ck["state_dict"].items() if model.unet is not None or not k.startswith("unet.")})
+        return cls(model, block)
+
+    @property
+    def device(self):
+        return next(self.model.ifnet.parameters()).device
+
+    def _views(self, depth, point_cloud, voxel_occupancy):
+        m, h = self.model, self.model.hparams
+        dims = m.dims.cpu().numpy().astype(np.int32)
+        inf_res = int(getattr(h, "inf_res", 1))
+        scale_shift = m.project._consts(h.scale_factor)[3:9]
+        views = []
+        for i in range(depth.shape[0]):
+            vox = voxel_occupancy[i]
+            vertices, faces = implicit_to_vertices(m.ifnet, vox.reshape(1, 1, *vox.shape[-3:]), dims, 0.5, inf_res, self.block)
+            views.append(Reconstruction(depth[i], point_cloud[i], vox, vertices, faces, h.scale_factor, inf_res, scale_shift))
+        return views
+
+    def preprocess(self, pixels, flip=False):
+        """(B, H, W, 3) uint8 device tensor -> the UNet's input, as the dataset's transform makes it."""
+        h = self.model.hparams
+        return ops.rgb_preprocess(pixels, int(getattr(h, "W", 256)), bool(h.resize_input), flip)
+
+    def reconstruct(self, images, flip=False):
+        if self.model.unet is None:
+            raise RuntimeError("reconstruct: this model was built with skip_unet and has no UNet to predict a depth map from an "
+                               "image; give it a depth map or a distance .exr through reconstruct_depth()")
+        single = not isinstance(images, (list, tuple))
+        pixels = [_pixels(im) for im in ([images] if single else images)]
+        if not self.model.hparams.resize_input and any(tuple(p.shape[:2]) != (240, 320) for p in pixels):
+            raise ValueError("reconstruct: a model trained without resize_input takes 240 x 320 images only")
+        groups = {}
+        for i, p in enumerate(pixels):
+            groups.setdefault(tuple(p.shape), []).append(i)
+        out = [None] * len(pixels)
+        with torch.no_grad():
+            for indices in groups.values():
+                batch = torch.stack([torch.as_tensor(pixels[i]).to(self.device) for i in indices])
+                depth = self.model._predict_depth(self.preprocess(batch, flip))
+                for i, view in zip(indices, self._views(depth, *self.model._voxels_from_depth(depth))):
+                    out[i] = view
+        return out[0] if single else out
+
+    def reconstruct_depth(self, depth):
+        h = self.model.hparams
+        if isinstance(depth, (str, os.PathLike)):
+            distance = sample_io.exr_read(depth, "R")
+            depth = FromDistanceToDepth(get_intrinsic(getattr(h, "intrinsics_path", None))[0][0])(distance)
+        elif not torch.is_tensor(depth):
+            depth = torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(self.device)
+        elif not depth.is_cuda:
+            raise RuntimeError("reconstruct_depth HIP path needs GPU tensors (no CPU fallback)")
+        single = depth.dim() == 2
+        depth = (depth.unsqueeze(0) if single else depth).float().contiguous()
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (240, 320):
+            raise ValueError(f"reconstruct_depth: expected (B, 240, 320) or (240, 320), got {tuple(depth.shape)}")
+        with torch.no_grad():
+            views = self._views(depth, *self.model._voxels_from_depth(depth))
+        return views[0] if single else views
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="Reconstruct meshes from images with a trained scene network")
+    parser.add_argument("--checkpoint", required=True, help="a train_scene_net checkpoint")
+    source = parser.add_mutually_exclusive_group(required=True)
+    source.add_argument("--rgb", nargs="+", help="image files")
+    source.add_argument("--distance", help="a distance .exr (channel R): skips the UNet")
+    parser.add_argument("--out", required=True, help="output directory")
+    parser.add_argument("--inf_res", type=int, default=None, help="inference lattice per grid cell (default: the checkpoint's)")
+    parser.add_argument("--block", type=int, default=None, help="sparse lattice block edge, 0 = dense (default: SVR_INF_BLOCK)")
+    parser.add_argument("--space", choices=SPACES, default="grid", help="space of the predicted mesh")
+    parser.add_argument("--flip", action="store_true", help="mirror the images left-right first")
+    args = parser.parse_args(argv)
+    rec = Reconstructor.from_checkpoint(args.checkpoint, inf_res=args.inf_res, skip_unet=True if args.distance else None,
+                                        block=args.block)
+    if args.distance:
+        names, views = [Path(args.distance).stem], [rec.reconstruct_depth(args.distance)]
+    else:
+        names, views = [Path(p).stem for p in args.rgb], rec.reconstruct(list(args.rgb), flip=args.flip)
+    for name, view in zip(names, views):
+        paths = view.save(Path(args.out) / name, space=args.space)
+        print(" ".join(paths.values()), f"vertices={view.vertices.shape[0]} faces={view.faces.shape[0]}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

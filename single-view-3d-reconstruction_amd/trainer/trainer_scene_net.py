@@ -115,30 +115,39 @@ class SceneNetTrainer(nn.Module):
         return torch.utils.data.DataLoader(self.dataset("test"), batch_size=self.hparams.batch_size, shuffle=False, num_workers=0,
                                            drop_last=False)
 
-    def forward(self, batch):
+    def _depth_and_voxels(self, batch):
+        """The stages in front of the IF-Net query, shared with reconstruct.Reconstructor: batch['rgb'] (or, without a UNet,
+        batch['depthmap_target']) -> (depth (B, 240, 320), point_cloud (B, 76800, 3) normalised grid space,
+        voxel_occupancy (B, 1, *dims)).  Reads no other key."""
+        depth = self._predict_depth(batch["rgb"]) if self.unet is not None else batch["depthmap_target"]
+        return (depth,) + self._voxels_from_depth(depth)
+
+    def _predict_depth(self, rgb):
+        """rgb (B, 3, H, W) -> depth (B, 240, 320): the UNet and its depth head."""
         h = self.hparams
-        deterministic = _ifnet.DETERMINISTIC          # read at call time, like the IF-Net's own use of it
-        if deterministic:
-            self._check_deterministic(batch)
-        if self.unet is not None and deterministic:
+        raw = self.unet(rgb)
+        if _ifnet.DETERMINISTIC:                      # read at call time, like the IF-Net's own use of it
             # ATen's backward of F.interpolate(mode="bilinear") accumulates with float atomics: the depth head's gather-form
             # transposed interpolation instead (resize_input False: identity mode, the sigmoid map alone)
-            raw = self.unet(batch["rgb"])
-            depth = ops.depth_head_scene(raw, 320 if h.resize_input else 0, (40, 280), h.min_z, h.max_z).squeeze(1)
-        elif self.unet is not None:
-            raw = self.unet(batch["rgb"])
-            if h.resize_input:
-                logits = F.interpolate(raw, size=320, mode="bilinear")[:, :, 40:280, :].squeeze(1)
-            else:
-                # UNetMini's (B, 1, 240, 320): one map per item, like the resized branch.  (The reference keeps the channel
-                # axis here, :77, and its mse_loss then broadcasts (B, 1, H, W) against the (B, H, W) target to B x B pairs.)
-                logits = raw.squeeze(1)
-            depth = torch.sigmoid(logits) * (h.max_z - h.min_z) + h.min_z
+            return ops.depth_head_scene(raw, 320 if h.resize_input else 0, (40, 280), h.min_z, h.max_z).squeeze(1)
+        if h.resize_input:
+            logits = F.interpolate(raw, size=320, mode="bilinear")[:, :, 40:280, :].squeeze(1)
         else:
-            depth = batch["depthmap_target"]
-        # unproject + normalise fused in one kernel
-        point_cloud = self.project.depthmap_to_gridspace(depth.contiguous(), h.scale_factor, normalize=True)
-        voxel_occupancy = self.project(point_cloud)
+            # UNetMini's (B, 1, 240, 320): one map per item, like the resized branch.  (The reference keeps the channel
+            # axis here, :77, and its mse_loss then broadcasts (B, 1, H, W) against the (B, H, W) target to B x B pairs.)
+            logits = raw.squeeze(1)
+        return torch.sigmoid(logits) * (h.max_z - h.min_z) + h.min_z
+
+    def _voxels_from_depth(self, depth):
+        """depth (B, 240, 320) -> (point_cloud, voxel_occupancy): unproject + normalise fused in one kernel, then project()."""
+        point_cloud = self.project.depthmap_to_gridspace(depth.contiguous(), self.hparams.scale_factor, normalize=True)
+        return point_cloud, self.project(point_cloud)
+
+    def forward(self, batch):
+        h = self.hparams
+        if _ifnet.DETERMINISTIC:
+            self._check_deterministic(batch)
+        depth, point_cloud, voxel_occupancy = self._depth_and_voxels(batch)
         # trainer_scene_net.py:91-99.  The reference's first condition reads `n < (240*320) & n > 0`: `&` binds tighter
         # than the comparisons, so it is the chain  n < (76800 & n) > 0 , which no n satisfies (76800 & n <= n) -- the
         # random-subset branch is dead code there and the whole point cloud is used whenever n != 0.  Mirrored as is.
