@@ -796,6 +796,62 @@ int svr_eval_sums(const float *dist, const double *dot, int64_t n, double *sums_
 int svr_iou_counts(const uint8_t *a, const uint8_t *b, int64_t n, int64_t *counts_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Unsigned distance field of a triangle mesh on a lattice (no reference op: the reference's distance_field.df came
+ * from a tool that was never shipped; data_processing/mesh_to_df.py drives this, tests/df_oracle.py restates it in
+ * numpy).  Errors, ownership and streams as for svr_mc_*; one rounding per operation (no contraction).
+ *   tri: (F, 9) float64 on the device, a, b, c per face, in grid index space (what svr_mc_emit writes: x along
+ *   axis 0).  Lattice (X, Y, Z), every extent >= 1, fewer than 2^31 points; point (i, j, k) sits at p = (i, j, k).
+ *   dot(u, v) := (ux*vx + uy*vy) + uz*vz.  Per pair (p, face), all float64, in this order:
+ *     ab = b - a;  ac = c - a;  ap = p - a;  bp = p - b;  cp = p - c                 (per component)
+ *     d1 = dot(ab, ap);  d2 = dot(ac, ap);  d3 = dot(ab, bp);  d4 = dot(ac, bp);  d5 = dot(ab, cp);  d6 = dot(ac, cp)
+ *     vc = d1*d4 - d3*d2;  vb = d5*d2 - d1*d6;  va = d3*d6 - d5*d4;  e43 = d4 - d3;  e56 = d5 - d6
+ *     (v, w) := the FIRST line whose condition holds (a comparison with NaN is false):
+ *       1. d1 <= 0 and d2 <= 0                     (0, 0)                                vertex a
+ *       2. d3 >= 0 and d4 <= d3                    (1, 0)                                vertex b
+ *       3. vc <= 0 and d1 >= 0 and d3 <= 0         (d1 / (d1 - d3), 0)                   edge ab
+ *       4. d6 >= 0 and d5 <= d6                    (0, 1)                                vertex c
+ *       5. vb <= 0 and d2 >= 0 and d6 <= 0         (0, d2 / (d2 - d6))                   edge ac
+ *       6. va <= 0 and e43 >= 0 and e56 >= 0       w = e43 / (e43 + e56), v = 1 - w      edge bc
+ *       7. otherwise                               den = (va + vb) + vc, (vb / den, vc / den)   face interior
+ *     q = (a + v*ab) + w*ac;  e = p - q  (per component);  dd = dot(e, e)            (the pair's squared distance)
+ *   A face whose ab x ac = (aby*acz - abz*acy, abz*acx - abx*acz, abx*acy - aby*acx) is exactly (0, 0, 0) is skipped.
+ *   Per point: best = min dd over the other faces in ascending index with a strict `<` (the lowest index wins a tie,
+ *   a NaN dd never wins).  field[i, j, k] = (float)sqrt(best), float32, C order (X, Y, Z); face[i, j, k] = the winner
+ *   (int32, optional; -1 when no dd was a number).  truncate = T > 0: where field > (float)T, field = (float)T and
+ *   face = -1; truncate <= 0: untruncated (the .df format's rule).
+ *   The lattice is cut into bricks of s^3 points, s in {4, 8} (else SVR_E_BADSHAPE), numbered in C order of
+ *   (bx, by, bz); the last brick per axis is partial.  Per brick a candidate list of face indices, ascending, that
+ *   holds at least every face that wins a point of the brick; the field does not depend on s,
+ *   on the lists or on how the bricks are batched: bit-identical to the rule above.
+ *   svr_mesh_df_bricks:      number of bricks (negative = SVR_E_BADSHAPE).
+ *   svr_mesh_df_workspace_bytes: device workspace of svr_mesh_df_count (negative = SVR_E_BADSHAPE).
+ *   svr_mesh_df_valid_faces: counts the faces that are not skipped; SYNCHRONISES the stream and writes the count to
+ *                            the HOST int64 *n_valid.  ws: 8 device bytes.  F == 0 or no face with area: SVR_E_BADSHAPE.
+ *   svr_mesh_df_count:       the cull sweep: per brick the squared threshold (kept in ws) and the candidate count, then
+ *                            an exclusive scan: offsets (bricks + 1 int64, device) -- offsets[bricks] is the total.
+ *                            With c the centre and r the half diagonal of the points the brick holds, and dmin the
+ *                            smallest sqrt(dd(c, face)): a face is a candidate iff sqrt(dd(c, face)) <= min(dmin, T) +
+ *                            2 r + slack (T only when truncate > 0).  `slack` >= 0 covers the rounding of dd and of this
+ *                            comparison (DESIGN.md section 18 derives the value the Python driver passes).
+ *                            The caller reads offsets back and walks the bricks in batches whose lists fit its buffer.
+ *   svr_mesh_df_emit:        lists of bricks [b0, b1) into list (int32, `capacity` entries: no write goes past it; the
+ *                            caller sizes it offsets[b1] - offsets[b0]); the list of brick b starts at offsets[b] -
+ *                            offsets[b0].  Same tri, lattice, s and ws as the count that filled ws and offsets.
+ *   svr_mesh_df_eval:        field / face (face may be NULL) of bricks [b0, b1) from their lists.  list == NULL: every
+ *                            face is a candidate of every brick (brute force; offsets is not read).
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_mesh_df_bricks(int32_t X, int32_t Y, int32_t Z, int32_t s);
+int64_t svr_mesh_df_workspace_bytes(int32_t X, int32_t Y, int32_t Z, int32_t s);
+int svr_mesh_df_valid_faces(const double *tri, int64_t F, void *ws, int64_t *n_valid, void *stream);
+int svr_mesh_df_count(const double *tri, int64_t F, int32_t X, int32_t Y, int32_t Z, int32_t s, double truncate, double slack,
+                      void *ws, int64_t ws_bytes, int64_t *offsets, void *stream);
+int svr_mesh_df_emit(const double *tri, int64_t F, int32_t X, int32_t Y, int32_t Z, int32_t s, const void *ws,
+                     const int64_t *offsets, int64_t b0, int64_t b1, int32_t *list, int64_t capacity, void *stream);
+int svr_mesh_df_eval(const double *tri, int64_t F, int32_t X, int32_t Y, int32_t Z, int32_t s, double truncate,
+                     const int64_t *offsets, const int32_t *list, int64_t b0, int64_t b1, float *field, int32_t *face,
+                     void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * Host side (plain C++ + zlib; `out` / `payload` are HOST buffers, ideally pinned):
@@ -812,6 +868,10 @@ int svr_iou_counts(const uint8_t *a, const uint8_t *b, int64_t n, int64_t *count
 #define SVR_DT_I64 5
 int svr_df_dims(const char *path, int64_t *dims /*[3]*/);
 int svr_df_read(const char *path, float *payload, int64_t n);
+/* svr_df_write: host only; the inverse of svr_df_dims + svr_df_read: three little-endian uint64 extents, then the X*Y*Z
+ *   float32 values of `payload` (HOST, x fastest).  SVR_E_IO on a failed open or write, SVR_E_BADARG for an extent outside [1, 2^20), the range
+ *   svr_df_dims accepts. */
+int svr_df_write(const char *path, const float *payload, int64_t X, int64_t Y, int64_t Z);
 int svr_npz_member_info(const char *path, const char *member, int32_t *dtype, int32_t *ndim, int64_t *shape /*[8]*/,
                         int32_t *fortran_order);
 int svr_npz_member_read(const char *path, const char *member, void *out, int64_t nbytes);

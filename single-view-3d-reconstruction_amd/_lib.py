@@ -163,6 +163,12 @@ SIGNATURES = {
     "svr_nn_normals_dot": (C.c_int, [P, P, I32, P, I64, I64, P, P]),
     "svr_eval_sums": (C.c_int, [P, P, I64, P, P, I64, P]),
     "svr_iou_counts": (C.c_int, [P, P, I64, P, P]),
+    "svr_mesh_df_bricks": (I64, [I32, I32, I32, I32]),
+    "svr_mesh_df_workspace_bytes": (I64, [I32, I32, I32, I32]),
+    "svr_mesh_df_valid_faces": (C.c_int, [P, I64, P, P, P]),
+    "svr_mesh_df_count": (C.c_int, [P, I64, I32, I32, I32, I32, C.c_double, C.c_double, P, I64, P, P]),
+    "svr_mesh_df_emit": (C.c_int, [P, I64, I32, I32, I32, I32, P, P, I64, I64, P, I64, P]),
+    "svr_mesh_df_eval": (C.c_int, [P, I64, I32, I32, I32, I32, C.c_double, P, P, I64, I64, P, P, P]),
     "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),
@@ -177,6 +183,7 @@ SIGNATURES = {
     "svr_sl_leak_check": (C.c_int, [P, I32, I32, I32, I32, C.c_double, P, P, I64, P, P]),
     "svr_df_dims": (C.c_int, [C.c_char_p, P]),
     "svr_df_read": (C.c_int, [C.c_char_p, P, I64]),
+    "svr_df_write": (C.c_int, [C.c_char_p, P, I64, I64, I64]),
     "svr_npz_member_info": (C.c_int, [C.c_char_p, C.c_char_p, P, P, P, P]),
     "svr_npz_member_read": (C.c_int, [C.c_char_p, C.c_char_p, P, I64]),
     "svr_df_to_grid": (C.c_int, [P, P, I32, I32, I32, P]),

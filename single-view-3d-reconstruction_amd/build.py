@@ -33,6 +33,7 @@ SOURCES = {
     "sparse_lattice.hip": ["-ffp-contract=off"],
     "voxel_mesh.hip": ["-ffp-contract=off"],
     "mesh_eval.hip": ["-ffp-contract=off"],
+    "mesh_df.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "exr_io.cpp": [],
     "raw_sample.hip": ["-ffp-contract=off"],

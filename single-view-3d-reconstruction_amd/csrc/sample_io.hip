@@ -324,6 +324,23 @@ extern "C" int svr_df_read(const char *path, float *payload, int64_t n) {
   return SVR_OK;
 }
 
+extern "C" int svr_df_write(const char *path, const float *payload, int64_t X, int64_t Y, int64_t Z) {
+  SVR_CHECK(path && payload, SVR_E_BADARG, "df_write: null argument");
+  SVR_CHECK(X > 0 && Y > 0 && Z > 0 && X < (1 << 20) && Y < (1 << 20) && Z < (1 << 20), SVR_E_BADARG,
+            "df_write: dims %ld x %ld x %ld (svr_df_dims reads extents in [1, 2^20))", (long)X, (long)Y, (long)Z);
+  FILE *f = fopen(path, "wb");
+  SVR_CHECK(f != nullptr, SVR_E_IO, "df_write: cannot open %s", path);
+  unsigned char h[24];
+  const int64_t dims[3] = {X, Y, Z};
+  for (int a = 0; a < 3; ++a)
+    for (int i = 0; i < 8; ++i) h[8 * a + i] = (unsigned char)((uint64_t)dims[a] >> (8 * i));
+  const size_t n = (size_t)(X * Y * Z);
+  const bool ok = fwrite(h, 1, 24, f) == 24 && fwrite(payload, sizeof(float), n, f) == n;
+  const bool closed = fclose(f) == 0;
+  SVR_CHECK(ok && closed, SVR_E_IO, "df_write: %s: write failed", path);
+  return SVR_OK;
+}
+
 // The host readers never throw across the ABI: std::bad_alloc / std::length_error / std::out_of_range from a malformed file
 // come back as SVR_E_IO (a half-written occupancy_*.npz must not abort the training process).
 namespace {

@@ -37,8 +37,19 @@ def sample_dims(down_scale_factor=1):
     return (round(139 / down_scale_factor), round(104 / down_scale_factor), round(112 / down_scale_factor))
 
 
-def _process_view(sample, out, intrinsic_path, down_scale_factor, sample_num, generator, copy_target):
+def _ensure_distance_field(sample, scene_mesh, down_scale_factor):
+    """`scene_mesh` given and no distance_field.df in the view: compute it from <sample>/<scene_mesh> (grid units of the
+    down_scale_factor's lattice) and write it next to the raw files.  An existing file is not touched."""
+    target = sample / "distance_field.df"
+    if scene_mesh is None or target.exists():
+        return
+    from .mesh_to_df import mesh_to_df          # imports this module for EmptyMeshError / sample_dims
+    mesh_to_df(sample / scene_mesh, target, dims=sample_dims(down_scale_factor))
+
+
+def _process_view(sample, out, intrinsic_path, down_scale_factor, sample_num, generator, copy_target, scene_mesh=None):
     dims = sample_dims(down_scale_factor)
+    _ensure_distance_field(sample, scene_mesh, down_scale_factor)
     distance = sample_io.exr_read(sample / "distance.exr", "R")
     grid, out_of_range = depth_grid(distance, dims, intrinsic_path, down_scale_factor)
     n_out = int(out_of_range.item())
@@ -61,26 +72,42 @@ def _process_view(sample, out, intrinsic_path, down_scale_factor, sample_num, ge
                  grid_coords=grid_coords.cpu().numpy())
 
 
-def process_sample(dataset_path, splitsdir, sample_name, down_scale_factor=1, sample_num=100000, generator=None):
+def process_sample(dataset_path, splitsdir, sample_name, down_scale_factor=1, sample_num=100000, generator=None, scene_mesh=None):
     """raw/<splitsdir>/<sample_name> -> processed/<splitsdir>/<sample_name> (+ mesh.obj next to the raw files).
-    `generator`: a torch.Generator for sample_points' draws."""
+    `generator`: a torch.Generator for sample_points' draws.
+
+    `scene_mesh` (default None: nothing changes): the name of a triangle mesh in the view's directory, e.g. "scene.obj", in
+    grid units of the down_scale_factor's lattice.  A view without distance_field.df gets one computed from it
+    (data_processing.mesh_to_df) and written next to the raw files before the unchanged rest runs; a view that already has
+    the file is not touched.  A mesh without a face that has an area raises EmptyMeshError.  mesh.obj stays what it is
+    today -- the level-1.0 surface of the field -- and is NOT the input mesh, so `scene_mesh` must not be "mesh.obj".
+    The written file has the extents sample_dims(down_scale_factor); the unchanged rest reads it like any
+    distance_field.df, i.e. read_df block-averages it by down_scale_factor once more -- so with a factor other than 1 write
+    the full-resolution field yourself (mesh_to_df with the mesh in full-resolution grid units) instead of using
+    `scene_mesh`."""
+    if scene_mesh == "mesh.obj":
+        raise ValueError("process_sample: scene_mesh must not be mesh.obj, the file this function writes")
     sample = Path(dataset_path) / "raw" / splitsdir / sample_name
     out = Path(dataset_path) / "processed" / splitsdir / sample_name
     out.mkdir(exist_ok=True, parents=True)
-    _process_view(sample, out, sample / "intrinsic.txt", down_scale_factor, sample_num, generator, True)
+    _process_view(sample, out, sample / "intrinsic.txt", down_scale_factor, sample_num, generator, True, scene_mesh)
 
 
-def process_sample_pipeline(dataset_path, splitsdir, down_scale_factor=1, sample_num=100000, generator=None):
+def process_sample_pipeline(dataset_path, splitsdir, down_scale_factor=1, sample_num=100000, generator=None, scene_mesh=None):
     """Every <dataset_path>/<splitsdir>/<scene>/<view>, processed in place with <dataset_path>/intrinsics.txt
     (process_sample.py:32-72; like there, no target.df copy).  A view with out-of-range depth (IndexError) or an empty
-    mesh (AttributeError) is moved to <dataset_path>/quarantine/<splitsdir>/<scene>/<view>.  -> the quarantined paths."""
+    mesh (AttributeError; an empty `scene_mesh` included) is moved to <dataset_path>/quarantine/<splitsdir>/<scene>/<view>.
+    `scene_mesh`: as for process_sample.  -> the quarantined paths."""
+    if scene_mesh == "mesh.obj":
+        raise ValueError("process_sample_pipeline: scene_mesh must not be mesh.obj, the file this function writes")
     d_path = Path(dataset_path) / splitsdir
     quarantined = []
     for scene in sorted(os.listdir(d_path)):
         for view in sorted(os.listdir(d_path / scene)):
             sample = d_path / scene / view
             try:
-                _process_view(sample, sample, Path(dataset_path) / "intrinsics.txt", down_scale_factor, sample_num, generator, False)
+                _process_view(sample, sample, Path(dataset_path) / "intrinsics.txt", down_scale_factor, sample_num, generator, False,
+                              scene_mesh)
             except (IndexError, AttributeError) as e:
                 quarantine = Path(dataset_path) / "quarantine" / splitsdir / scene / view
                 print(f"{type(e).__name__}: {e}; moving {sample} to {quarantine}")

@@ -36,6 +36,26 @@ def df_read_payload(path, out=None):
     return out, (X, Y, Z)
 
 
+def grid_to_df(grid):
+    """(X, Y, Z) array (host, or a device tensor: copied to the host) -> the flat float32 payload of a .df file, x fastest:
+    the inverse of df_to_grid, on the host."""
+    if torch.is_tensor(grid):
+        grid = grid.detach().cpu().numpy()
+    grid = np.asarray(grid, dtype=np.float32)
+    if grid.ndim != 3:
+        raise ValueError(f"grid_to_df: an (X, Y, Z) array, got shape {grid.shape}")
+    return np.ascontiguousarray(grid.reshape(-1, order="F"))
+
+
+def df_write(path, grid):
+    """Write a host or device (X, Y, Z) array as a .df file: three little-endian uint64 extents, then the float32 values
+    with x fastest (what df_dims / df_read_payload parse).  Raises on a failed open or write."""
+    payload = grid_to_df(grid)
+    X, Y, Z = grid.shape
+    check(_lib.lib().svr_df_write(_path(path), payload.ctypes.data_as(C.c_void_p), X, Y, Z), "df_write")
+    return path
+
+
 def npz_member_info(path, member):
     dt, nd, fo = C.c_int32(), C.c_int32(), C.c_int32()
     shape = (C.c_int64 * 8)()
