@@ -450,25 +450,30 @@ int svr_conv3d_k3_variant(int32_t op, int32_t B, int32_t D, int32_t H, int32_t W
 int64_t svr_bn_stats_workspace(int64_t rows, int32_t C);
 int svr_bn_stats(const float *x, double *stats, int64_t rows /*B*D*H*W*/, int32_t C,
                  void *workspace, void *stream);
-/* svr_bn_stats followed by svr_bn_finalize(training = 1) in two launches instead of three (stats may be NULL).      */
+/* svr_bn_stats followed by svr_bn_finalize(training = 1) in two launches instead of three (stats may be NULL).
+ * mean_lo (C floats, may be NULL): mean - mean_f32, so that mean_f32 + mean_lo is the mean to ~2^-48; the backward
+ * centres x with both (svr_bn_bwd_*), which keeps xhat accurate where |mean| >> std.                                */
 int svr_bn_stats_finalize(const float *x, double *stats, const float *gamma, const float *beta, float *running_mean,
-                          float *running_var, float *scale_shift, float *mean_f32, int64_t rows, int32_t C,
-                          float eps, float momentum, void *workspace, void *stream);
+                          float *running_var, float *scale_shift, float *mean_f32, float *mean_lo, int64_t rows,
+                          int32_t C, float eps, float momentum, void *workspace, void *stream);
 /* The same from per-workgroup partial sums part[blocks][2][C] (float64 sum / sum of squares of the BatchNorm's input, left by
  * svr_conv3d_k3_fwd_f16x3_stats): no pass over the tensor at all.                                                   */
 int svr_bn_finalize_parts(const double *part, int32_t blocks, double *stats, const float *gamma, const float *beta,
-                          float *running_mean, float *running_var, float *scale_shift, float *mean_f32, int64_t rows,
-                          int32_t C, float eps, float momentum, void *stream);
+                          float *running_mean, float *running_var, float *scale_shift, float *mean_f32, float *mean_lo,
+                          int64_t rows, int32_t C, float eps, float momentum, void *stream);
 /* scale_shift[0:C] = gamma*invstd, [C:2C] = beta - mean*gamma*invstd, [2C:3C] = invstd (f32);
  * training != 0 also updates running_mean/var (momentum, unbiased var) like torch.          */
 int svr_bn_finalize(const double *stats, const float *gamma, const float *beta, float *running_mean,
                     float *running_var, float *scale_shift, float *mean_f32, int64_t rows,
                     int32_t C, float eps, float momentum, int training, void *stream);
 /* y = x*scale + shift (full resolution);  pooled (B,D/2,H/2,W/2,C) = 2x2x2 max of y (floor),
- * argmax (uint8 0..7, first maximum in z,y,x scan order) -- pooled/argmax may be NULL.      */
-int svr_bn_apply_pool(const float *x, const float *scale_shift, float *y, float *pooled,
-                      uint8_t *argmax, int32_t B, int32_t D, int32_t H, int32_t W, int32_t C,
-                      void *stream);
+ * argmax (uint8 0..7, first maximum in z,y,x scan order) -- pooled/argmax may be NULL.
+ * With mean_f32 (else NULL, and mean_lo / beta NULL too): y = ((x - mean_f32) - mean_lo)*scale + beta (mean_lo, beta may
+ * be NULL = 0), which has no f32 shift of the size of mean*scale in it: accurate where |mean| >> std, y = beta exactly
+ * on a constant channel.                                                                      */
+int svr_bn_apply_pool(const float *x, const float *scale_shift, const float *mean_f32, const float *mean_lo,
+                      const float *beta, float *y, float *pooled, uint8_t *argmax, int32_t B, int32_t D, int32_t H,
+                      int32_t W, int32_t C, void *stream);
 /* Backward of [ReLU ->] BN -> {sample, pool}:
  *   dy_total = dy (may be NULL = 0) + unpool(dpooled via argmax) (dpooled may be NULL)
  *   sums[0:C] = sum dy_total, sums[C:2C] = sum dy_total*xhat   (float64, step 1)
@@ -476,12 +481,13 @@ int svr_bn_apply_pool(const float *x, const float *scale_shift, float *y, float 
  *   dgamma = sum2, dbeta = sum1.
  * relu_mask bit 1 (value 2): the forward used FROZEN statistics (eval mode, running mean / var from
  * svr_bn_finalize(training = 0)): autograd of F.batch_norm(training=False) is dx = gamma*invstd*dy_total;
- * dgamma / dbeta are the same sums.                                                          */
+ * dgamma / dbeta are the same sums.
+ * xhat = ((x - mean_f32) - mean_lo) * invstd; mean_lo may be NULL (= 0: the forward left none).   */
 int svr_bn_bwd_reduce(const float *x, const float *dy, const float *dpooled, const uint8_t *argmax,
-                      const float *mean_f32, const float *scale_shift, double *sums, int32_t B,
+                      const float *mean_f32, const float *mean_lo, const float *scale_shift, double *sums, int32_t B,
                       int32_t D, int32_t H, int32_t W, int32_t C, void *workspace, void *stream);
 int svr_bn_bwd_apply(const float *x, const float *dy, const float *dpooled, const uint8_t *argmax,
-                     const float *mean_f32, const float *scale_shift, const float *gamma,
+                     const float *mean_f32, const float *mean_lo, const float *scale_shift, const float *gamma,
                      const double *sums, float *dx, float *dgamma, float *dbeta, int32_t B,
                      int32_t D, int32_t H, int32_t W, int32_t C, int relu_mask, uint32_t *amax_dx,
                      void *stream);   /* amax_dx (may be NULL; 0 on entry): bit pattern of max |dx|, as svr_fc_out_bwd's */

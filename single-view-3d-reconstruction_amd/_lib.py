@@ -126,12 +126,12 @@ SIGNATURES = {
     "svr_conv3d_k3_variant": (C.c_int, [I32, I32, I32, I32, I32, I32, I32, P, P, P, P, P]),
     "svr_bn_stats_workspace": (I64, [I64, I32]),
     "svr_bn_stats": (C.c_int, [P, P, I64, I32, P, P]),
-    "svr_bn_stats_finalize": (C.c_int, [P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, P]),
-    "svr_bn_finalize_parts": (C.c_int, [P, I32, P, P, P, P, P, P, P, I64, I32, F32, F32, P]),
+    "svr_bn_stats_finalize": (C.c_int, [P, P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, P]),
+    "svr_bn_finalize_parts": (C.c_int, [P, I32, P, P, P, P, P, P, P, P, I64, I32, F32, F32, P]),
     "svr_bn_finalize": (C.c_int, [P, P, P, P, P, P, P, I64, I32, F32, F32, C.c_int, P]),
-    "svr_bn_apply_pool": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, P]),
-    "svr_bn_bwd_reduce": (C.c_int, [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P]),
-    "svr_bn_bwd_apply": (C.c_int, [P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, C.c_int, P, P]),
+    "svr_bn_apply_pool": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P]),
+    "svr_bn_bwd_reduce": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P]),
+    "svr_bn_bwd_apply": (C.c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, C.c_int, P, P]),
     "svr_stage1_supported": (I32, [I32, I32, I32, I32, I32]),
     "svr_stage1_workspace": (I64, [I32, I32, I32, I32]),
     "svr_stage1_fwd": (C.c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, C.c_int, C.c_int, P, P]),

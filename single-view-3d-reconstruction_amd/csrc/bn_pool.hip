@@ -7,8 +7,14 @@
 // argmax; the backward merges {gather gradient, un-pooled gradient} -> BN backward -> ReLU mask.
 //
 // Bandwidth bound (HBM): every element is read once / written once per pass, float4 per lane.
-// Statistics are accumulated in short f32 runs and carried in f64 (torch's CPU kernel uses a
-// double accumulator for float input), so mean / variance are good to ~1e-7 relative.
+// Statistics are sums of x - p and (x - p)^2 with the pivot p = the channel's value in row 0, accumulated in short f32
+// runs and carried in f64; mean = p + s/n, var = ss/n - (s/n)^2.  The pivot takes the channel's mean out of the squares,
+// so the variance does not lose (mean/std)^2 * 2^-24 to cancellation: measured against float64 on channels with
+// |mean/std| up to 1000 and 2 .. 4096 rows, the variance is within 1.3e-7 and invstd within 8e-8 relative (stock f32
+// batch norm on the CPU: 1.0e-7 and 6.5e-8; sums of x and x^2 lost up to 2.5e-1; table in tests/test_gpu_bn_paths.py),
+// and a constant channel gets var = 0 exactly.  Where the statistics come from this pass, the apply and the backward
+// centre x with the mean as two floats (mean_f32 + mean_lo), so y and xhat keep f32 accuracy where |mean| >> std.
+// Partial sums from a convolution's epilogue (after a ReLU: |mean/std| ~ 1) are plain sums of x and x^2.
 #include "common.h"
 
 using namespace svr;
@@ -19,12 +25,14 @@ constexpr int STAT_BLOCKS_MAX = 2048;
 
 // ---------------------------------------------------------------- statistics
 // thread -> (row lane r = tid / Q, quad q = tid % Q); rows strided by 256/Q.
-__global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float *__restrict__ x, double *__restrict__ part,
-                                                               int64_t rows, int C, int64_t rows_per_block) {
+// (6 waves per SIMD, i.e. <= 80 VGPRs, as before the pivot: left alone the compiler takes 82 for it and drops to 5)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void bn_stats_partial_kernel(
+    const float *__restrict__ x, double *__restrict__ part, int64_t rows, int C, int64_t rows_per_block) {
   const int Q = C / 4;
   const int q = threadIdx.x % Q, rl = threadIdx.x / Q, RL = 256 / Q;
   int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
   double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+  const float4 pv = *reinterpret_cast<const float4 *>(x + q * 4);   // pivot: row 0 (the same for every block)
   int64_t r = r0 + rl;
   while (r < r1) {
     float fs[4] = {0, 0, 0, 0}, fss[4] = {0, 0, 0, 0};
@@ -42,8 +50,9 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float *__re
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         if (r + (int64_t)i * RL < r1) {
-          fs[0] += v[i].x; fs[1] += v[i].y; fs[2] += v[i].z; fs[3] += v[i].w;
-          fss[0] += v[i].x * v[i].x; fss[1] += v[i].y * v[i].y; fss[2] += v[i].z * v[i].z; fss[3] += v[i].w * v[i].w;
+          const float d[4] = {v[i].x - pv.x, v[i].y - pv.y, v[i].z - pv.z, v[i].w - pv.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { fs[j] += d[j]; fss[j] += d[j] * d[j]; }
         }
       }
       r += 8 * (int64_t)RL;
@@ -67,11 +76,12 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float *__re
 }
 
 // what svr_bn_finalize computes for one channel from (mean, biased variance): running statistics (training), scale / shift /
-// invstd, the f32 mean
+// invstd, the f32 mean (and, with mean_lo, what the f32 mean leaves of it: mean = mean_f32 + mean_lo to ~2^-48)
 struct BnFinalize {
   const float *gamma, *beta;
   float *rmean, *rvar, *ss, *mean_f32;   // ss == nullptr: nothing to finalize
   float eps, momentum;
+  float *mean_lo;                        // may be nullptr
 };
 __device__ __forceinline__ void bn_finalize_channel(const BnFinalize &f, int c, int C, double mean, double var, int64_t rows,
                                                     int training) {
@@ -89,12 +99,15 @@ __device__ __forceinline__ void bn_finalize_channel(const BnFinalize &f, int c, 
   f.ss[C + c] = b - (float)mean * scale;
   f.ss[2 * C + c] = (float)invstd;
   f.mean_f32[c] = (float)mean;
+  if (f.mean_lo) f.mean_lo[c] = (float)(mean - (double)(float)mean);
 }
 
 // one workgroup per channel: f64 tree over the block partials (fixed order); with fin.ss the same thread also does
-// svr_bn_finalize's work for its channel (training mode), one launch instead of two
-__global__ __launch_bounds__(256) void bn_stats_final_kernel(const double *__restrict__ part, double *__restrict__ stats,
-                                                             int64_t rows, int C, int blocks, BnFinalize fin) {
+// svr_bn_finalize's work for its channel (training mode), one launch instead of two.  pivot (may be nullptr = 0): the
+// partials are sums of x - pivot[c] and (x - pivot[c])^2 (bn_stats_partial_kernel; the epilogue producers sum x and x^2)
+__global__ __launch_bounds__(256) void bn_stats_final_kernel(const double *__restrict__ part, const float *__restrict__ pivot,
+                                                             double *__restrict__ stats, int64_t rows, int C, int blocks,
+                                                             BnFinalize fin) {
   const int c = blockIdx.x;
   double s = 0, ss = 0;
   for (int b = threadIdx.x; b < blocks; b += 256) { s += part[(int64_t)b * 2 * C + c]; ss += part[(int64_t)b * 2 * C + C + c]; }
@@ -109,6 +122,7 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const double *__res
     double mean = r1[0] / (double)rows;
     double var = r2[0] / (double)rows - mean * mean;
     var = var > 0 ? var : 0;
+    if (pivot) mean += (double)pivot[c];
     if (stats) { stats[c] = mean; stats[C + c] = var; }
     if (fin.ss) bn_finalize_channel(fin, c, C, mean, var, rows, 1);
   }
@@ -133,10 +147,18 @@ struct Vol {
   int B, D, H, W, C;
 };
 
+// CENTRED: y = ((x - mean_f32) - mean_lo) * scale + beta instead of x * scale + shift.  shift = beta - mean * scale is an
+// f32 of the size of mean * scale, so the scale / shift form errs by |mean/std| * 2^-24 in y (and does not give y = beta on
+// a constant channel); the centred form cancels the mean before anything is rounded.
+struct BnCentre {
+  const float *mean, *mean_lo, *beta;   // mean_lo, beta may be nullptr (= 0)
+};
+
 // one thread = one 2x2x2 cell (ceil-div grid, so odd trailing voxels are still normalised) x 4 channels
+template <bool CENTRED>
 __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const float *__restrict__ x, const float *__restrict__ ss,
                                                             float *__restrict__ y, float *__restrict__ pooled,
-                                                            uint8_t *__restrict__ argmax, Vol v, int64_t total) {
+                                                            uint8_t *__restrict__ argmax, Vol v, int64_t total, BnCentre ctr) {
   int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= total) return;
   const int Q = v.C / 4;
@@ -152,7 +174,15 @@ __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const float *__restr
   int cz = (int)(cell % (uint32_t)Dc);
   int64_t b = cell / (uint32_t)Dc;
   float4 sc = *reinterpret_cast<const float4 *>(ss + q * 4);
-  float4 sh = *reinterpret_cast<const float4 *>(ss + v.C + q * 4);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 sh = zero4, mu = zero4, ml = zero4;
+  if (CENTRED) {   // sh = beta
+    mu = *reinterpret_cast<const float4 *>(ctr.mean + q * 4);
+    if (ctr.mean_lo) ml = *reinterpret_cast<const float4 *>(ctr.mean_lo + q * 4);
+    if (ctr.beta) sh = *reinterpret_cast<const float4 *>(ctr.beta + q * 4);
+  } else {
+    sh = *reinterpret_cast<const float4 *>(ss + v.C + q * 4);
+  }
   float4 best = make_float4(0.f, 0.f, 0.f, 0.f);
   int am[4] = {0, 0, 0, 0};
   bool first = true;
@@ -176,7 +206,8 @@ __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const float *__restr
     int z = cz * 2 + (k >> 2), yy = cy * 2 + ((k >> 1) & 1), xx = cx * 2 + (k & 1);
     if (z < v.D && yy < v.H && xx < v.W) {
       const int64_t off = off8[k];
-      const float4 a = in8[k];
+      float4 a = in8[k];
+      if (CENTRED) { a.x = (a.x - mu.x) - ml.x; a.y = (a.y - mu.y) - ml.y; a.z = (a.z - mu.z) - ml.z; a.w = (a.w - mu.w) - ml.w; }
       float4 o;
       o.x = a.x * sc.x + sh.x; o.y = a.y * sc.y + sh.y; o.z = a.z * sc.z + sh.z; o.w = a.w * sc.w + sh.w;
       *reinterpret_cast<float4 *>(y + off) = o;
@@ -203,7 +234,8 @@ template <bool APPLY>
 __global__ __launch_bounds__(256) void bn_bwd_kernel(const float *__restrict__ x, const float *__restrict__ dy,
                                                      const float *__restrict__ dpooled,
                                                      const uint8_t *__restrict__ argmax,
-                                                     const float *__restrict__ mean, const float *__restrict__ ss,
+                                                     const float *__restrict__ mean, const float *__restrict__ mean_lo,
+                                                     const float *__restrict__ ss,
                                                      const double *__restrict__ sums, double *__restrict__ part,
                                                      float *__restrict__ dx, Vol v, int64_t cells, int relu_mask,
                                                      float *__restrict__ dgamma, float *__restrict__ dbeta,
@@ -219,6 +251,9 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const float *__restrict__ x
   const int Dp = v.D / 2, Hp = v.H / 2, Wp = v.W / 2;
   const double n = (double)v.B * v.D * v.H * v.W;
   float4 mu = *reinterpret_cast<const float4 *>(mean + q * 4);
+  // x - mean as (x - mean_f32) - mean_lo: the first difference is exact where it cancels, so xhat does not inherit the
+  // f32 mean's rounding (|mean| * 2^-24, which is 1e-5 of the std at |mean/std| = 100)
+  float4 ml = mean_lo ? *reinterpret_cast<const float4 *>(mean_lo + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
   float4 sc = *reinterpret_cast<const float4 *>(ss + q * 4);          // gamma*invstd
   float4 is = *reinterpret_cast<const float4 *>(ss + 2 * v.C + q * 4);  // invstd
   float m1[4] = {0, 0, 0, 0}, m2[4] = {0, 0, 0, 0};
@@ -276,7 +311,8 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const float *__restrict__ x
         if (((am >> 8) & 0xff) == (uint32_t)k) g.y += dp.y;
         if (((am >> 16) & 0xff) == (uint32_t)k) g.z += dp.z;
         if (((am >> 24) & 0xff) == (uint32_t)k) g.w += dp.w;
-        float xh[4] = {(a.x - mu.x) * is.x, (a.y - mu.y) * is.y, (a.z - mu.z) * is.z, (a.w - mu.w) * is.w};
+        float xh[4] = {((a.x - mu.x) - ml.x) * is.x, ((a.y - mu.y) - ml.y) * is.y, ((a.z - mu.z) - ml.z) * is.z,
+                       ((a.w - mu.w) - ml.w) * is.w};
         float gg[4] = {g.x, g.y, g.z, g.w};
         if (APPLY) {
           float av[4] = {a.x, a.y, a.z, a.w};
@@ -360,14 +396,15 @@ int bwd_blocks(int64_t cells, int C) {
 namespace svr {
 // mean / biased variance from per-block partial sums [blocks][2C] (f64): shared with conv3d.hip's fused conv_in forward
 void bn_stats_final_launch(const double *part, double *stats, int64_t rows, int C, int blocks, hipStream_t s) {
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, s, part, stats, rows, C, blocks, BnFinalize{});
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, s, part, (const float *)nullptr, stats, rows, C, blocks,
+                     BnFinalize{});
 }
 // ... the same + svr_bn_finalize(training = 1) in ONE launch (stats may be null): shared with stage1.hip
 void bn_stats_finalize_launch(const double *part, double *stats, int64_t rows, int C, int blocks, const float *gamma,
                               const float *beta, float *rmean, float *rvar, float *ss, float *mean_f32, float eps, float momentum,
                               hipStream_t s) {
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, s, part, stats, rows, C, blocks,
-                     BnFinalize{gamma, beta, rmean, rvar, ss, mean_f32, eps, momentum});
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, s, part, (const float *)nullptr, stats, rows, C, blocks,
+                     BnFinalize{gamma, beta, rmean, rvar, ss, mean_f32, eps, momentum, nullptr});
 }
 // out[c] = ordered f64 sum over `blocks` partial rows [blocks][cols]: shared with stage1.hip's backward reduction
 void bn_sum_parts_launch(const double *part, double *out, int cols, int blocks, hipStream_t s) {
@@ -387,33 +424,34 @@ extern "C" int svr_bn_stats(const float *x, double *stats, int64_t rows, int32_t
   int64_t rpb;
   int blocks = stats_blocks(rows, &rpb);
   hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(blocks), dim3(256), 0, s, x, (double *)workspace, rows, C, rpb);
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, s, (const double *)workspace, stats, rows, C, blocks, BnFinalize{});
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, s, (const double *)workspace, x, stats, rows, C, blocks,
+                     BnFinalize{});
   return launch_status("bn_stats");
 }
 
 // svr_bn_stats + svr_bn_finalize(training = 1) as two launches instead of three (the per-channel tree also finalizes)
 extern "C" int svr_bn_stats_finalize(const float *x, double *stats, const float *gamma, const float *beta, float *running_mean,
-                                     float *running_var, float *scale_shift, float *mean_f32, int64_t rows, int32_t C, float eps,
-                                     float momentum, void *workspace, void *stream) {
+                                     float *running_var, float *scale_shift, float *mean_f32, float *mean_lo, int64_t rows,
+                                     int32_t C, float eps, float momentum, void *workspace, void *stream) {
   if (int rc = check_c(C)) return rc;
   SVR_CHECK(x && scale_shift && mean_f32 && workspace && rows > 0, SVR_E_BADARG, "bn_stats_finalize: bad argument");
   hipStream_t s = (hipStream_t)stream;
   int64_t rpb;
   int blocks = stats_blocks(rows, &rpb);
   hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(blocks), dim3(256), 0, s, x, (double *)workspace, rows, C, rpb);
-  bn_stats_finalize_launch((const double *)workspace, stats, rows, C, blocks, gamma, beta, running_mean, running_var, scale_shift,
-                           mean_f32, eps, momentum, s);
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, s, (const double *)workspace, x, stats, rows, C, blocks,
+                     BnFinalize{gamma, beta, running_mean, running_var, scale_shift, mean_f32, eps, momentum, mean_lo});
   return launch_status("bn_stats_finalize");
 }
 
 // Finalize from per-workgroup partial sums part[blocks][2][C] (sum, sum of squares; what svr_conv3d_k3_fwd_f16x3_stats and
 // svr_conv3d_c1_fwd_stats' kernels leave): mean / biased variance (stats, may be NULL) + svr_bn_finalize(training = 1), one launch.
 extern "C" int svr_bn_finalize_parts(const double *part, int32_t blocks, double *stats, const float *gamma, const float *beta,
-                                     float *running_mean, float *running_var, float *scale_shift, float *mean_f32, int64_t rows,
-                                     int32_t C, float eps, float momentum, void *stream) {
+                                     float *running_mean, float *running_var, float *scale_shift, float *mean_f32, float *mean_lo,
+                                     int64_t rows, int32_t C, float eps, float momentum, void *stream) {
   SVR_CHECK(part && blocks > 0 && scale_shift && mean_f32 && rows > 0 && C > 0, SVR_E_BADARG, "bn_finalize_parts: bad argument");
-  bn_stats_finalize_launch(part, stats, rows, C, blocks, gamma, beta, running_mean, running_var, scale_shift, mean_f32, eps, momentum,
-                           (hipStream_t)stream);
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, part, (const float *)nullptr, stats, rows, C,
+                     blocks, BnFinalize{gamma, beta, running_mean, running_var, scale_shift, mean_f32, eps, momentum, mean_lo});
   return launch_status("bn_finalize_parts");
 }
 
@@ -422,26 +460,34 @@ extern "C" int svr_bn_finalize(const double *stats, const float *gamma, const fl
                                float momentum, int training, void *stream) {
   SVR_CHECK(scale_shift && mean_f32 && (training ? stats != nullptr : (running_mean && running_var)), SVR_E_BADARG, "bn_finalize: bad argument");
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, stats,
-                     BnFinalize{gamma, beta, running_mean, running_var, scale_shift, mean_f32, eps, momentum}, rows, C, training);
+                     BnFinalize{gamma, beta, running_mean, running_var, scale_shift, mean_f32, eps, momentum, nullptr}, rows, C,
+                     training);
   return launch_status("bn_finalize");
 }
 
-extern "C" int svr_bn_apply_pool(const float *x, const float *scale_shift, float *y, float *pooled, uint8_t *argmax,
-                                 int32_t B, int32_t D, int32_t H, int32_t W, int32_t C, void *stream) {
+extern "C" int svr_bn_apply_pool(const float *x, const float *scale_shift, const float *mean_f32, const float *mean_lo,
+                                 const float *beta, float *y, float *pooled, uint8_t *argmax, int32_t B, int32_t D, int32_t H,
+                                 int32_t W, int32_t C, void *stream) {
   if (int rc = check_c(C)) return rc;
   SVR_CHECK(x && scale_shift && y, SVR_E_BADARG, "bn_apply_pool: null pointer");
+  SVR_CHECK(mean_f32 || (!mean_lo && !beta), SVR_E_BADARG, "bn_apply_pool: mean_lo / beta need mean_f32");
   Vol v{B, D, H, W, C};
   int64_t total = (int64_t)B * ((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
   if (total == 0) return SVR_OK;
   SVR_CHECK(total < (1LL << 32), SVR_E_UNSUPPORTED, "bn_apply_pool: %ld work items (32-bit index arithmetic)", (long)total);
-  hipLaunchKernelGGL(bn_apply_pool_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     scale_shift, y, pooled, argmax, v, total);
+  const dim3 grid((unsigned)cdiv(total, 256));
+  if (mean_f32)
+    hipLaunchKernelGGL(bn_apply_pool_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, scale_shift, y, pooled, argmax, v,
+                       total, BnCentre{mean_f32, mean_lo, beta});
+  else
+    hipLaunchKernelGGL(bn_apply_pool_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, scale_shift, y, pooled, argmax, v,
+                       total, BnCentre{});
   return launch_status("bn_apply_pool");
 }
 
 extern "C" int svr_bn_bwd_reduce(const float *x, const float *dy, const float *dpooled, const uint8_t *argmax,
-                                 const float *mean_f32, const float *scale_shift, double *sums, int32_t B, int32_t D,
-                                 int32_t H, int32_t W, int32_t C, void *workspace, void *stream) {
+                                 const float *mean_f32, const float *mean_lo, const float *scale_shift, double *sums, int32_t B,
+                                 int32_t D, int32_t H, int32_t W, int32_t C, void *workspace, void *stream) {
   if (int rc = check_c(C)) return rc;
   SVR_CHECK(x && mean_f32 && scale_shift && sums && workspace, SVR_E_BADARG, "bn_bwd_reduce: null pointer");
   SVR_CHECK(!dpooled || argmax, SVR_E_BADARG, "bn_bwd_reduce: dpooled needs argmax");
@@ -450,7 +496,7 @@ extern "C" int svr_bn_bwd_reduce(const float *x, const float *dy, const float *d
   int64_t cells = (int64_t)B * ((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2);
   SVR_CHECK(cells < (1LL << 32), SVR_E_UNSUPPORTED, "bn_bwd: %ld cells (32-bit index arithmetic)", (long)cells);
   int blocks = bwd_blocks(cells, C);
-  hipLaunchKernelGGL(bn_bwd_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, dpooled, argmax, mean_f32, scale_shift,
+  hipLaunchKernelGGL(bn_bwd_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, dpooled, argmax, mean_f32, mean_lo, scale_shift,
                      (const double *)nullptr, (double *)workspace, (float *)nullptr, v, cells, 0, (float *)nullptr, (float *)nullptr,
                      (uint32_t *)nullptr);
   hipLaunchKernelGGL(sum_parts_kernel, dim3(2 * C), dim3(256), 0, s, (const double *)workspace, sums, 2 * C, blocks);
@@ -458,9 +504,9 @@ extern "C" int svr_bn_bwd_reduce(const float *x, const float *dy, const float *d
 }
 
 extern "C" int svr_bn_bwd_apply(const float *x, const float *dy, const float *dpooled, const uint8_t *argmax,
-                                const float *mean_f32, const float *scale_shift, const float *gamma, const double *sums,
-                                float *dx, float *dgamma, float *dbeta, int32_t B, int32_t D, int32_t H, int32_t W,
-                                int32_t C, int relu_mask, uint32_t *amax_dx, void *stream) {
+                                const float *mean_f32, const float *mean_lo, const float *scale_shift, const float *gamma,
+                                const double *sums, float *dx, float *dgamma, float *dbeta, int32_t B, int32_t D, int32_t H,
+                                int32_t W, int32_t C, int relu_mask, uint32_t *amax_dx, void *stream) {
   (void)gamma;
   if (int rc = check_c(C)) return rc;
   SVR_CHECK(x && mean_f32 && scale_shift && sums && dx, SVR_E_BADARG, "bn_bwd_apply: null pointer");
@@ -472,7 +518,7 @@ extern "C" int svr_bn_bwd_apply(const float *x, const float *dy, const float *dp
   int CL = 256 / (C / 4);
   int64_t blocks = cdiv(cells, CL);
   if (blocks > 65535 * 16) blocks = 65535 * 16;
-  hipLaunchKernelGGL(bn_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, dy, dpooled, argmax, mean_f32,
+  hipLaunchKernelGGL(bn_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, dy, dpooled, argmax, mean_f32, mean_lo,
                      scale_shift, sums, (double *)nullptr, dx, v, cells, relu_mask, dgamma, dbeta, amax_dx);
   return launch_status("bn_bwd_apply");
 }

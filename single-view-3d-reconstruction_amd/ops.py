@@ -1103,8 +1103,10 @@ def conv3d_k3_bwd_weight(x, dout, want_bias=True, mode=None, param_layout=False)
 
 
 def bn_forward(x, gamma, beta, running_mean, running_var, training, eps=1e-5, momentum=0.1, want_pool=True, stats=None):
-    """x (B,D,H,W,C) -> y, pooled, argmax, scale_shift(3C), mean(C).  `stats` (float64 [mean | biased var]): statistics
-    of x already computed by the producer (conv3d_c1_fwd_stats); the statistics pass over x is then skipped."""
+    """x (B,D,H,W,C) -> y, pooled, argmax, scale_shift(3C), mean.  `stats` (float64 [mean | biased var]): statistics
+    of x already computed by the producer (conv3d_c1_fwd_stats); the statistics pass over x is then skipped.
+    mean (for bn_backward): the f32 mean (C), and behind it, where the statistics were taken from x here, what the
+    rounding to f32 left (2C in all): the backward centres x with both, so xhat stays accurate where |mean| >> std."""
     _f32(x, gamma, beta, running_mean, running_var)
     B, D, H, W, Cc = x.shape
     rows = B * D * H * W
@@ -1115,14 +1117,17 @@ def bn_forward(x, gamma, beta, running_mean, running_var, training, eps=1e-5, mo
     l = _lib.lib()
     dev = x.device
     ss = torch.empty(3 * Cc, device=dev, dtype=torch.float32)
-    mean = torch.empty(Cc, device=dev, dtype=torch.float32)
+    own_stats = training and stats is None
+    mean = torch.empty(2 * Cc if own_stats else Cc, device=dev, dtype=torch.float32)
+    mean_lo = C.c_void_p(mean.data_ptr() + 4 * Cc) if own_stats else C.c_void_p(0)      # (no view: host time per layer)
     if training and isinstance(stats, StatParts):      # partial sums from the producing kernel's epilogue: one launch
         check(l.svr_bn_finalize_parts(_p(stats.part), stats.blocks, C.c_void_p(0), _p(gamma), _p(beta), _p(running_mean),
-                                      _p(running_var), _p(ss), _p(mean), rows, Cc, eps, momentum, _stream()), "bn_finalize_parts")
-    elif training and stats is None:      # statistics + finalize: two launches
+                                      _p(running_var), _p(ss), _p(mean), C.c_void_p(0), rows, Cc, eps, momentum, _stream()),
+              "bn_finalize_parts")
+    elif own_stats:                       # statistics + finalize: two launches
         ws = torch.empty(l.svr_bn_stats_workspace(rows, Cc), device=dev, dtype=torch.uint8)
         check(l.svr_bn_stats_finalize(_p(x), C.c_void_p(0), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(ss), _p(mean),
-                                      rows, Cc, eps, momentum, _p(ws), _stream()), "bn_stats_finalize")
+                                      mean_lo, rows, Cc, eps, momentum, _p(ws), _stream()), "bn_stats_finalize")
     else:
         check(l.svr_bn_finalize(_p(stats if training else None), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(ss),
                                 _p(mean), rows, Cc, eps, momentum, int(training), _stream()), "bn_finalize")
@@ -1131,7 +1136,9 @@ def bn_forward(x, gamma, beta, running_mean, running_var, training, eps=1e-5, mo
     if want_pool:
         pooled = torch.empty(B, D // 2, H // 2, W // 2, Cc, device=dev, dtype=torch.float32)
         argmax = torch.empty(B, D // 2, H // 2, W // 2, Cc, device=dev, dtype=torch.uint8)
-    check(l.svr_bn_apply_pool(_p(x), _p(ss), _p(y), _p(pooled), _p(argmax), B, D, H, W, Cc, _stream()), "bn_apply_pool")
+    # statistics taken from x here (any mean: the UNet's BatchNorm follows a convolution, not a ReLU): the centred apply
+    check(l.svr_bn_apply_pool(_p(x), _p(ss), _p(mean if own_stats else None), mean_lo, _p(beta if own_stats else None), _p(y),
+                              _p(pooled), _p(argmax), B, D, H, W, Cc, _stream()), "bn_apply_pool")
     return y, pooled, argmax, ss, mean
 
 
@@ -1144,13 +1151,16 @@ def bn_backward(x, dy, dpooled, argmax, mean, ss, relu_mask=True, training=True)
     dev = x.device
     sums = torch.empty(2 * Cc, device=dev, dtype=torch.float64)
     ws = torch.empty(l.svr_bn_stats_workspace(B * D * H * W, Cc), device=dev, dtype=torch.uint8)
-    check(l.svr_bn_bwd_reduce(_p(x), _p(dy), _p(dpooled), _p(argmax), _p(mean), _p(ss), _p(sums), B, D, H, W, Cc, _p(ws),
+    if mean.numel() not in (Cc, 2 * Cc):
+        raise ValueError(f"bn_backward: mean has {mean.numel()} elements for {Cc} channels")
+    mean_lo = C.c_void_p(mean.data_ptr() + 4 * Cc if mean.numel() == 2 * Cc else 0)
+    check(l.svr_bn_bwd_reduce(_p(x), _p(dy), _p(dpooled), _p(argmax), _p(mean), mean_lo, _p(ss), _p(sums), B, D, H, W, Cc, _p(ws),
                               _stream()), "bn_bwd_reduce")
     dx = torch.empty_like(x)
     dgamma = torch.empty(Cc, device=dev, dtype=torch.float32)
     dbeta = torch.empty(Cc, device=dev, dtype=torch.float32)
     amax = amax_slot(dev) if "f16x3s" in (BACKWARD_CONV, BACKWARD_CONV_WEIGHT, BACKWARD_GEMM) else None
-    check(l.svr_bn_bwd_apply(_p(x), _p(dy), _p(dpooled), _p(argmax), _p(mean), _p(ss), C.c_void_p(0), _p(sums), _p(dx),
+    check(l.svr_bn_bwd_apply(_p(x), _p(dy), _p(dpooled), _p(argmax), _p(mean), mean_lo, _p(ss), C.c_void_p(0), _p(sums), _p(dx),
                              _p(dgamma), _p(dbeta), B, D, H, W, Cc, int(relu_mask) | (0 if training else 2), _p(amax), _stream()),
           "bn_bwd_apply")
     if amax is not None:
