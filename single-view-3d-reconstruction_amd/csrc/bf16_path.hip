@@ -12,22 +12,12 @@
 // Build with -ffp-contract=off (gather_common.h).
 #include "common.h"
 #include "gather_common.h"
+#include "f16x3.h"
 
 using namespace svr;
 
 namespace {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float bf_lo(uint32_t p) { return __uint_as_float(p << 16); }          // element 0 of a pair
-__device__ __forceinline__ float bf_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }  // element 1
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {  // round to nearest even (v_cvt_pk_bf16_f32), NaN safe
-  f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
 __device__ __forceinline__ uint16_t to_bf16(float a) { return (uint16_t)(pack_bf16(a, 0.f) & 0xffffu); }
 
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int64_t n) {

@@ -16,6 +16,7 @@
 // centre x with the mean as two floats (mean_f32 + mean_lo), so y and xhat keep f32 accuracy where |mean| >> std.
 // Partial sums from a convolution's epilogue (after a ReLU: |mean/std| ~ 1) are plain sums of x and x^2.
 #include "common.h"
+#include "reduce.h"
 
 using namespace svr;
 
@@ -362,12 +363,7 @@ __global__ __launch_bounds__(256) void sum_parts_kernel(const double *__restrict
   double s = 0;
   for (int b = threadIdx.x; b < blocks; b += 256) s += part[(int64_t)b * cols + c];
   __shared__ double red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_f64(s, red);
   if (threadIdx.x == 0) out[c] = red[0];
 }
 

@@ -24,6 +24,33 @@ __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 
 constexpr int kXcds = 8;
 inline unsigned xcd_grid(int64_t total) { return (unsigned)(kXcds * cdiv(total, kXcds)); }
 __device__ __forceinline__ int64_t xcd_logical(int64_t bid, int64_t grid) { return (bid % kXcds) * (grid / kXcds) + bid / kXcds; }
+// 256-byte aligned start of a caller's workspace (every *_workspace size includes the slack) ...
+template <class T = char>
+inline T *align256(const void *p) { return (T *)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+inline int64_t align256(int64_t bytes) { return (bytes + 255) / 256 * 256; }   // ... and the size of a piece of it
+
+// ---- functions shared between translation units, each declared once here ----
+// gemm.hip: out[n] = sum_m Y[m][n] (part: colsum_workspace_floats(M, N) floats), and the ordered f64 sum of partials it ends
+// in, out[n] = sum_p part[p][n] -- one workgroup per column
+void colsum_launch(const float *Y, int64_t ldy, float *out, float *part, int64_t M, int64_t N, hipStream_t s);
+int64_t colsum_workspace_floats(int64_t M, int64_t N);
+void col_parts_sum_launch(const float *part, float *out, int64_t N, int parts, hipStream_t s);
+// gemm_f16x3.hip: amax[0] = bit pattern of max |W[n * ldw + k]| over N x K (memset + one launch); the input of w_scale (f16x3.h).
+// grid = 0: min(cdiv(N K, 1024), 1024) workgroups
+void w_amax_launch(const float *W, int64_t ldw, int64_t N, int64_t K, uint32_t *amax, hipStream_t s, unsigned grid = 0);
+// bn_pool.hip: mean / biased variance from per-block partial sums [blocks][2C] (f64); ... + svr_bn_finalize(training = 1) in
+// one launch (stats may be null); out[c] = ordered f64 sum of part[b][c]
+void bn_stats_final_launch(const double *part, double *stats, int64_t rows, int C, int blocks, hipStream_t s);
+void bn_stats_finalize_launch(const double *part, double *stats, int64_t rows, int C, int blocks, const float *gamma,
+                              const float *beta, float *rmean, float *rvar, float *ss, float *mean_f32, float eps, float momentum,
+                              hipStream_t s);
+void bn_sum_parts_launch(const double *part, double *out, int cols, int blocks, hipStream_t s);
+// conv3d.hip: dWp = ordered f64 sum of `parts` slabs [part][tap][tile][32][32] (+ db from dbpart [dbparts][Co] in the same
+// launch); conv_in's dWp[tap][co] / db[co] from per-workgroup slabs [part][32 taps][32] / [part][Co]
+void conv3d_bwd_weight_reduce_launch(const float *slab, float *dWp, int Ci, int Co, int cit, int cot, int parts,
+                                     hipStream_t s, int param_layout, const float *dbpart, float *db, int dbparts);
+void conv3d_c1_wgrad_reduce_launch(const float *slab, float *dWp, int Co, int parts, int param_layout, const float *dbpart,
+                                   float *db, hipStream_t s);
 // sort.hip: stable 32-bit key / value radix sort (rocPRIM)
 size_t sort_pairs_u32_temp_bytes(int64_t n, int bits);
 hipError_t sort_pairs_u32(void *tmp, size_t tmp_bytes, const uint32_t *kin, uint32_t *kout, const int32_t *vin, int32_t *vout,

@@ -25,7 +25,6 @@ struct Src2 {
   int C0, C1;
 };
 
-__device__ __forceinline__ float act_f(float v, int act) { return act == 1 ? (v > 0.f ? v : 0.2f * v) : (act == 2 ? fmaxf(v, 0.f) : v); }
 __device__ __forceinline__ float act_g(float v, int act) { return act == 1 ? (v > 0.f ? 1.f : 0.2f) : (act == 2 ? (v > 0.f ? 1.f : 0.f) : 1.f); }
 
 __device__ __forceinline__ void up_axis(int dst, int n, int &i0, int &i1, float &l0, float &l1) {
@@ -45,9 +44,9 @@ __device__ __forceinline__ void load_virtual(const Src2 &S, int b, int y, int x,
     const float *q = p + (((int64_t)b * H + yy) * W + xx) * C + cc;
     if constexpr (VEC == 4) {
       const float4 t = *reinterpret_cast<const float4 *>(q);
-      v[0] = act_f(t.x, act); v[1] = act_f(t.y, act); v[2] = act_f(t.z, act); v[3] = act_f(t.w, act);
+      v[0] = cv_act(t.x, act); v[1] = cv_act(t.y, act); v[2] = cv_act(t.z, act); v[3] = cv_act(t.w, act);
     } else {
-      v[0] = act_f(q[0], act);
+      v[0] = cv_act(q[0], act);
     }
   };
   if (!up) {
@@ -569,7 +568,7 @@ extern "C" int svr_conv2d_small_bwd_weight(const svr_conv2d_desc *d, const float
   const int64_t M = (int64_t)d->B * Ho * Wo;
   const int rpb = sm_rows_per_block(M);
   const int parts = (int)cdiv(M, rpb);
-  float *part = (float *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  float *part = align256<float>(workspace);
   const int items = kk * ((C + 3) / 4);
   const int ipg = std::min(1024, (items + 63) / 64 * 64), G = std::max(1, 1024 / ipg);   // items per group, groups per workgroup
   const dim3 grid((unsigned)parts, (unsigned)cdiv(items, ipg));

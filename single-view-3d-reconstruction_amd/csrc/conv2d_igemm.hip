@@ -30,20 +30,12 @@ using namespace svr;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int GK = 16;           // reduction elements per step (one MFMA depth)
 constexpr int GLW = 8;           // dwords per LDS row of a plane: 16 halves
 constexpr int GTM = 128;         // tile rows
 constexpr int GAPLANE = GTM * GLW;
 
-// (row, half h) -> dword offset of the 16-byte slot; see gemm_f16x3.hip (conflict-free ds_read_b128 on unpadded rows)
-__device__ __forceinline__ int g_slot(int row, int h) { return (row * 2 + (h ^ ((row >> 3) & 1))) * 4; }
-__device__ __forceinline__ f16x8 g_frag(const uint32_t *plane, int row, int lh) {
-  union { uint4 q; f16x8 v; } f;
-  f.q = *reinterpret_cast<const uint4 *>(plane + g_slot(row, lh));
-  return f.v;
-}
+// LDS planes: slot_dw / frag_f16 of f16x3.h (conflict-free ds_read_b128 on unpadded rows), as gemm_f16x3.hip
 
 struct IgGeom {
   CvSrc S;            // the gathered operand: forward = the block's input, backward-data = dY (B, Ho, Wo, Cout)
@@ -149,12 +141,12 @@ __global__ __launch_bounds__(2 * TN, TN == 128 ? 3 : 2) void conv2d_igemm_kernel
       uint32_t h0, l0, h1, l1;
       split_x(v.x * sx, v.y * sx, h0, l0);
       split_x(v.z * sx, v.w * sx, h1, l1);
-      const int off = g_slot((t >> 2) + (NT / 4) * i, (t & 3) >> 1) + (t & 1) * 2;
+      const int off = slot_dw((t >> 2) + (NT / 4) * i, (t & 3) >> 1) + (t & 1) * 2;
       *reinterpret_cast<uint2 *>(st + off) = make_uint2(h0, h1);
       *reinterpret_cast<uint2 *>(st + GAPLANE + off) = make_uint2(l0, l1);
     }
     uint32_t *sb = st + 2 * GAPLANE;
-    const int offb = g_slot(t >> 1, t & 1);
+    const int offb = slot_dw(t >> 1, t & 1);
 #pragma unroll
     for (int p = 0; p < 2; ++p) *reinterpret_cast<uint4 *>(sb + p * BPLANE + offb) = r.w[p];
   };
@@ -173,10 +165,10 @@ __global__ __launch_bounds__(2 * TN, TN == 128 ? 3 : 2) void conv2d_igemm_kernel
     f16x8 a[2][2], b[3][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      a[0][i] = g_frag(pa, wr * 64 + i * 32 + l31, lh);
-      a[1][i] = g_frag(pa + GAPLANE, wr * 64 + i * 32 + l31, lh);
-      b[0][i] = g_frag(pb, wc * 64 + i * 32 + l31, lh);
-      b[1][i] = g_frag(pb + BPLANE, wc * 64 + i * 32 + l31, lh);
+      a[0][i] = frag_f16(pa + slot_dw(wr * 64 + i * 32 + l31, lh));
+      a[1][i] = frag_f16(pa + GAPLANE + slot_dw(wr * 64 + i * 32 + l31, lh));
+      b[0][i] = frag_f16(pb + slot_dw(wc * 64 + i * 32 + l31, lh));
+      b[1][i] = frag_f16(pb + BPLANE + slot_dw(wc * 64 + i * 32 + l31, lh));
       b[2][i] = scale_2m11(b[0][i]);
     }
 #pragma unroll
@@ -333,11 +325,11 @@ __device__ __forceinline__ void ig_split_fwd_item(const float *__restrict__ W, c
   const float sc = w_scale(amax[0], false);
   const int64_t kk2 = (int64_t)k * k;
   const float w0 = c < C ? W[(n * C + c) * kk2 + tap] * sc : 0.f, w1 = c + 1 < C ? W[(n * C + c + 1) * kk2 + tap] * sc : 0.f;
-  const uint32_t hi = pack_f16(w0, w1);
-  const f32x2 h = unpack_f16(hi);
   const int64_t o = (((kk >> 4) * 2) * Cout + n) * 16 + (kk & 15);
+  uint32_t hi, lo;
+  split_w(w0, w1, hi, lo);
   *reinterpret_cast<uint32_t *>(p0 + o) = hi;
-  *reinterpret_cast<uint32_t *>(p0 + o + (int64_t)Cout * 16) = pack_f16(w0 - h.x, w1 - h.y);
+  *reinterpret_cast<uint32_t *>(p0 + o + (int64_t)Cout * 16) = lo;
 }
 __global__ __launch_bounds__(256) void ig_split_fwd_kernel(const float *__restrict__ W, const uint32_t *__restrict__ amax,
                                                            uint16_t *__restrict__ p0, int Cout, int C, int k, int Cpad) {
@@ -358,11 +350,11 @@ __device__ __forceinline__ void ig_split_bwd_item(const float *__restrict__ W, c
   const int64_t kk2 = (int64_t)k * k, tap = ky * k + kx;
   const float w0 = co < Cout ? W[((int64_t)co * C + n) * kk2 + tap] * sc : 0.f;
   const float w1 = co + 1 < Cout ? W[((int64_t)(co + 1) * C + n) * kk2 + tap] * sc : 0.f;
-  const uint32_t hi = pack_f16(w0, w1);
-  const f32x2 h = unpack_f16(hi);
   const int64_t o = cls * (2 * K * C) + (((kk >> 4) * 2) * C + n) * 16 + (kk & 15);
+  uint32_t hi, lo;
+  split_w(w0, w1, hi, lo);
   *reinterpret_cast<uint32_t *>(p0 + o) = hi;
-  *reinterpret_cast<uint32_t *>(p0 + o + (int64_t)C * 16) = pack_f16(w0 - h.x, w1 - h.y);
+  *reinterpret_cast<uint32_t *>(p0 + o + (int64_t)C * 16) = lo;
 }
 __global__ __launch_bounds__(256) void ig_split_bwd_kernel(const float *__restrict__ W, const uint32_t *__restrict__ amax,
                                                            uint16_t *__restrict__ p0, int Cout, int C, int k, int Copad, int mode) {
@@ -407,7 +399,6 @@ __global__ __launch_bounds__(256) void ig_split_many_kernel(const IgPrepTable T,
 }
 
 int pad16(int c) { return (c + 15) / 16 * 16; }
-int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
 
 int ig_check(const svr_conv2d_desc *d, int Cout, const char *what) {
   SVR_CHECK(d && d->src0 && d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0 && Cout > 0, SVR_E_BADARG, "%s: bad descriptor", what);
@@ -453,7 +444,7 @@ bool vec4_ok(const CvSrc &S) {
 // ---- C ABI --------------------------------------------------------------------------------------------------------------
 extern "C" int64_t svr_conv2d_planes_bytes(int32_t Cout, int32_t C, int32_t k) {
   const int64_t fwd = 4LL * Cout * k * k * pad16(C), bwd = 4LL * C * k * k * pad16(Cout);
-  return a256(fwd) + a256(bwd) + 256;
+  return align256(fwd) + align256(bwd) + 256;
 }
 
 extern "C" int svr_conv2d_prepare(const float *W, int32_t Cout, int32_t C, int32_t k, int32_t stride, int32_t want_bwd,
@@ -463,14 +454,14 @@ extern "C" int svr_conv2d_prepare(const float *W, int32_t Cout, int32_t C, int32
             "conv2d_prepare: k=%d stride=%d (k = 1: forward planes only)", k, stride);
   hipStream_t s = (hipStream_t)stream;
   const int64_t numel = (int64_t)Cout * C * k * k;
-  uint16_t *pf = (uint16_t *)(((uintptr_t)planes + 255) & ~(uintptr_t)255);
-  uint16_t *pb = (uint16_t *)((char *)pf + a256(4LL * Cout * k * k * pad16(C)));
-  (void)hipMemsetAsync(amax, 0, sizeof(uint32_t), s);
-  if ((((uintptr_t)W) & 15) == 0)
+  uint16_t *pf = align256<uint16_t>(planes);
+  uint16_t *pb = (uint16_t *)((char *)pf + align256(4LL * Cout * k * k * pad16(C)));
+  if ((((uintptr_t)W) & 15) == 0) {
+    (void)hipMemsetAsync(amax, 0, sizeof(uint32_t), s);
     hipLaunchKernelGGL(ig_amax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(numel, 4096), 256)), dim3(256), 0, s, W, numel, amax);
-  else
-    hipLaunchKernelGGL(w_amax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(numel, 1024), 1024)), dim3(256), 0, s, W, numel, (int64_t)1,
-                       numel, amax);
+  } else {
+    w_amax_launch(W, numel, 1, numel, amax, s);
+  }
   const int Cpad = pad16(C), Copad = pad16(Cout);
   hipLaunchKernelGGL(ig_split_fwd_kernel, dim3((unsigned)cdiv((int64_t)Cout * k * k * Cpad / 2, 256)), dim3(256), 0, s, W, amax, pf,
                      Cout, C, k, Cpad);
@@ -494,8 +485,8 @@ extern "C" int svr_conv2d_prepare_many(int32_t n, const float *const *W, const i
     SVR_CHECK(W[i] && planes[i] && Cout[i] > 0 && C[i] > 0, SVR_E_BADARG, "conv2d_prepare_many: layer %d", i);
     SVR_CHECK((k[i] == 4 && stride[i] == 2) || (k[i] == 3 && stride[i] == 1), SVR_E_UNSUPPORTED, "conv2d_prepare_many: layer %d k=%d stride=%d",
               i, k[i], stride[i]);
-    uint16_t *pf = (uint16_t *)(((uintptr_t)planes[i] + 255) & ~(uintptr_t)255);
-    uint16_t *pb = (uint16_t *)((char *)pf + a256(4LL * Cout[i] * k[i] * k[i] * pad16(C[i])));
+    uint16_t *pf = align256<uint16_t>(planes[i]);
+    uint16_t *pb = (uint16_t *)((char *)pf + align256(4LL * Cout[i] * k[i] * k[i] * pad16(C[i])));
     T.it[i] = IgPrepItem{W[i], pf, want_bwd[i] ? pb : nullptr, Cout[i], C[i], k[i], stride[i]};
     const int64_t items = (int64_t)Cout[i] * k[i] * k[i] * pad16(C[i]) / 2 + (want_bwd[i] ? (int64_t)C[i] * k[i] * k[i] * pad16(Cout[i]) / 2 : 0);
     maxitems = std::max(maxitems, items);
@@ -523,7 +514,7 @@ extern "C" int64_t svr_conv2d_workspace_bytes(const svr_conv2d_desc *d, int32_t 
   const int64_t mb = cdiv((int64_t)d->B * cdiv(d->H, d->stride) * cdiv(d->W, d->stride), GTM) * cdiv(C, C <= 64 ? 64 : 128);
   const int sb = ig_splits(mb * ncls, (d->stride == 2 ? 4 : 9) * pad16(Cout) / GK, C, &ks);
   const int64_t bwd = (sb > 1 && d->k != 1) ? (int64_t)sb * d->B * d->H * d->W * C * 4 : 0;   // (k = 1: forward only)
-  return a256(std::max(fwd, bwd)) + 256;
+  return align256(std::max(fwd, bwd)) + 256;
 }
 
 extern "C" int svr_conv2d_fwd(const svr_conv2d_desc *d, const void *planes, const uint32_t *amax_w, const float *bias, float *Y,
@@ -543,9 +534,9 @@ extern "C" int svr_conv2d_fwd(const svr_conv2d_desc *d, const void *planes, cons
   float *partial = nullptr;
   if (splits > 1) {
     SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_fwd: %d reduction splits need the workspace", splits);
-    partial = (float *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    partial = align256<float>(workspace);
   }
-  const uint16_t *pf = (const uint16_t *)(((uintptr_t)planes + 255) & ~(uintptr_t)255);
+  const uint16_t *pf = align256<const uint16_t>(planes);
   hipStream_t s = (hipStream_t)stream;
   if (vec4_ok(G.S)) ig_launch<true>(G, 1, mtiles, splits, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
   else ig_launch<false>(G, 1, mtiles, splits, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
@@ -575,10 +566,10 @@ extern "C" int svr_conv2d_bwd_data(const svr_conv2d_desc *d, const void *planes,
   float *partial = nullptr;
   if (splits > 1) {
     SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_bwd_data: %d reduction splits need the workspace", splits);
-    partial = (float *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    partial = align256<float>(workspace);
   }
-  const uint16_t *pf = (const uint16_t *)(((uintptr_t)planes + 255) & ~(uintptr_t)255);
-  const uint16_t *pb = (const uint16_t *)((const char *)pf + a256(4LL * Cout * d->k * d->k * pad16(C)));
+  const uint16_t *pf = align256<const uint16_t>(planes);
+  const uint16_t *pb = (const uint16_t *)((const char *)pf + align256(4LL * Cout * d->k * d->k * pad16(C)));
   hipStream_t s = (hipStream_t)stream;
   if (vec4_ok(G.S)) ig_launch<true>(G, ncls, mtiles, splits, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);
   else ig_launch<false>(G, ncls, mtiles, splits, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);

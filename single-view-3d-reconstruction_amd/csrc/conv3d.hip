@@ -14,16 +14,9 @@
 #include "common.h"
 #include <algorithm>
 #include "gemm_core.h"
+#include "reduce.h"
 
 using namespace svr;
-
-namespace svr {
-// defined in gemm.hip
-void colsum_launch(const float *Y, int64_t ldy, float *out, float *part, int64_t M, int64_t N, hipStream_t s);
-int64_t colsum_workspace_floats(int64_t M, int64_t N);
-// defined in bn_pool.hip
-void bn_stats_final_launch(const double *part, double *stats, int64_t rows, int C, int blocks, hipStream_t s);
-}  // namespace svr
 
 namespace {
 
@@ -477,12 +470,7 @@ __global__ __launch_bounds__(256) void conv3d_bwd_weight_reduce_kernel(const flo
     const int co = blockIdx.x - wblocks;
     double sum = 0.0;
     for (int p = threadIdx.x; p < dbparts; p += 256) sum += (double)dbpart[(int64_t)p * Co + co];
-    red[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
+    block_sum_f64(sum, red);
     if (threadIdx.x == 0) db[co] = (float)red[0];
     return;
   }
@@ -760,21 +748,6 @@ __global__ __launch_bounds__(256) void conv3d_c1_bwd_weight_co16_lds_kernel(cons
   }
 }
 
-// db[co] = ordered f64 sum of the per-workgroup partial bias gradients [parts][Co]
-__global__ void conv3d_db_reduce_kernel(const float *__restrict__ dbpart, float *__restrict__ db, int Co, int parts) {
-  __shared__ double red[256];
-  const int co = blockIdx.x;
-  double sum = 0.0;
-  for (int p = threadIdx.x; p < parts; p += 256) sum += (double)dbpart[(int64_t)p * Co + co];
-  red[threadIdx.x] = sum;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) db[co] = (float)red[0];
-}
-
 // one workgroup per (tap, co): f64 tree over the per-wave partial slabs (fixed order)
 // (param_layout: dW(Co,1,3,3,3) instead of [tap][co]; workgroups >= 27 Co reduce the bias-gradient partials dbpart [parts][Co])
 __global__ __launch_bounds__(256) void conv3d_c1_bwd_weight_reduce_kernel(const float *__restrict__ slab,
@@ -790,12 +763,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_bwd_weight_reduce_kernel(const 
     for (int p = threadIdx.x; p < parts; p += 256) sum += (double)slab[(int64_t)p * 1024 + tap * 32 + co];
   }
   __shared__ double red[256];
-  red[threadIdx.x] = sum;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_f64(sum, red);
   if (threadIdx.x == 0) {
     if (bias) db[co] = (float)red[0];
     else dWp[param_layout ? co * 27 + tap : tap * Co + co] = (float)red[0];
@@ -934,14 +902,14 @@ extern "C" int svr_conv3d_k3_bwd_weight(const float *in, const float *dout, floa
       float *dbpart = db ? slab + (int64_t)parts * 1024 : nullptr;
       hipLaunchKernelGGL(conv3d_c1_bwd_weight_co16_lds_kernel, dim3(parts), dim3(256), 0, s, in, dout, slab, sh, nyb, dbpart);
       if (db) {
-        hipLaunchKernelGGL(conv3d_db_reduce_kernel, dim3(16), dim3(256), 0, s, dbpart, db, 16, parts);
+        col_parts_sum_launch(dbpart, db, 16, parts, s);  // db[co] = ordered f64 sum of the partials [parts][16]
         db = nullptr;  // done
       }
     } else if (Co == 16) {
       float *dbpart = db ? slab + (int64_t)chunks * 1024 : nullptr;  // the colsum scratch is at least chunks * 16 floats
       hipLaunchKernelGGL(conv3d_c1_bwd_weight_co16_kernel, dim3(chunks), dim3(256), 0, s, in, dout, slab, sh, dbpart);
       if (db) {
-        hipLaunchKernelGGL(conv3d_db_reduce_kernel, dim3(16), dim3(256), 0, s, dbpart, db, 16, chunks);
+        col_parts_sum_launch(dbpart, db, 16, chunks, s);  // db[co] = ordered f64 sum of the partials [parts][16]
         db = nullptr;  // done
       }
     } else
@@ -983,7 +951,7 @@ extern "C" int svr_conv3d_c1_fwd_stats(const float *in, const float *Wp, const f
   ConvShape sh{B, D, H, W, 1, Co};
   const int nbz = (int)cdiv(D, C1B), nby = (int)cdiv(H, C1B), nbx = (int)cdiv(W, C1B);
   const unsigned grid = (unsigned)((int64_t)B * nbz * nby * nbx);
-  double *part = (double *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  double *part = align256<double>(workspace);
   if (Co == 16) hipLaunchKernelGGL(conv3d_c1_mfma_kernel<16>, dim3(grid), dim3(256), 0, s, in, Wp, bias, out, sh, nbz, nby, nbx, epilogue, part);
   else if (Co == 32) hipLaunchKernelGGL(conv3d_c1_mfma_kernel<32>, dim3(grid), dim3(256), 0, s, in, Wp, bias, out, sh, nbz, nby, nbx, epilogue, part);
   else SVR_CHECK(false, SVR_E_UNSUPPORTED, "conv3d_c1_fwd_stats: Co in {16,32}, got %d", Co);

@@ -21,20 +21,9 @@
 #include "common.h"
 #include "f16x3.h"
 
-namespace svr {
-void colsum_launch(const float *Y, int64_t ldy, float *out, float *part, int64_t M, int64_t N, hipStream_t s);
-int64_t colsum_workspace_floats(int64_t M, int64_t N);
-void conv3d_bwd_weight_reduce_launch(const float *slab, float *dWp, int Ci, int Co, int cit, int cot, int parts,
-                                     hipStream_t s, int param_layout, const float *dbpart, float *db, int dbparts);
-}  // namespace svr
-
 using namespace svr;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvShape {
   int B, D, H, W, Ci, Co;
@@ -54,15 +43,6 @@ constexpr int DO_ITEMS = BRZ * BRY * 4 * 8;       // (row, voxel pair, 4-channel
 constexpr int IN_IT = (IN_ITEMS + NT - 1) / NT;   // 3: two travel in the first half of a brick's prefetch, one + the dout item in the second
 static_assert(IN_IT == 3 && DO_ITEMS == NT, "prefetch phases below are written for 3 + 1 items per thread");
 constexpr int TAPS_PER_WAVE = 7;                  // 27 taps over 4 tap groups: 7 / 7 / 7 / 6
-
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t &hi, uint32_t &mid) {
-  f32x2 v = {x0, x1};
-  bf16x2 h = __builtin_convertvector(v, bf16x2);
-  hi = __builtin_bit_cast(uint32_t, h);
-  f32x2 r = {x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u)};
-  bf16x2 m = __builtin_convertvector(r, bf16x2);
-  mid = __builtin_bit_cast(uint32_t, m);
-}
 
 __device__ __forceinline__ bf16x8 frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   union { uint4 q; bf16x8 v; } f;
@@ -581,22 +561,6 @@ __global__ __launch_bounds__(NT) void conv3d_bwd_weight_ws_kernel(const float *_
       if (co0 + t < s.Co) dbpart[(int64_t)blockIdx.x * s.Co + co0 + t] = sum;
     }
   }
-}
-
-// db[co] = f64 tree (fixed order) over the workgroups' partial bias gradients; one workgroup per channel
-__global__ __launch_bounds__(256) void db_reduce_kernel(const float *__restrict__ dbpart, float *__restrict__ db, int Co,
-                                                        int parts) {
-  __shared__ double red[256];
-  const int co = blockIdx.x;
-  double sum = 0.0;
-  for (int p = threadIdx.x; p < parts; p += 256) sum += (double)dbpart[(int64_t)p * Co + co];
-  red[threadIdx.x] = sum;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) db[co] = (float)red[0];
 }
 
 // persistent workgroups per channel-tile pair: one workgroup per CU in total (LDS bound)

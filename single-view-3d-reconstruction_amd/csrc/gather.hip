@@ -14,6 +14,7 @@
 // float4 per lane; a point's 7*C outputs of one level are contiguous in its feature row.
 #include "common.h"
 #include "gather_common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -1124,12 +1125,7 @@ __global__ __launch_bounds__(256) void pull_stats_kernel(const int32_t *__restri
     len = cs[k + ncell] - cs[k];
   }
   __shared__ int red[256];
-  red[threadIdx.x] = len;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] = max(red[threadIdx.x], red[threadIdx.x + o]);
-    __syncthreads();
-  }
+  block_max(len, red);
   if (threadIdx.x == 0 && red[0] > 0) atomicMax(stats, red[0]);
 }
 
@@ -1139,7 +1135,6 @@ int pull_key_bits(int64_t cells) {  // sentinel = cells must fit
   while ((1LL << nb) <= cells) ++nb;
   return nb;
 }
-int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
 int check_desc(const svr_gather_desc *d, bool bwd) {
   SVR_CHECK(d != nullptr, SVR_E_BADARG, "gather: null descriptor");
@@ -1327,12 +1322,12 @@ extern "C" int64_t svr_gather_pull_plan_workspace(int32_t B, int32_t N) {
   // svr_gather_pull_plan_workspace_cells below -- callers add both
   const int64_t T = (int64_t)7 * B * N;
   if (T <= 0) return 256;
-  return 3 * al256(T * 4) + al256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32)) + 256;
+  return 3 * svr::align256(T * 4) + svr::align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32)) + 256;
 }
 
 extern "C" int64_t svr_gather_pull_plan_workspace_cells(int32_t B, int32_t D, int32_t H, int32_t W) {
   const int64_t cells = pull_cells(B, D, H, W);
-  return al256((cells + 1) * 4) + al256((int64_t)svr::scan_max_i32_temp_bytes(cells + 1)) + 256;
+  return svr::align256((cells + 1) * 4) + svr::align256((int64_t)svr::scan_max_i32_temp_bytes(cells + 1)) + 256;
 }
 
 extern "C" int svr_gather_pull_plan(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W, int32_t C,
@@ -1347,22 +1342,22 @@ extern "C" int svr_gather_pull_plan(const float *points, int32_t B, int32_t N, i
   SVR_CHECK(cells < (1LL << 31) - 1 && T < (1LL << 31) && (int64_t)B * N * row_stride < (1LL << 31), SVR_E_UNSUPPORTED,
             "pull_plan: %ld cells / %ld items / %ld gradient floats exceed 32-bit offsets", (long)cells, (long)T,
             (long)((int64_t)B * N * row_stride));
-  char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char *w = svr::align256(workspace);
   int32_t *ends = (int32_t *)w;   // raw cell ends, then the running maximum goes to `heads`
-  w += al256((cells + 1) * 4);
+  w += svr::align256((cells + 1) * 4);
   void *scan_tmp = (void *)w;
   const size_t scan_bytes = svr::scan_max_i32_temp_bytes(cells + 1);
-  w += al256((int64_t)scan_bytes);
+  w += svr::align256((int64_t)scan_bytes);
   hipError_t e = hipMemsetAsync(ends, 0, (size_t)(cells + 1) * sizeof(int32_t), s);
   SVR_CHECK(e == hipSuccess, (int)e, "pull_plan: memset failed: %s", hipGetErrorString(e));
   if (T > 0) {
     SVR_CHECK(points && keys && recs, SVR_E_BADARG, "pull_plan: null pointer");
     uint32_t *keys_in = (uint32_t *)w;
-    w += al256(T * 4);
+    w += svr::align256(T * 4);
     int32_t *vals_in = (int32_t *)w;
-    w += al256(T * 4);
+    w += svr::align256(T * 4);
     int32_t *items = items_out ? items_out : (int32_t *)w;   // the sorted item ids double as svr_level.item_order
-    w += al256(T * 4);
+    w += svr::align256(T * 4);
     const uint32_t sentinel = (uint32_t)cells;
     const int bits = pull_key_bits(cells);
     hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys_in, vals_in, T, N, D,
@@ -1399,13 +1394,13 @@ int item_order_impl(const float *points, int32_t B, int32_t N, int32_t D, int32_
   SVR_CHECK(nkeys < (1LL << 31) - 1 && T < (1LL << 31), SVR_E_UNSUPPORTED, "item_order: %ld keys / %ld items exceed 32 bits",
             (long)nkeys, (long)T);
   hipStream_t s = (hipStream_t)stream;
-  char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char *w = svr::align256(workspace);
   uint32_t *keys_in = (uint32_t *)w;
-  w += al256(T * 4);
+  w += svr::align256(T * 4);
   int32_t *vals_in = (int32_t *)w;
-  w += al256(T * 4);
+  w += svr::align256(T * 4);
   uint32_t *keys_out = (uint32_t *)w;
-  w += al256(T * 4);
+  w += svr::align256(T * 4);
   const int bits = pull_key_bits(nkeys);
   hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys_in, vals_in, T, N, D, H,
                      W, displacement, align_corners, (uint32_t)nkeys, kblk);
@@ -1449,8 +1444,8 @@ extern "C" int svr_gather_project_bwd(const float *points, const float *dh, int6
 extern "C" int64_t svr_gather_project_plan_workspace(int32_t B, int32_t N) {
   const int64_t T = (int64_t)7 * B * N;
   if (T <= 0) return 256;
-  return 2 * al256(T * 4) + al256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32)) + al256((T + 1) * 4) +
-         al256((int64_t)svr::scan_sum_excl_i32_temp_bytes(T + 1)) + 512;
+  return 2 * svr::align256(T * 4) + svr::align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32)) + svr::align256((T + 1) * 4) +
+         svr::align256((int64_t)svr::scan_sum_excl_i32_temp_bytes(T + 1)) + 512;
 }
 
 extern "C" int64_t svr_gather_project_slots(int32_t B, int32_t N, int32_t D, int32_t H, int32_t W) {
@@ -1469,16 +1464,16 @@ extern "C" int svr_gather_project_plan(const float *points, int32_t B, int32_t N
   SVR_CHECK(nkeys < (1LL << 31) - 1 && T < (1LL << 31) - 1, SVR_E_UNSUPPORTED, "project_plan: %ld keys / %ld items exceed 32 bits",
             (long)nkeys, (long)T);
   hipStream_t s = (hipStream_t)stream;
-  char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char *w = svr::align256(workspace);
   uint32_t *keys_in = (uint32_t *)w;
-  w += al256(T * 4);
+  w += svr::align256(T * 4);
   int32_t *vals_in = (int32_t *)w;
-  w += al256(T * 4);
+  w += svr::align256(T * 4);
   const int bits = pull_key_bits(nkeys);
   void *sort_tmp = w;
-  w += al256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32));
+  w += svr::align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32));
   int32_t *flags = (int32_t *)w;
-  w += al256((T + 1) * 4);
+  w += svr::align256((T + 1) * 4);
   hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys_in, vals_in, T, N, D, H,
                      W, displacement, align_corners, (uint32_t)nkeys, 1);
   hipError_t e = svr::sort_pairs_u32(sort_tmp, svr::sort_pairs_u32_temp_bytes(T, bits), keys_in, keys, vals_in, items, T, bits, s);

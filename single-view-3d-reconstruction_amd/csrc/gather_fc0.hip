@@ -36,20 +36,11 @@ using namespace svr;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define GLOBAL_AS __attribute__((address_space(1)))
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_bf16_rne(float a, float b) {  // round to nearest even (v_cvt_pk_bf16_f32), NaN safe
-  f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
 
 constexpr int FK = 16;                 // reduction elements per MFMA step
-constexpr int FLW = 8;                 // dwords per LDS row of one k-step: 16 halves = two 16-byte slots (fc_slot_dw), as gemm_f16x3.hip
+constexpr int FLW = 8;                 // dwords per LDS row of one k-step: 16 halves = two 16-byte slots (slot_dw), as gemm_f16x3.hip
 constexpr int FTM = 64;                // points per workgroup.  64 (two workgroups per CU: 128 VGPRs, 42 KB of LDS each,
                                        // 16 waves per CU hide the producers' load latency; one pass in flight per producer
                                        // wave) 2.58 ms at config 3 against 2.83 for 128 (one workgroup per CU, 255 VGPRs,
@@ -134,8 +125,8 @@ __global__ void split_w_fused_kernel(FcArgs A, const float *__restrict__ W, int6
   if (kk >= A.KF || n >= N) return;
   const int src = fused_col(A, kk);
   const float w = src >= 0 ? W[(int64_t)n * ldw + src] * w_scale(amax[0], false) : 0.f;
-  const _Float16 h = (_Float16)w;  // round to nearest even, like pack_f16
-  const _Float16 l = (_Float16)(w - (float)h);
+  _Float16 h, l;
+  split_w(w, h, l);
   p0[wfrag_index(kk, 0, n, N / 32)] = __builtin_bit_cast(uint16_t, h);
   p0[wfrag_index(kk, 1, n, N / 32)] = __builtin_bit_cast(uint16_t, l);
 }
@@ -146,19 +137,11 @@ __global__ void split_w_fused_bf16_kernel(FcArgs A, const float *__restrict__ W,
   if (kk >= A.KF || n >= N) return;
   const int src = fused_col(A, kk);
   const float w = src >= 0 ? W[(int64_t)n * ldw + src] : 0.f;
-  p0[wfrag_index(kk, 0, n, N / 32, 1)] = (uint16_t)(pack_bf16_rne(w, 0.f) & 0xffffu);
+  p0[wfrag_index(kk, 0, n, N / 32, 1)] = (uint16_t)(pack_bf16(w, 0.f) & 0xffffu);
 }
 
-// LDS rows of the feature tile: slot (16 bytes = 8 halves) h of a row sits at 2 row + (h ^ bit 3 of the row), so that a
-// consumer's fragment is ONE ds_read_b128 (256 B/clk; the padded 8-byte aligned rows of the first version made it a
-// ds_read2_b64 at 128 B/clk) and its 16-lane groups hit 16 different slots (see gemm_f16x3.hip / conv3d_bf16.hip).
-__device__ __forceinline__ int fc_slot_dw(int row, int h) { return (row * 2 + (h ^ ((row >> 3) & 1))) * 4; }
-
-__device__ __forceinline__ f16x8 lds_frag(const uint32_t *plane, int row, int lh) {
-  union { uint4 q; f16x8 v; } f;
-  f.q = *reinterpret_cast<const uint4 *>(plane + fc_slot_dw(row, lh));
-  return f.v;
-}
+// LDS rows of the feature tile: the unpadded 16-byte slots of slot_dw (f16x3.h), so that a consumer's fragment is ONE
+// ds_read_b128 (frag_f16) whose 16-lane groups hit 16 different slots.
 
 // Levels with C >= 16.  The producers are bound by the instructions they issue (one wave per SIMD, 4 cycles per wave64
 // VALU instruction), so the code is split by how often each part has to run:
@@ -302,7 +285,7 @@ __device__ __forceinline__ void produce_slab(const FcLevel L, const FcSlab S, ui
     for (int k = 0; k < 8; ++k) acc = acc + I.v[k] * w[k];
     uint32_t *d = buf + (dsto ^ (PPW == 16 ? 0 : (((it * PPW) >> 3) & 1) * 4)) + it * (PPW * FLW);
     if constexpr (BF) {   // the feature values in bf16 (one rounding), one plane
-      *reinterpret_cast<uint2 *>(d) = make_uint2(pack_bf16_rne(acc.x, acc.y), pack_bf16_rne(acc.z, acc.w));
+      *reinterpret_cast<uint2 *>(d) = make_uint2(pack_bf16(acc.x, acc.y), pack_bf16(acc.z, acc.w));
       return;
     }
     uint32_t h0, l0, h1, l1;
@@ -367,8 +350,8 @@ __device__ __forceinline__ void produce_c1(const FcLevel L, const FcSlab S, uint
     if (j == 7) acc = 0.f;  // (a volume with non-finite values must not leak into the zero columns)
     const _Float16 h = (_Float16)acc;
     const _Float16 l = (_Float16)((acc - (float)h) * 2048.f);
-    const uint16_t hb = BF ? (uint16_t)(pack_bf16_rne(acc, 0.f) & 0xffffu) : __builtin_bit_cast(uint16_t, h);
-    const int s0 = fc_slot_dw(row, 0), s1 = fc_slot_dw(row, 1);   // halves 0 .. 7 / 8 .. 15 of the row
+    const uint16_t hb = BF ? (uint16_t)(pack_bf16(acc, 0.f) & 0xffffu) : __builtin_bit_cast(uint16_t, h);
+    const int s0 = slot_dw(row, 0), s1 = slot_dw(row, 1);   // halves 0 .. 7 / 8 .. 15 of the row
     if (j < 7) {
       b16[s0 * 2 + j] = hb;
       if (!BF) b16[(FPLANE + s0) * 2 + j] = __builtin_bit_cast(uint16_t, l);
@@ -546,11 +529,11 @@ __global__ __launch_bounds__(NTHR, 4) void gather_fc0_kernel(const FcArgs *__res
       if constexpr (BF) {   // one bf16 product per block
 #pragma unroll
         for (int i = 0; i < FMT; ++i) {
-          union { f16x8 h; bf16x8_t b; } ua;
-          ua.h = lds_frag(pa, i * 32 + l31, lh);
+          union { f16x8 h; bf16x8 b; } ua;
+          ua.h = frag_f16(pa + slot_dw(i * 32 + l31, lh));
 #pragma unroll
           for (int jt = 0; jt < 2; ++jt) {
-            union { uint4 q; bf16x8_t b; } ub;
+            union { uint4 q; bf16x8 b; } ub;
             ub.q = cur[jt][0];
             acc[i][jt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.b, ub.b, acc[i][jt], 0, 0, 0);
           }
@@ -568,7 +551,7 @@ __global__ __launch_bounds__(NTHR, 4) void gather_fc0_kernel(const FcArgs *__res
       }
 #pragma unroll
       for (int i = 0; i < FMT; ++i) {
-        const f16x8 ah = lds_frag(pa, i * 32 + l31, lh), al = lds_frag(pa + FPLANE, i * 32 + l31, lh);
+        const f16x8 ah = frag_f16(pa + slot_dw(i * 32 + l31, lh)), al = frag_f16(pa + FPLANE + slot_dw(i * 32 + l31, lh));
 #pragma unroll
         for (int jt = 0; jt < 2; ++jt) {
           acc[i][jt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, b[2][jt], acc[i][jt], 0, 0, 0);  // lo(x) hi(w)
@@ -605,7 +588,7 @@ __global__ __launch_bounds__(NTHR, 4) void gather_fc0_kernel(const FcArgs *__res
         if (m < M) {
           float v = acc[i][jt][r] * inv + bv;
           if (relu) v = fmaxf(v, 0.f);
-          if constexpr (BF) reinterpret_cast<uint16_t *>(Y)[m * ldy + n] = (uint16_t)(pack_bf16_rne(v, 0.f) & 0xffffu);   // ldy in bf16 elements
+          if constexpr (BF) reinterpret_cast<uint16_t *>(Y)[m * ldy + n] = (uint16_t)(pack_bf16(v, 0.f) & 0xffffu);   // ldy in bf16 elements
           else Y[m * ldy + n] = v;
         }
       }
@@ -764,11 +747,11 @@ struct FcWorkspace {
 };
 FcWorkspace carve(void *workspace, int32_t n_out, int KF) {
   FcWorkspace w;
-  w.amax = (uint32_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  w.amax = align256<uint32_t>(workspace);
   w.p0 = (uint16_t *)(w.amax + 64);
   uint16_t *p1 = w.p0 + (int64_t)n_out * KF;
-  w.Ad = (FcArgs *)(((uintptr_t)(p1 + (int64_t)n_out * KF) + 255) & ~(uintptr_t)255);
-  w.boxes = (FcBox *)(((uintptr_t)(w.Ad + 1) + 255) & ~(uintptr_t)255);
+  w.Ad = align256<FcArgs>(p1 + (int64_t)n_out * KF);
+  w.boxes = align256<FcBox>(w.Ad + 1);
   return w;
 }
 
@@ -813,9 +796,7 @@ extern "C" int svr_gather_fc0_prepare(const svr_gather_desc *d, const float *W, 
   // W's columns: every column of the layout the slabs cover (the row's padding columns never enter the product)
   int64_t kw = 0;
   for (int l = 0; l < d->n_levels; ++l) kw = std::max<int64_t>(kw, d->level[l].col + 7 * d->level[l].C);
-  (void)hipMemsetAsync(ws.amax, 0, sizeof(uint32_t), s);
-  hipLaunchKernelGGL(w_amax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n_out * kw, 1024), 1024)), dim3(256), 0, s, W, ldw,
-                     (int64_t)n_out, kw, ws.amax);
+  w_amax_launch(W, ldw, n_out, kw, ws.amax, s);
   hipLaunchKernelGGL(split_w_fused_kernel, dim3((unsigned)cdiv(A.KF, 64), (unsigned)n_out), dim3(64), 0, s, A, W, ldw, ws.amax,
                      ws.p0, (int)n_out);
   hipLaunchKernelGGL(args_store_kernel, dim3(1), dim3(256), 0, s, A, ws.Ad);

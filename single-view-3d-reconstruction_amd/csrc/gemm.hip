@@ -5,6 +5,7 @@
 // plus the BCE-with-logits loss of trainer/trainer_ifnet.py:46.
 #include "common.h"
 #include "gemm_core.h"
+#include "reduce.h"
 
 using namespace svr;
 
@@ -162,19 +163,15 @@ __global__ void colsum_partial_slow_kernel(const float *__restrict__ Y, int64_t 
   part[(int64_t)blockIdx.x * N + n] = s;
 }
 
-// out[n] = sum_chunks part[chunk][n]: one workgroup per column, f64 tree (fixed order: reproducible)
-__global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restrict__ part, float *__restrict__ out,
-                                                           int64_t N, int chunks) {
+// out[n] = sum_p part[p][n]: one workgroup per column, f64 tree (fixed order: reproducible).  The one reduce behind every
+// column-of-partials sum: colsum_launch's chunks and the bias-gradient partials of the weight-gradient kernels.
+__global__ __launch_bounds__(256) void col_parts_sum_kernel(const float *__restrict__ part, float *__restrict__ out,
+                                                            int64_t N, int parts) {
   const int64_t n = blockIdx.x;
   double s = 0.0;
-  for (int c = threadIdx.x; c < chunks; c += 256) s += (double)part[(int64_t)c * N + n];
+  for (int p = threadIdx.x; p < parts; p += 256) s += (double)part[(int64_t)p * N + n];
   __shared__ double red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_f64(s, red);
   if (threadIdx.x == 0) out[n] = (float)red[0];
 }
 
@@ -287,12 +284,7 @@ __global__ __launch_bounds__(256) void fc_out_bwd_final_kernel(const float *__re
   double s = 0.0;
   for (int b = threadIdx.x; b < blocks; b += 256) s += (double)part[(int64_t)b * (K + 1) + k];
   __shared__ double red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_f64(s, red);
   if (threadIdx.x == 0) {
     if (k < K) dw[k] = (float)red[0];
     else if (db) db[0] = (float)red[0];
@@ -313,12 +305,7 @@ __global__ __launch_bounds__(256) void bce_kernel(const float *__restrict__ z, c
     if (dz) dz[b * N + n] = (1.f / (1.f + expf(-x)) - t) * gscale_over_B;
   }
   __shared__ double red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_f64(s, red);
   if (threadIdx.x == 0) atomicAdd(persample + b, red[0]);
 }
 
@@ -345,12 +332,7 @@ __global__ __launch_bounds__(256) void bce_parts_kernel(const float *__restrict_
     if (dz) dz[b * N + n] = (1.f / (1.f + expf(-x)) - t) * gscale_over_B;
   }
   __shared__ double red[256];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_f64(s, red);
   if (threadIdx.x == 0) part[(int64_t)b * BCE_BLOCKS + blockIdx.x] = red[0];
 }
 
@@ -390,6 +372,9 @@ int tn_splits(int64_t M, int64_t N, int64_t K, int *steps_per_split) {
 }  // namespace
 
 namespace svr {
+void col_parts_sum_launch(const float *part, float *out, int64_t N, int parts, hipStream_t s) {
+  hipLaunchKernelGGL(col_parts_sum_kernel, dim3((unsigned)N), dim3(256), 0, s, part, out, N, parts);
+}
 static int64_t colsum_rows_per_chunk(int64_t M) {
   int64_t r = cdiv(M > 0 ? M : 1, 2048);
   return r < 256 ? 256 : r;
@@ -404,7 +389,7 @@ void colsum_launch(const float *Y, int64_t ldy, float *out, float *part, int64_t
     hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)chunks), dim3(256), 0, s, Y, ldy, part, M, N, rpc);
   else
     hipLaunchKernelGGL(colsum_partial_slow_kernel, dim3((unsigned)chunks, (unsigned)cdiv(N, 64)), dim3(64), 0, s, Y, ldy, part, M, N, rpc);
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)N), dim3(256), 0, s, part, out, N, chunks);
+  col_parts_sum_launch(part, out, N, chunks, s);
 }
 }  // namespace svr
 

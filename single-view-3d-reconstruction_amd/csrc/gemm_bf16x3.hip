@@ -23,32 +23,12 @@
 
 using namespace svr;
 
-namespace svr {
-void colsum_launch(const float *Y, int64_t ldy, float *out, float *part, int64_t M, int64_t N, hipStream_t s);
-int64_t colsum_workspace_floats(int64_t M, int64_t N);
-}  // namespace svr
-
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int XK = 32;    // reduction elements per step
 constexpr int XLD = 40;   // bf16 per LDS row (80 B: 16-byte aligned rows, and 16 consecutive rows cover all 64 banks
                           // with their 16-byte pieces -> ds_read_b128 / ds_write_b128 are conflict free)
 constexpr int XLW = XLD / 2;  // ... in dwords
-
-// (x0, x1) -> packed bf16 pairs of the hi and mid parts
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t &hi, uint32_t &mid) {
-  f32x2 v = {x0, x1};
-  bf16x2 h = __builtin_convertvector(v, bf16x2);
-  hi = __builtin_bit_cast(uint32_t, h);
-  f32x2 r = {x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u)};
-  bf16x2 m = __builtin_convertvector(r, bf16x2);
-  mid = __builtin_bit_cast(uint32_t, m);
-}
 
 // ---- operand loaders (ROWS tile rows, NT threads) -------------------------------------------------
 // A "plane pair" in LDS is uint32_t[2][ROWS * XLW]: hi plane then mid plane, [row][k] bf16.
@@ -398,10 +378,10 @@ __global__ void pack_planes_f16_kernel(const float *__restrict__ W, int64_t ldw,
   const int64_t k = idx / (N / 2), n = (idx % (N / 2)) * 2;
   const float sc = w_scale(amax[0], false);
   const float w0 = W[n * ldw + k] * sc, w1 = W[(n + 1) * ldw + k] * sc;
-  const uint32_t h = pack_f16(w0, w1);
-  const f32x2 hf = unpack_f16(h);
+  uint32_t h, l;
+  split_w(w0, w1, h, l);
   *reinterpret_cast<uint32_t *>(hi + k * N + n) = h;
-  *reinterpret_cast<uint32_t *>(lo + k * N + n) = pack_f16(w0 - hf.x, w1 - hf.y);
+  *reinterpret_cast<uint32_t *>(lo + k * N + n) = l;
 }
 
 // slab[z][N,K] = dY[rows of split z]^T X[rows of split z].  128 x 128 tile, 4 waves, 36 KB of LDS: three
@@ -723,22 +703,6 @@ __global__ __launch_bounds__(256) void dy_planes_kernel(const float *__restrict_
   }
 }
 
-// db[n] = f64 tree over the row-tile partials [parts][N]
-__global__ __launch_bounds__(256) void dy_db_reduce_kernel(const float *__restrict__ dbpart, float *__restrict__ db, int64_t N,
-                                                           int64_t parts) {
-  __shared__ double red[256];
-  const int64_t n = blockIdx.x;
-  double s = 0.0;
-  for (int64_t p = threadIdx.x; p < parts; p += 256) s += (double)dbpart[p * N + n];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) db[n] = (float)red[0];
-}
-
 // out = sum over the split-K slabs, in a FIXED order (bit-reproducible): a workgroup owns 64 outputs, its four 64-lane groups
 // each walk every fourth slab with eight loads in flight, and the four partial sums are combined in lane-group order.  (One
 // thread per output walking all 110-384 slabs four at a time was a latency chain: 46-110 us per call on the main stream.)
@@ -811,11 +775,10 @@ namespace svr {
 int linear_bwd_data_f16_nn(const float *dY, int64_t lddy, const float *W, int64_t ldw, float *dX, int64_t lddx, int64_t M, int64_t N,
                            int64_t K, int epilogue, const float *mask, int64_t ldmask, const uint32_t *amax_dy, uint32_t *amax_dx,
                            void *workspace, hipStream_t s) {
-  uint32_t *amax = (uint32_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  uint32_t *amax = align256<uint32_t>(workspace);
   uint16_t *hi = (uint16_t *)(amax + 64), *lo = hi + N * K;
   if (W) {
-    (void)hipMemsetAsync(amax, 0, sizeof(uint32_t), s);
-    hipLaunchKernelGGL(w_amax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(N * K, 1024), 1024)), dim3(256), 0, s, W, ldw, N, K, amax);
+    w_amax_launch(W, ldw, N, K, amax, s);
     hipLaunchKernelGGL(pack_planes_f16_kernel, dim3((unsigned)cdiv(K * (N / 2), 256)), dim3(256), 0, s, W, ldw, amax, hi, lo, N, K);
   }
   if (!dY) return launch_status("linear_bwd_data_f16x3 (prepare)");
@@ -828,7 +791,6 @@ int linear_bwd_data_f16_nn(const float *dY, int64_t lddy, const float *W, int64_
 
 namespace {
 int64_t tn_mpad(int64_t M) { return cdiv(M, 64) * 64; }
-int64_t align256b(int64_t x) { return (x + 255) / 256 * 256; }
 }  // namespace
 
 extern "C" int64_t svr_linear_bwd_weight_bf16x3_workspace(int64_t M, int64_t N, int64_t K) {
@@ -836,7 +798,7 @@ extern "C" int64_t svr_linear_bwd_weight_bf16x3_workspace(int64_t M, int64_t N, 
   int splits = tn_splits(M, N, K, &rps);
   // slabs | dY planes (hi, mid) | per-row-tile column sums
   const int64_t dbparts = cdiv(M, 64) > splits ? cdiv(M, 64) : splits;  // row tiles (pre-pass) or splits (tr kernel)
-  return align256b((int64_t)splits * N * K * 4) + 2 * align256b(N * tn_mpad(M) * 2) + align256b(dbparts * N * 4) + 256;
+  return align256((int64_t)splits * N * K * 4) + 2 * align256(N * tn_mpad(M) * 2) + align256(dbparts * N * 4) + 256;
 }
 
 extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const float *X, int64_t ldx, float *dW,
@@ -849,13 +811,13 @@ extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const
   int64_t rps;
   int splits = tn_splits(M, N, K, &rps);
   const int64_t Mpad = tn_mpad(M), parts = cdiv(M, 64);
-  char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char *w = align256(workspace);
   float *slab = (float *)w;
-  w += align256b((int64_t)splits * N * K * 4);
+  w += align256((int64_t)splits * N * K * 4);
   uint16_t *ph = (uint16_t *)w;
-  w += align256b(N * Mpad * 2);
+  w += align256(N * Mpad * 2);
   uint16_t *pm = (uint16_t *)w;
-  w += align256b(N * Mpad * 2);
+  w += align256(N * Mpad * 2);
   float *dbpart = (float *)w;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
   if (K % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)X & 15) == 0 && N >= 4 && K >= 4) {
@@ -863,13 +825,13 @@ extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const
     hipLaunchKernelGGL(linear_tn_x3_tr_kernel<>, grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
                        rps, splits, (const uint32_t *)nullptr, CwGeom{});
     hipLaunchKernelGGL(slab_reduce_x3_kernel, dim3((unsigned)cdiv(N * K, 64)), dim3(256), 0, s, slab, dW, N, K, lddw, splits);
-    if (db) hipLaunchKernelGGL(dy_db_reduce_kernel, dim3((unsigned)N), dim3(256), 0, s, dbpart, db, N, (int64_t)splits);
+    if (db) col_parts_sum_launch(dbpart, db, N, splits, s);
     return launch_status("linear_bwd_weight_bf16x3");
   }
   hipLaunchKernelGGL(dy_planes_kernel, dim3((unsigned)parts), dim3(256), 0, s, dY, lddy, ph, pm, Mpad, M, N, db ? dbpart : nullptr);
   hipLaunchKernelGGL(linear_tn_x3_kernel, grid, dim3(256), 0, s, ph, pm, Mpad, X, ldx, slab, M, N, K, rps, splits);
   hipLaunchKernelGGL(slab_reduce_x3_kernel, dim3((unsigned)cdiv(N * K, 64)), dim3(256), 0, s, slab, dW, N, K, lddw, splits);
-  if (db) hipLaunchKernelGGL(dy_db_reduce_kernel, dim3((unsigned)N), dim3(256), 0, s, dbpart, db, N, parts);
+  if (db) col_parts_sum_launch(dbpart, db, N, (int)parts, s);
   return launch_status("linear_bwd_weight_bf16x3");
 }
 
@@ -889,15 +851,15 @@ extern "C" int svr_linear_bwd_weight_f16x3(const float *dY, int64_t lddy, const 
   int64_t rps;
   int splits = tn_splits(M, N, K, &rps);
   const int64_t Mpad = tn_mpad(M);
-  char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char *w = align256(workspace);
   float *slab = (float *)w;
-  w += align256b((int64_t)splits * N * K * 4) + 2 * align256b(N * Mpad * 2);
+  w += align256((int64_t)splits * N * K * 4) + 2 * align256(N * Mpad * 2);
   float *dbpart = (float *)w;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
   hipLaunchKernelGGL((linear_tn_x3_tr_kernel<true>), grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
                      rps, splits, amax_dy, CwGeom{});
   hipLaunchKernelGGL(slab_reduce_x3_kernel, dim3((unsigned)cdiv(N * K, 64)), dim3(256), 0, s, slab, dW, N, K, lddw, splits);
-  if (db) hipLaunchKernelGGL(dy_db_reduce_kernel, dim3((unsigned)N), dim3(256), 0, s, dbpart, db, N, (int64_t)splits);
+  if (db) col_parts_sum_launch(dbpart, db, N, splits, s);
   return launch_status("linear_bwd_weight_f16x3");
 }
 
@@ -938,7 +900,7 @@ extern "C" int64_t svr_conv2d_bwd_weight_workspace(const svr_conv2d_desc *d, int
   int64_t rps;
   const int64_t K = (int64_t)d->k * d->k * Cpad;
   const int splits = conv_wgrad_splits((int64_t)d->B * Ho * Wo, Cout, K, &rps);
-  return align256b((int64_t)splits * Cout * K * 4) + align256b((int64_t)splits * Cout * 4) + 256;
+  return align256((int64_t)splits * Cout * K * 4) + align256((int64_t)splits * Cout * 4) + 256;
 }
 
 extern "C" int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, const uint32_t *amax_dy, int32_t Cout, float *dW,
@@ -954,9 +916,9 @@ extern "C" int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, 
   hipStream_t s = (hipStream_t)stream;
   int64_t rps;
   const int splits = conv_wgrad_splits(M, N, K, &rps);
-  char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char *w = align256(workspace);
   float *slab = (float *)w;
-  float *dbpart = (float *)(w + align256b((int64_t)splits * N * K * 4));
+  float *dbpart = (float *)(w + align256((int64_t)splits * N * K * 4));
   CwGeom G{CvSrc{d->src0, d->src1, d->C0, d->C1, d->H, d->W, d->act}, Wo, Ho * Wo, 1.0f / (float)Wo, 1.0f / (float)(Ho * Wo), d->k, d->stride, 1, Cpad};
   const bool vec4 = d->C0 % 4 == 0 && d->C1 % 4 == 0 && (((uintptr_t)d->src0 | (uintptr_t)d->src1 | (uintptr_t)dY) & 15) == 0;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
@@ -969,6 +931,6 @@ extern "C" int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, 
   const int64_t total = (int64_t)Cout * C * d->k * d->k;
   hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)cdiv(total, 64)), dim3(256), 0, s, (const float *)slab, dW, Cout, C,
                      d->k * d->k, Cpad, splits);
-  if (db) hipLaunchKernelGGL(dy_db_reduce_kernel, dim3((unsigned)N), dim3(256), 0, s, dbpart, db, N, (int64_t)splits);
+  if (db) col_parts_sum_launch(dbpart, db, N, splits, s);
   return launch_status("conv2d_bwd_weight");
 }

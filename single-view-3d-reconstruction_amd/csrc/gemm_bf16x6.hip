@@ -14,35 +14,17 @@
 // 128x128 tile, 4 waves x (2x2) v_mfma_f32_32x32x16_bf16 tiles, k-step 16, LDS planes [row][k] with a 40-byte
 // row stride (ds_read_b64 fragment reads conflict free), one 30 KB LDS stage (4 workgroups per CU).
 #include "common.h"
+#include "f16x3.h"
 
 using namespace svr;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int YK = 16;   // reduction elements per step
 constexpr int YLW = 10;  // dwords per LDS row (16 bf16 + 8 B pad)
 constexpr int TM = 128, TN = 128;
 constexpr int PLANE = TM * YLW;           // dwords per plane
 constexpr int STAGE = 3 * (TM + TN) * YLW;  // dwords per stage
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  f32x2 v = {a, b};
-  bf16x2 h = __builtin_convertvector(v, bf16x2);
-  return __builtin_bit_cast(uint32_t, h);
-}
-
-// (x0, x1) -> packed bf16 pairs of the hi / mid / lo terms
-__device__ __forceinline__ void split3(float x0, float x1, uint32_t &hi, uint32_t &mid, uint32_t &lo) {
-  hi = pack_bf16(x0, x1);
-  const float r0 = x0 - __uint_as_float(hi << 16), r1 = x1 - __uint_as_float(hi & 0xffff0000u);
-  mid = pack_bf16(r0, r1);
-  lo = pack_bf16(r0 - __uint_as_float(mid << 16), r1 - __uint_as_float(mid & 0xffff0000u));
-}
 
 __device__ __forceinline__ bf16x8 read_frag(const uint32_t *plane, int row, int lh) {
   const uint2 a = *reinterpret_cast<const uint2 *>(plane + row * YLW + lh * 4);

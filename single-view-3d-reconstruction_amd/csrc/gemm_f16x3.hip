@@ -23,30 +23,20 @@
 // (X read once) ran one workgroup per CU and was slower (3.1 ms vs 2.4); `nt` loads of X were slower too (3.5).
 #include "common.h"
 #include "f16x3.h"
+#include "reduce.h"
 #include <algorithm>
 
 using namespace svr;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int YK = 16;   // reduction elements per step
 constexpr int YLW = 8;   // dwords per LDS row: 16 halves = two 16-byte slots, no padding
 constexpr int TM = 128;
 constexpr int APLANE = TM * YLW;  // dwords per X plane
 
-// A fragment (8 halves of one row) is one 16-byte slot and comes out of ONE ds_read_b128 (256 B/clk; the 8-byte aligned
-// padded rows of the first version made it a ds_read2_b64: 128 B/clk).  Slot of (row, half h) = 2 row + (h ^ bit 3 of row):
-// the 16-lane groups of ds_read_b128 ({0-3,12-15,20-27}, {4-11,16-19,28-31}, + 32: MI355X_MICROARCH.md "LDS") hold rows that
-// pair up mod 8 at distances 8 and 24, so the 16 lanes hit 16 different slots mod 16 -- conflict free.
-__device__ __forceinline__ int slot_dw(int row, int h) { return (row * 2 + (h ^ ((row >> 3) & 1))) * 4; }
-
-__device__ __forceinline__ f16x8 read_frag(const uint32_t *plane, int row, int lh) {
-  union { uint4 q; f16x8 v; } f;
-  f.q = *reinterpret_cast<const uint4 *>(plane + slot_dw(row, lh));
-  return f.v;
-}
+// A fragment (8 halves of one row) is one 16-byte slot of the LDS planes and comes out of ONE ds_read_b128, conflict free:
+// slot_dw / frag_f16 (f16x3.h).
 
 // W[N][K] f32 -> f16 planes hi(Ws), lo(Ws), K-STEP MAJOR: [k-step][hi / lo][n][16 halves].  A workgroup's W tile of one
 // k-step is then one contiguous 4 KB block per plane (16 bytes per thread); row-major planes [N][K] gave every thread a
@@ -63,12 +53,22 @@ __global__ void split_w_kernel(const float *__restrict__ W, int64_t ldw, const u
   const int64_t n = idx / (K / 2), k = (idx % (K / 2)) * 2;
   const float sc = w_scale(amax[0], false);
   const float w0 = (transposed ? W[k * ldw + n] : W[n * ldw + k]) * sc, w1 = (transposed ? W[(k + 1) * ldw + n] : W[n * ldw + k + 1]) * sc;
-  const uint32_t hi = pack_f16(w0, w1);
-  const f32x2 h = unpack_f16(hi);
+  uint32_t hi, lo;
+  split_w(w0, w1, hi, lo);
   *reinterpret_cast<uint32_t *>(p0 + wplane_index(k, 0, n, N)) = hi;
-  *reinterpret_cast<uint32_t *>(p0 + wplane_index(k, 1, n, N)) = pack_f16(w0 - h.x, w1 - h.y);
+  *reinterpret_cast<uint32_t *>(p0 + wplane_index(k, 1, n, N)) = lo;
 }
 
+// amax[0] = bit pattern of max |W| (non-negative floats order like unsigned integers); zeroed by the host first
+__global__ __launch_bounds__(256) void w_amax_kernel(const float *__restrict__ W, int64_t ldw, int64_t N, int64_t K,
+                                                     uint32_t *__restrict__ amax) {
+  __shared__ float red[256];
+  float m = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N * K; i += (int64_t)gridDim.x * 256)
+    m = fmaxf(m, fabsf(W[(i / K) * ldw + i % K]));
+  block_max(m, red);
+  if (threadIdx.x == 0) atomicMax(amax, __float_as_uint(red[0]));
+}
 
 // TN = 128: 4 waves, three workgroups per CU.  SCHED selects the instruction-scheduling hint of the k-step.
 //
@@ -170,10 +170,10 @@ __global__ __launch_bounds__(2 * TN, 1024 / (2 * TN) >= 4 ? 3 : 2) void linear_n
     f16x8 a[2][2], b[3][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      a[0][i] = read_frag(pa, wr * 64 + i * 32 + l31, lh);
-      a[1][i] = read_frag(pa + APLANE, wr * 64 + i * 32 + l31, lh);
-      b[0][i] = read_frag(pb, wc * 64 + i * 32 + l31, lh);
-      b[1][i] = read_frag(pb + BPLANE, wc * 64 + i * 32 + l31, lh);
+      a[0][i] = frag_f16(pa + slot_dw(wr * 64 + i * 32 + l31, lh));
+      a[1][i] = frag_f16(pa + APLANE + slot_dw(wr * 64 + i * 32 + l31, lh));
+      b[0][i] = frag_f16(pb + slot_dw(wc * 64 + i * 32 + l31, lh));
+      b[1][i] = frag_f16(pb + BPLANE + slot_dw(wc * 64 + i * 32 + l31, lh));
       b[2][i] = scale_2m11(b[0][i]);
     }
 #pragma unroll
@@ -324,6 +324,14 @@ __global__ __launch_bounds__(256) void amax_rows_kernel(const float *__restrict_
 
 }  // namespace
 
+namespace svr {
+void w_amax_launch(const float *W, int64_t ldw, int64_t N, int64_t K, uint32_t *amax, hipStream_t s, unsigned grid) {
+  (void)hipMemsetAsync(amax, 0, sizeof(uint32_t), s);
+  if (!grid) grid = (unsigned)std::min<int64_t>(cdiv(N * K, 1024), 1024);
+  hipLaunchKernelGGL(w_amax_kernel, dim3(grid), dim3(256), 0, s, W, ldw, N, K, amax);
+}
+}  // namespace svr
+
 extern "C" int64_t svr_linear_fwd_f16x3_workspace(int64_t N, int64_t K) { return 2 * N * K * (int64_t)sizeof(uint16_t) + 512; }
 
 extern "C" int svr_linear_fwd_f16x3(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias, float *Y,
@@ -334,11 +342,10 @@ extern "C" int svr_linear_fwd_f16x3(const float *X, int64_t ldx, const float *W,
   SVR_CHECK((X || W) && (!X || Y) && workspace, SVR_E_BADARG, "linear_fwd_f16x3: null pointer");
   SVR_CHECK(M >= 0 && N > 0 && K > 0 && K % YK == 0, SVR_E_BADSHAPE, "linear_fwd_f16x3: M=%ld N=%ld K=%ld (K %% 16)", (long)M, (long)N, (long)K);
   hipStream_t s = (hipStream_t)stream;
-  uint32_t *amax = (uint32_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  uint32_t *amax = align256<uint32_t>(workspace);
   uint16_t *p0 = (uint16_t *)(amax + 64);
   if (W) {
-    (void)hipMemsetAsync(amax, 0, sizeof(uint32_t), s);
-    hipLaunchKernelGGL(w_amax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(N * K, 1024), 1024)), dim3(256), 0, s, W, ldw, N, K, amax);
+    w_amax_launch(W, ldw, N, K, amax, s);
     hipLaunchKernelGGL(split_w_kernel, dim3((unsigned)cdiv(N * (K / 2), 256)), dim3(256), 0, s, W, ldw, amax, p0, N, K, 0);
   }
   if (!X) return launch_status("linear_fwd_f16x3 (prepare)");
@@ -391,11 +398,10 @@ extern "C" int svr_linear_bwd_data_f16x3(const float *dY, int64_t lddy, const fl
     }
     return svr::linear_bwd_data_f16_nn(dY, lddy, W, ldw, dX, lddx, M, N, K, epilogue, mask, ldmask, amax_dy, amax_dx, workspace, s);
   }
-  uint32_t *amax = (uint32_t *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  uint32_t *amax = align256<uint32_t>(workspace);
   uint16_t *p0 = (uint16_t *)(amax + 64);
   if (W) {   // planes of W^T: K rows (dX columns) x N reduction elements
-    (void)hipMemsetAsync(amax, 0, sizeof(uint32_t), s);
-    hipLaunchKernelGGL(w_amax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(N * K, 1024), 1024)), dim3(256), 0, s, W, ldw, N, K, amax);
+    w_amax_launch(W, ldw, N, K, amax, s);
     hipLaunchKernelGGL(split_w_kernel, dim3((unsigned)cdiv(K * (N / 2), 256)), dim3(256), 0, s, W, ldw, amax, p0, K, N, 1);
   }
   if (!dY) return launch_status("linear_bwd_data_f16x3 (prepare)");

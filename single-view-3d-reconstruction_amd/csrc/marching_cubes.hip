@@ -20,6 +20,7 @@
 // Also here: svr_write_obj, the host-side .obj writer.
 #include "common.h"
 #include "mc_table.h"
+#include "reduce.h"
 #include <algorithm>
 #include <charconv>
 #include <cmath>
@@ -82,30 +83,8 @@ __global__ __launch_bounds__(kBlock) void mc_classify_kernel(const float *__rest
     nv_sum += nv;
     nt_sum += nt;
   }
-  // block totals: wave shuffles, then the 4 waves through LDS, then one atomic per total
-  uint64_t v = nv_sum, t = nt_sum;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    v += __shfl_xor(v, o);
-    t += __shfl_xor(t, o);
-  }
   __shared__ uint64_t part[2][kBlock / 64];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    part[0][w] = v;
-    part[1][w] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t sv = 0, st = 0;
-#pragma unroll
-    for (int q = 0; q < kBlock / 64; ++q) {
-      sv += part[0][q];
-      st += part[1][q];
-    }
-    if (sv) atomicAdd(&totals[0], (unsigned long long)sv);
-    if (st) atomicAdd(&totals[1], (unsigned long long)st);
-  }
+  block_add_totals_u64<kBlock>(nv_sum, nt_sum, part, totals);
 }
 
 __global__ __launch_bounds__(kBlock) void mc_emit_kernel(const float *__restrict__ field, Lattice L, double level,
@@ -149,7 +128,6 @@ __global__ __launch_bounds__(kBlock) void mc_emit_kernel(const float *__restrict
   }
 }
 
-int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 bool lattice(int32_t X, int32_t Y, int32_t Z, Lattice &L) {
   if (X < 0 || Y < 0 || Z < 0) return false;

@@ -23,8 +23,6 @@ using namespace svr;
 
 namespace {
 
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 struct Bricks {
   int32_t X, Y, Z, s, nbx, nby, nbz;
   int64_t n;  // bricks

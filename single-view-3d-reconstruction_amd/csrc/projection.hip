@@ -13,6 +13,7 @@
 // and the integer voxel indices are bit-exact.
 #include "common.h"
 #include "unproject.h"
+#include "reduce.h"
 
 using namespace svr;
 
@@ -173,12 +174,7 @@ __global__ __launch_bounds__(256) void blur_taps_grad_kernel(const float *__rest
   }
   __shared__ double red[256];
   for (int t = 0; t < K; ++t) {
-    red[threadIdx.x] = (double)s[t];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
+    block_sum_f64((double)s[t], red);
     if (threadIdx.x == 0) atomicAdd(gtaps + t, red[0]);
     __syncthreads();
   }
@@ -205,12 +201,7 @@ __global__ __launch_bounds__(256) void blur_taps_grad_parts_kernel(const float *
   }
   __shared__ double red[256];
   for (int t = 0; t < K; ++t) {
-    red[threadIdx.x] = (double)s[t];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
+    block_sum_f64((double)s[t], red);
     if (threadIdx.x == 0) part[(int64_t)blockIdx.x * K + t] = red[0];
     __syncthreads();
   }
@@ -358,7 +349,6 @@ __global__ __launch_bounds__(256) void splat_pull_kernel(float *__restrict__ acc
     }
 }
 
-int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 int64_t splat_cells(int B, int D0, int D1, int D2) { return (int64_t)B * (D0 + 1) * (D1 + 1) * (D2 + 1); }
 int splat_key_bits(int64_t cells) {  // the sentinel (= cells) must fit
   int nb = 1;
@@ -409,8 +399,8 @@ extern "C" int svr_voxelize_splat_fwd(const float *pts, float *acc, int32_t *bas
 extern "C" int64_t svr_voxelize_splat_ordered_workspace(int32_t B, int32_t N, int32_t D0, int32_t D1, int32_t D2) {
   if (!splat_ordered_fits(B, N, D0, D1, D2)) return SVR_E_UNSUPPORTED;
   const int64_t cells = splat_cells(B, D0, D1, D2), T = (int64_t)B * N;
-  int64_t bytes = 2 * al256((cells + 1) * 4) + al256((int64_t)svr::scan_max_i32_temp_bytes(cells + 1)) + 512;
-  if (T > 0) bytes += 4 * al256(T * 4) + al256(T * 16) + al256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32));
+  int64_t bytes = 2 * align256((cells + 1) * 4) + align256((int64_t)svr::scan_max_i32_temp_bytes(cells + 1)) + 512;
+  if (T > 0) bytes += 4 * align256(T * 4) + align256(T * 16) + align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32));
   return bytes;
 }
 
@@ -426,29 +416,29 @@ extern "C" int svr_voxelize_splat_fwd_ordered(const float *pts, float *acc, floa
   SVR_CHECK(acc && workspace, SVR_E_BADARG, "splat_fwd_ordered: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const int64_t cells = splat_cells(B, D0, D1, D2), T = (int64_t)B * N;
-  char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char *w = align256(workspace);
   int32_t *ends = (int32_t *)w;
-  w += al256((cells + 1) * 4);
+  w += align256((cells + 1) * 4);
   int32_t *cs = (int32_t *)w;
-  w += al256((cells + 1) * 4);
+  w += align256((cells + 1) * 4);
   void *scan_tmp = (void *)w;
   const size_t scan_bytes = svr::scan_max_i32_temp_bytes(cells + 1);
-  w += al256((int64_t)scan_bytes);
+  w += align256((int64_t)scan_bytes);
   hipError_t e = hipMemsetAsync(ends, 0, (size_t)(cells + 1) * sizeof(int32_t), s);
   SVR_CHECK(e == hipSuccess, (int)e, "splat_fwd_ordered: memset failed: %s", hipGetErrorString(e));
   const SplatRec *recs = nullptr;
   if (T > 0) {
     SVR_CHECK(pts, SVR_E_BADARG, "splat_fwd_ordered: null points");
     uint32_t *keys_in = (uint32_t *)w;
-    w += al256(T * 4);
+    w += align256(T * 4);
     int32_t *vals_in = (int32_t *)w;
-    w += al256(T * 4);
+    w += align256(T * 4);
     uint32_t *keys = (uint32_t *)w;
-    w += al256(T * 4);
+    w += align256(T * 4);
     int32_t *items = (int32_t *)w;
-    w += al256(T * 4);
+    w += align256(T * 4);
     SplatRec *rw = (SplatRec *)w;
-    w += al256(T * 16);
+    w += align256(T * 16);
     const uint32_t sentinel = (uint32_t)cells;
     const int bits = splat_key_bits(cells);
     hipLaunchKernelGGL(splat_key_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, s, pts, keys_in, vals_in, base, valid, T, N,

@@ -98,7 +98,6 @@ size_t rocprim_temp_bytes(int64_t total, int bits) {
   return tmp;
 }
 
-int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 int sort_points(const float *points, int32_t *order, float *sorted_points, int B, int N, int mode, int D, int H, int W,
                 int ac, void *workspace, hipStream_t s, const char *what) {

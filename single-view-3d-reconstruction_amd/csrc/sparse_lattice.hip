@@ -222,7 +222,6 @@ __global__ __launch_bounds__(kBlock) void sl_leak_kernel(const float *__restrict
   }
 }
 
-int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 bool grid(int32_t X, int32_t Y, int32_t Z, int32_t s, Grid &G) {
   if (X < 2 || Y < 2 || Z < 2 || s < 2) return false;

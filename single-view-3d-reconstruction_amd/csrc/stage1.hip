@@ -34,23 +34,12 @@
 // v_mfma_f32_16x16x32_f16 (H3): A[i = l15][k = 8 kq + m], B[k = 8 kq + m][j = l15], m = 0..7; D as above.
 #include "common.h"
 #include "f16x3.h"
+#include "reduce.h"
 
 using namespace svr;
 
-namespace svr {
-// bn_pool.hip
-void bn_stats_finalize_launch(const double *part, double *stats, int64_t rows, int C, int blocks, const float *gamma,
-                              const float *beta, float *rmean, float *rvar, float *ss, float *mean_f32, float eps, float momentum,
-                              hipStream_t s);
-void bn_sum_parts_launch(const double *part, double *out, int cols, int blocks, hipStream_t s);
-// conv3d.hip
-void conv3d_c1_wgrad_reduce_launch(const float *slab, float *dWp, int Co, int parts, int param_layout, const float *dbpart,
-                                   float *db, hipStream_t s);
-}  // namespace svr
-
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SB = 8;                      // brick edge (voxels)
 constexpr int HE = SB + 2;                 // halo tile edge (10 voxels)
@@ -183,12 +172,7 @@ __global__ __launch_bounds__(256) void stage1_kernel(const S1Args a) {
     float *redf = reinterpret_cast<float *>(redd);
     float m = fabsf(a.Wp[t]);                                      // 27 x 16 = 432 weights
     if (t + 256 < 27 * CO) m = fmaxf(m, fabsf(a.Wp[t + 256]));
-    redf[t] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (t < o) redf[t] = fmaxf(redf[t], redf[t + o]);
-      __syncthreads();
-    }
+    block_max(m, redf);
     const uint32_t amax = __float_as_uint(redf[0]);
     __syncthreads();   // (redd is used again at the end)
     const float wsc = w_scale(amax, false);
