@@ -858,6 +858,71 @@ int svr_mesh_df_eval(const double *tri, int64_t F, int32_t X, int32_t Y, int32_t
                      void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Ray casting a triangle mesh through the pipeline's pinhole camera: depth, distance, face and normal maps (no reference
+ * op: the reference's distance.exr came from a renderer that was never shipped; data_processing/render_view.py drives
+ * this, tests/raycast_oracle.py restates it in numpy).  Errors, ownership and streams as for svr_mc_*; one rounding per
+ * operation (no contraction).
+ *   tri: (F, 9) float64 on the device, a, b, c per face, in grid index space (the space of svr_mesh_df_*).
+ *   consts: the 12 float32 constants of svr_unproject_fwd in HOST memory, f, cx, cy, s00, t0, s11, t1, s22, t2, dims (dims
+ *   unused); each is widened to float64 first.  Image (H, W), 1 <= H, W <= 32768; pixel (u = column, v = row).
+ *   unproject_point sends pixel (u, v) at depth z to (s00*(u-cx)/f*z + t0, -s11*(v-cy)/f*z + t1, s22*z + t2), so the
+ *   pixel's ray has
+ *     o = (t0, t1, t2);   d = (s00 * (((double)u - cx) / f),  -(s11 * (((double)v - cy) / f)),  s22)
+ *   and the ray parameter is the depth in metres.  dot(x, y) := (x0*y0 + x1*y1) + x2*y2; cross products component by
+ *   component, (x1*y2 - x2*y1, x2*y0 - x0*y2, x0*y1 - x1*y0).  Per pair (pixel, face), all float64, in this order
+ *   (Moeller-Trumbore, two-sided; a comparison with NaN is false, so a NaN anywhere rejects the pair):
+ *     e1 = b - a;  e2 = c - a;  p = d x e2;  det = dot(e1, p);          det == 0: the face is skipped (edge-on, zero area)
+ *     inv = 1 / det;  s = o - a;  bu = dot(s, p) * inv;                 rejected unless 0 <= bu <= 1
+ *     q = s x e1;  bv = dot(d, q) * inv;                                rejected unless bv >= 0 and bu + bv <= 1
+ *     z = dot(e2, q) * inv;                                             accepted when near < z <= far
+ *   Per pixel: best = min z over the accepted faces in ascending index with a strict `<` (the lowest index wins a tie, a
+ *   NaN never wins).  Outputs, C order:
+ *     depth    (H, W) float32: (float)best; `miss` where no face was accepted (0.0 in the Python driver: svr_depth_grid_mark
+ *              sends it to index -8 on axis 2 and counts it out of range);
+ *     face     (H, W) int32, optional: the winner, -1 for a miss;
+ *     distance (H, W) float32, optional: the inverse of svr_distance_to_depth in the same float32 operations,
+ *              distance = depth * sqrt((float)(r*r + c*c) / (f*f) + 1), r = row - H/2, c = col - W/2 (integer division; f
+ *              the float32 constant), applied to the stored depth, `miss` included.  The ray uses cx, cy, the distance the
+ *              integer centres: exactly what unprojection and svr_distance_to_depth undo;
+ *     normal   (H, W, 3) float32, optional: n = e1 x e2 of the winner, len = sqrt(dot(n, n)), m = n / len per component,
+ *              m = -m when dot(m, d) > 0; (float)m; 0 for a miss;
+ *     shade    (H, W) uint8, optional: rint((255 * |dot(m, d)|) / sqrt(dot(d, d))) (half to even), 0 for a miss or NaN.
+ *   Cracks: a ray through a shared edge or vertex may be accepted by both faces, by one or by neither -- the two faces
+ *   round bu, bv independently.  Rays go through pixel centres, which makes this rare.  A face without area whose det
+ *   rounds to a non-zero value is not skipped; its bu, bv are then noise of size 1 / eps and all but never in range.
+ *   The image is cut into tiles of T x T pixels, T in {8, 16} (else SVR_E_BADSHAPE), numbered row by row; the last tile
+ *   per axis is partial.  Per tile a candidate list of face indices, ascending, that holds every face accepted by a pixel
+ *   of the tile (DESIGN.md section 19 has the argument and what it assumes); the maps do not depend on T, on the lists or
+ *   on how the tiles are batched: bit-identical to the rule above.
+ *   svr_raycast_tiles:           number of tiles (negative = SVR_E_BADSHAPE).
+ *   svr_raycast_workspace_bytes: device workspace of svr_raycast_count (negative = SVR_E_BADSHAPE).
+ *   svr_raycast_face_bounds:     rects (F, 4) int32 on the device, {x0, x1, y0, y1} inclusive: per vertex g
+ *                                zc = (g2 - t2) / s22, u = cx + (f*(g0 - t0)) / (s00*zc), v = cy - (f*(g1 - t1)) / (s11*zc);
+ *                                [floor(min u) - 1, ceil(max u) + 1] x [floor(min v) - 1, ceil(max v) + 1], each side clamped
+ *                                to +-2^30.  A face with a zc not above 2^-20, a |u| or |v| not <= 2^30 (NaN, inf) or
+ *                                max zc > 1024 * min zc gets {-2^30, 2^30, -2^30, 2^30}: every tile.
+ *   svr_raycast_count:           per tile the number of faces whose rectangle overlaps the tile's pixels, then an exclusive
+ *                                scan: offsets (tiles + 1 int64, device) -- offsets[tiles] is the total.  The caller reads
+ *                                offsets back and walks the tiles in batches whose lists fit its buffer.
+ *   svr_raycast_emit:            lists of tiles [b0, b1) into list (int32, `capacity` entries: no write goes past it; the
+ *                                caller sizes it offsets[b1] - offsets[b0]); the list of tile t starts at offsets[t] -
+ *                                offsets[b0].  Same rects, image and T as the count that filled offsets.
+ *   svr_raycast_eval:            the maps of tiles [b0, b1) from their lists (face, distance, normal, shade may be NULL).
+ *                                list == NULL: every face is a candidate of every tile (brute force; offsets is not read).
+ *                                A list entry outside [0, F) is ignored.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_raycast_tiles(int32_t H, int32_t W, int32_t T);
+int64_t svr_raycast_workspace_bytes(int32_t H, int32_t W, int32_t T);
+int svr_raycast_face_bounds(const double *tri, int64_t F, const float *consts /*[12]*/, int32_t *rects, void *stream);
+int svr_raycast_count(const int32_t *rects, int64_t F, int32_t H, int32_t W, int32_t T, void *ws, int64_t ws_bytes,
+                      int64_t *offsets, void *stream);
+int svr_raycast_emit(const int32_t *rects, int64_t F, int32_t H, int32_t W, int32_t T, const int64_t *offsets, int64_t b0,
+                     int64_t b1, int32_t *list, int64_t capacity, void *stream);
+int svr_raycast_eval(const double *tri, int64_t F, const float *consts /*[12]*/, int32_t H, int32_t W, int32_t T, double near_z,
+                     double far_z, float miss, const int64_t *offsets, const int32_t *list, int64_t b0, int64_t b1,
+                     float *depth, int32_t *face, float *distance, float *normal, uint8_t *shade, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * Host side (plain C++ + zlib; `out` / `payload` are HOST buffers, ideally pinned):

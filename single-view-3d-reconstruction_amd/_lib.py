@@ -169,6 +169,13 @@ SIGNATURES = {
     "svr_mesh_df_count": (C.c_int, [P, I64, I32, I32, I32, I32, C.c_double, C.c_double, P, I64, P, P]),
     "svr_mesh_df_emit": (C.c_int, [P, I64, I32, I32, I32, I32, P, P, I64, I64, P, I64, P]),
     "svr_mesh_df_eval": (C.c_int, [P, I64, I32, I32, I32, I32, C.c_double, P, P, I64, I64, P, P, P]),
+    "svr_raycast_tiles": (I64, [I32, I32, I32]),
+    "svr_raycast_workspace_bytes": (I64, [I32, I32, I32]),
+    "svr_raycast_face_bounds": (C.c_int, [P, I64, C.POINTER(F32), P, P]),
+    "svr_raycast_count": (C.c_int, [P, I64, I32, I32, I32, P, I64, P, P]),
+    "svr_raycast_emit": (C.c_int, [P, I64, I32, I32, I32, P, I64, I64, P, I64, P]),
+    "svr_raycast_eval": (C.c_int, [P, I64, C.POINTER(F32), I32, I32, I32, C.c_double, C.c_double, F32, P, P, I64, I64, P, P, P,
+                                   P, P, P]),
     "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),

@@ -34,6 +34,7 @@ SOURCES = {
     "voxel_mesh.hip": ["-ffp-contract=off"],
     "mesh_eval.hip": ["-ffp-contract=off"],
     "mesh_df.hip": ["-ffp-contract=off"],
+    "raycast.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "exr_io.cpp": [],
     "raw_sample.hip": ["-ffp-contract=off"],

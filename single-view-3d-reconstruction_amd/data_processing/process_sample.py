@@ -47,8 +47,22 @@ def _ensure_distance_field(sample, scene_mesh, down_scale_factor):
     mesh_to_df(sample / scene_mesh, target, dims=sample_dims(down_scale_factor))
 
 
-def _process_view(sample, out, intrinsic_path, down_scale_factor, sample_num, generator, copy_target, scene_mesh=None):
+def _ensure_view(sample, scene_mesh, intrinsic_path, down_scale_factor):
+    """`scene_mesh` given and no distance.exr in the view: ray-cast <sample>/<scene_mesh> through the view's camera
+    (data_processing.render_view) and write distance.exr -- and rgb.png when that is absent too -- next to the raw files.
+    Existing files are not touched."""
+    if scene_mesh is None or (sample / "distance.exr").exists():
+        return
+    from .render_view import render_view        # imports this module (through mesh_to_df) for EmptyMeshError
+    render_view(sample / scene_mesh, sample, intrinsic=intrinsic_path, scale_factor=down_scale_factor,
+                write_rgb=not (sample / "rgb.png").exists())
+
+
+def _process_view(sample, out, intrinsic_path, down_scale_factor, sample_num, generator, copy_target, scene_mesh=None,
+                  render_missing=False):
     dims = sample_dims(down_scale_factor)
+    if render_missing:
+        _ensure_view(sample, scene_mesh, intrinsic_path, down_scale_factor)
     _ensure_distance_field(sample, scene_mesh, down_scale_factor)
     distance = sample_io.exr_read(sample / "distance.exr", "R")
     grid, out_of_range = depth_grid(distance, dims, intrinsic_path, down_scale_factor)
@@ -72,7 +86,8 @@ def _process_view(sample, out, intrinsic_path, down_scale_factor, sample_num, ge
                  grid_coords=grid_coords.cpu().numpy())
 
 
-def process_sample(dataset_path, splitsdir, sample_name, down_scale_factor=1, sample_num=100000, generator=None, scene_mesh=None):
+def process_sample(dataset_path, splitsdir, sample_name, down_scale_factor=1, sample_num=100000, generator=None, scene_mesh=None,
+                   render_missing=False):
     """raw/<splitsdir>/<sample_name> -> processed/<splitsdir>/<sample_name> (+ mesh.obj next to the raw files).
     `generator`: a torch.Generator for sample_points' draws.
 
@@ -84,20 +99,26 @@ def process_sample(dataset_path, splitsdir, sample_name, down_scale_factor=1, sa
     The written file has the extents sample_dims(down_scale_factor); the unchanged rest reads it like any
     distance_field.df, i.e. read_df block-averages it by down_scale_factor once more -- so with a factor other than 1 write
     the full-resolution field yourself (mesh_to_df with the mesh in full-resolution grid units) instead of using
-    `scene_mesh`."""
+    `scene_mesh`.
+
+    `render_missing` (default False: nothing changes): with `scene_mesh`, a view without distance.exr gets one ray-cast from
+    the mesh through the view's intrinsic.txt first (data_processing.render_view), and a grey stand-in rgb.png when that
+    is absent too; existing files are not touched."""
     if scene_mesh == "mesh.obj":
         raise ValueError("process_sample: scene_mesh must not be mesh.obj, the file this function writes")
     sample = Path(dataset_path) / "raw" / splitsdir / sample_name
     out = Path(dataset_path) / "processed" / splitsdir / sample_name
     out.mkdir(exist_ok=True, parents=True)
-    _process_view(sample, out, sample / "intrinsic.txt", down_scale_factor, sample_num, generator, True, scene_mesh)
+    _process_view(sample, out, sample / "intrinsic.txt", down_scale_factor, sample_num, generator, True, scene_mesh, render_missing)
 
 
-def process_sample_pipeline(dataset_path, splitsdir, down_scale_factor=1, sample_num=100000, generator=None, scene_mesh=None):
+def process_sample_pipeline(dataset_path, splitsdir, down_scale_factor=1, sample_num=100000, generator=None, scene_mesh=None,
+                            render_missing=False):
     """Every <dataset_path>/<splitsdir>/<scene>/<view>, processed in place with <dataset_path>/intrinsics.txt
     (process_sample.py:32-72; like there, no target.df copy).  A view with out-of-range depth (IndexError) or an empty
     mesh (AttributeError; an empty `scene_mesh` included) is moved to <dataset_path>/quarantine/<splitsdir>/<scene>/<view>.
-    `scene_mesh`: as for process_sample.  -> the quarantined paths."""
+    `scene_mesh`, `render_missing`: as for process_sample (the camera is <dataset_path>/intrinsics.txt).  -> the quarantined
+    paths."""
     if scene_mesh == "mesh.obj":
         raise ValueError("process_sample_pipeline: scene_mesh must not be mesh.obj, the file this function writes")
     d_path = Path(dataset_path) / splitsdir
@@ -107,7 +128,7 @@ def process_sample_pipeline(dataset_path, splitsdir, down_scale_factor=1, sample
             sample = d_path / scene / view
             try:
                 _process_view(sample, sample, Path(dataset_path) / "intrinsics.txt", down_scale_factor, sample_num, generator, False,
-                              scene_mesh)
+                              scene_mesh, render_missing)
             except (IndexError, AttributeError) as e:
                 quarantine = Path(dataset_path) / "quarantine" / splitsdir / scene / view
                 print(f"{type(e).__name__}: {e}; moving {sample} to {quarantine}")

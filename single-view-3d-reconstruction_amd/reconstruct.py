@@ -47,10 +47,26 @@ SPACES = ("grid", "normalized", "camera")
 class Reconstruction:
     """One view's result (module docstring)."""
 
-    def __init__(self, depth, point_cloud, voxel_occupancy, vertices, faces, scale_factor, inf_res, scale_shift):
+    def __init__(self, depth, point_cloud, voxel_occupancy, vertices, faces, scale_factor, inf_res, scale_shift, intrinsic=None):
         self.depth, self.point_cloud, self.voxel_occupancy = depth, point_cloud, voxel_occupancy
         self.vertices, self.faces = vertices, faces
         self._scale_factor, self._inf_res, self._scale_shift = scale_factor, int(inf_res), scale_shift
+        self._intrinsic = intrinsic                     # 4x4 of the input camera; None: the pipeline's default
+
+    def render_depth(self, size=None, **kw):
+        """The predicted mesh ray-cast from the input camera (data_processing.render_view.render_depth; `kw` goes there):
+        the (H, W) depth map on the device, 0 where no face is hit, or None when the mesh has no face.  `size` defaults to
+        the input depth map's.  The vertices are divided by inf_res first, as vertices_in("camera") does."""
+        from .data_processing.render_view import render_depth
+        if self.faces is None or int(self.faces.shape[0]) == 0:
+            return None
+        K = self._intrinsic if self._intrinsic is not None else get_intrinsic()
+        consts = [float(K[0][0]), float(K[0][2]), float(K[1][2])] + [float(v) for v in self._scale_shift] + [0.0, 0.0, 0.0]
+        if size is None:
+            size = tuple(self.depth.shape[-2:]) if self.depth is not None else (240, 320)
+        v = self.vertices if self._inf_res == 1 else self.vertices / float(self._inf_res)
+        as_host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)      # noqa: E731
+        return render_depth((as_host(v), as_host(self.faces)), size=size, consts=consts, **kw)
 
     def vertices_in(self, space):
         """The predicted mesh's vertices in `space`: a device tensor ("grid", "camera") or a float32 numpy array ("normalized":
@@ -128,7 +144,8 @@ class Reconstructor:
         for i in range(depth.shape[0]):
             vox = voxel_occupancy[i]
             vertices, faces = implicit_to_vertices(m.ifnet, vox.reshape(1, 1, *vox.shape[-3:]), dims, 0.5, inf_res, self.block)
-            views.append(Reconstruction(depth[i], point_cloud[i], vox, vertices, faces, h.scale_factor, inf_res, scale_shift))
+            views.append(Reconstruction(depth[i], point_cloud[i], vox, vertices, faces, h.scale_factor, inf_res, scale_shift,
+                                        m.project.intrinsic))
         return views
 
     def preprocess(self, pixels, flip=False):
