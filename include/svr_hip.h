@@ -286,7 +286,10 @@ int svr_linear_fwd_f16x3(const float *X, int64_t ldx, const float *W, int64_t ld
 /* The same two backward products on the bf16 matrix cores with a 3-term split (x = hi + mid, products
  * hi*hi + hi*mid + mid*hi, f32 accumulation): ~1.5e-5 relative error per product, ~5x fewer matrix-core
  * cycles than the exact-f32 MFMA.  Backward only -- the forward pass (logits, ReLU masks) stays exact f32.
- * bwd_data workspace: svr_linear_bwd_data_bf16x3_workspace(N, K) bytes (split + transposed weight planes). */
+ * bwd_data workspace: svr_linear_bwd_data_bf16x3_workspace(N, K) bytes (split + transposed weight planes).
+ * bwd_data needs N % 32 == 0, K % 4 == 0, and dX and the mask float4-able (16-byte aligned, leading dimensions multiples
+ * of 4: SVR_E_ALIGN / SVR_E_BADSHAPE otherwise); bwd_weight takes any K and any X layout (a slower path where K % 4 != 0
+ * or X is not float4-able).                                                                                              */
 int64_t svr_linear_bwd_data_bf16x3_workspace(int64_t N, int64_t K);
 int svr_linear_bwd_data_bf16x3(const float *dY, int64_t lddy, const float *W, int64_t ldw, float *dX,
                                int64_t lddx, int64_t M, int64_t N, int64_t K, int epilogue,
@@ -306,8 +309,8 @@ int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const float *X, 
  * bound) on entry -- the library launches no memset for it.
  * amax_dy == NULL: no scaling (values must then lie in f16's range).  The weight operand is normalised the same way when
  * its planes are prepared (PREPARE / RUN as above: dY NULL = prepare from W, W NULL = run); the activation operand X of
- * the weight gradient is taken as it is (|x| < 65504; below |x| ~ 0.1 its correction term has an absolute error floor of
- * 3e-8 |dY|).  Errors against f64: ~3e-7 (the exact-f32 kernels' own level), bf16x3: ~1e-5.                              */
+ * the weight gradient is taken as it is (|x| < 65504; below |x| ~ 1e-4 its correction term has an absolute error floor of
+ * 1.5e-11 |dY|).  Errors against f64: ~3e-7 (the exact-f32 kernels' own level), bf16x3: ~1e-5.                              */
 int svr_amax_f32(const float *X, int64_t ld, int64_t M, int64_t N, uint32_t *amax, void *stream);
 int64_t svr_linear_bwd_data_f16x3_workspace(int64_t N, int64_t K);
 int svr_linear_bwd_data_f16x3(const float *dY, int64_t lddy, const float *W, int64_t ldw, float *dX,
@@ -318,6 +321,44 @@ int64_t svr_linear_bwd_weight_f16x3_workspace(int64_t M, int64_t N, int64_t K);
 int svr_linear_bwd_weight_f16x3(const float *dY, int64_t lddy, const float *X, int64_t ldx, float *dW,
                                 int64_t lddw, float *db, int64_t M, int64_t N, int64_t K,
                                 const uint32_t *amax_dy, void *workspace, void *stream);
+
+/* What a linear entry point above does with a call (the launchers ask the same function).  Host only: no device memory is
+ * touched, callable without a GPU.  op = SVR_LIN_*; M, N, K as the entry point takes them (x (M,K), w (N,K), dy (M,N));
+ * ld_a / ld_b / ld_out / ld_mask and lo_a / lo_b / lo_out / lo_mask are the leading dimensions and the low four address bits
+ * of the first operand (X forward, dY backward), the second (W; X of backward-weight), the output (Y / dX / dW) and the
+ * mask; epilogue = SVR_EPI_*; want_bias: backward-weight is asked for db.  Outputs (each may be NULL):
+ *   kernel: SVR_LIN_K_*;  coalesced: 1 = the tile leaves through LDS as float4 rows, 0 = one dword per lane;
+ *   splits / rows_per_split: reduction splits of backward-weight (1 / M elsewhere);
+ *   bias_form: SVR_LIN_BIAS_* -- where db comes from;
+ *   status: what the entry point would return for these operands, SVR_OK or its refusal (outputs past the refused check
+ *   are not meaningful).  The return value is SVR_E_BADARG for an unknown op, else SVR_OK.                                   */
+#define SVR_LIN_FWD_F32 0
+#define SVR_LIN_FWD_F16X3 1
+#define SVR_LIN_FWD_BF16X6 2
+#define SVR_LIN_BWD_DATA_F32 3
+#define SVR_LIN_BWD_DATA_F16X3S 4
+#define SVR_LIN_BWD_DATA_BF16X3 5
+#define SVR_LIN_BWD_WEIGHT_F32 6
+#define SVR_LIN_BWD_WEIGHT_F16X3S 7
+#define SVR_LIN_BWD_WEIGHT_BF16X3 8
+#define SVR_LIN_K_NT 0          /* exact f32: linear_nt_kernel                                              */
+#define SVR_LIN_K_NN 1          /*            linear_nn_kernel                                              */
+#define SVR_LIN_K_TN 2          /*            linear_tn_kernel + slab_reduce_kernel                         */
+#define SVR_LIN_K_NT128 3       /* linear_nt_h3_kernel<128>                                                 */
+#define SVR_LIN_K_NT64 4        /* linear_nt_h3_kernel<64> (N <= 64)                                        */
+#define SVR_LIN_K_NT128_BWD 5   /* linear_nt_h3_kernel<128, BWD> on transposed planes                       */
+#define SVR_LIN_K_NN_X3 6       /* linear_nn_x3_kernel (bf16 or scaled f16 split)                           */
+#define SVR_LIN_K_TN_TR 7       /* linear_tn_x3_tr_kernel + slab_reduce_x3_kernel                           */
+#define SVR_LIN_K_TN_PREPASS 8  /* dy_planes_kernel + linear_tn_x3_kernel + slab_reduce_x3_kernel           */
+#define SVR_LIN_K_NT_X6 9       /* linear_nt_x6_kernel                                                      */
+#define SVR_LIN_BIAS_NONE 0
+#define SVR_LIN_BIAS_KERNEL 1       /* column sums of the dY rows the weight-gradient kernel loads          */
+#define SVR_LIN_BIAS_COLSUM_VEC 2   /* colsum_partial_kernel (float4)                                       */
+#define SVR_LIN_BIAS_COLSUM_SLOW 3  /* colsum_partial_slow_kernel (one thread per column)                   */
+int svr_linear_variant(int32_t op, int64_t M, int64_t N, int64_t K, int64_t ld_a, int64_t ld_b, int64_t ld_out,
+                       int64_t ld_mask, int32_t lo_a, int32_t lo_b, int32_t lo_out, int32_t lo_mask, int32_t epilogue,
+                       int32_t want_bias, int32_t *kernel, int32_t *coalesced, int32_t *splits, int64_t *rows_per_split,
+                       int32_t *bias_form, int32_t *status);
 
 /* fc_out (Conv1d(hidden,1,1), model/ifnet.py:35,58-59): logits[r(m)] = H[m,:].w + b, where
  * r(m) = row_map[m] if row_map != NULL (rows were processed in Morton order: scatter the logits back

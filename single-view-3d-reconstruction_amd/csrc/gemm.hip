@@ -220,10 +220,10 @@ __global__ __launch_bounds__(256) void fc_out_bwd_kernel(const float *__restrict
   if (amax_dh) {  // (uniform)
 svr_amax_publish(amax_dh, vmax);
   }
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int64_t m = r0; m < r1; ++m) s += dlogits[row_map ? (int64_t)row_map[m] : m];
-    part[(int64_t)blockIdx.x * (K + 1) + K] = s;
+  if (threadIdx.x == 0) {  // db: up to 512 terms in one chain -- in f64, as every other long sum here (an f32 chain was 1e-6 off at 512 rows)
+    double s = 0.0;
+    for (int64_t m = r0; m < r1; ++m) s += (double)dlogits[row_map ? (int64_t)row_map[m] : m];
+    part[(int64_t)blockIdx.x * (K + 1) + K] = (float)s;
   }
 }
 
@@ -272,9 +272,9 @@ svr_amax_publish(amax_dh, vmax);
   __syncthreads();
   part[(int64_t)blockIdx.x * 257 + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
   if (t == 0) {
-    float sb = 0.f;
-    for (int i = 0; i < nr; ++i) sb += gs[i];
-    part[(int64_t)blockIdx.x * 257 + 256] = sb;
+    double sb = 0.0;  // (f64: see fc_out_bwd_kernel)
+    for (int i = 0; i < nr; ++i) sb += (double)gs[i];
+    part[(int64_t)blockIdx.x * 257 + 256] = (float)sb;
   }
 }
 
@@ -356,18 +356,6 @@ int check_epi(int epilogue, const float *bias, const float *mask) {
   return SVR_OK;
 }
 
-int tn_splits(int64_t M, int64_t N, int64_t K, int *steps_per_split) {
-  int64_t tiles = cdiv(N, 128) * cdiv(K, 128);
-  int64_t steps = cdiv(M, BK);
-  int64_t want = cdiv(2048, tiles);  // ~2048 workgroups
-  int64_t splits = want < 1 ? 1 : want;
-  if (splits > steps) splits = steps > 0 ? steps : 1;
-  int64_t sps = cdiv(steps, splits);
-  splits = steps > 0 ? cdiv(steps, sps) : 1;
-  *steps_per_split = (int)sps;
-  return (int)splits;
-}
-
 
 }  // namespace
 
@@ -384,8 +372,7 @@ int64_t colsum_workspace_floats(int64_t M, int64_t N) { return cdiv(M > 0 ? M : 
 void colsum_launch(const float *Y, int64_t ldy, float *out, float *part, int64_t M, int64_t N, hipStream_t s) {
   int64_t rpc = colsum_rows_per_chunk(M);
   int chunks = (int)cdiv(M, rpc);
-  bool vec = N % 4 == 0 && N / 4 <= 256 && 256 % (N / 4) == 0 && ldy % 4 == 0 && ((uintptr_t)Y & 15) == 0;
-  if (vec)
+  if (colsum_vec(N, ldy, (uintptr_t)Y))
     hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)chunks), dim3(256), 0, s, Y, ldy, part, M, N, rpc);
   else
     hipLaunchKernelGGL(colsum_partial_slow_kernel, dim3((unsigned)chunks, (unsigned)cdiv(N, 64)), dim3(64), 0, s, Y, ldy, part, M, N, rpc);
@@ -398,10 +385,9 @@ extern "C" int svr_linear_fwd(const float *X, int64_t ldx, const float *W, int64
                               int64_t ldmask, void *stream) {
   if (M == 0) return SVR_OK;  // empty point set
   SVR_CHECK(X && W && Y, SVR_E_BADARG, "linear_fwd: null pointer");
-  SVR_CHECK(M >= 0 && N > 0 && K > 0 && K % BK == 0, SVR_E_BADSHAPE, "linear_fwd: M=%ld N=%ld K=%ld (K %% 16)", (long)M, (long)N, (long)K);
-  SVR_CHECK(ldx % 4 == 0 && ldw % 4 == 0 && (((uintptr_t)X | (uintptr_t)W) & 15) == 0, SVR_E_ALIGN, "linear_fwd: operands must be 16-byte aligned");
+  LinPlan plan;
+  if (int rc = lin_plan(LinQuery{SVR_LIN_FWD_F32, M, N, K, ldx, ldw, ldy, ldmask, lo4(X), lo4(W), lo4(Y), lo4(mask), epilogue, 0, 1}, plan)) return rc;
   if (int rc = check_epi(epilogue, bias, mask)) return rc;
-  if (M == 0) return SVR_OK;
   EpiArgs e{Y, ldy, bias, mask, ldmask, epilogue};
   dim3 grid((unsigned)cdiv(N, Cfg128::BN), (unsigned)cdiv(M, Cfg128::BM));
   hipLaunchKernelGGL(linear_nt_kernel, grid, dim3(256), 0, (hipStream_t)stream, X, ldx, W, ldw, e, M, N, K);
@@ -413,11 +399,9 @@ extern "C" int svr_linear_bwd_data(const float *dY, int64_t lddy, const float *W
                                    void *stream) {
   if (M == 0) return SVR_OK;
   SVR_CHECK(dY && W && dX, SVR_E_BADARG, "linear_bwd_data: null pointer");
-  SVR_CHECK(M >= 0 && N > 0 && K > 0 && N % BK == 0 && K % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_data: M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-  SVR_CHECK(lddy % 4 == 0 && ldw % 4 == 0 && (((uintptr_t)dY | (uintptr_t)W) & 15) == 0, SVR_E_ALIGN, "linear_bwd_data: operands must be 16-byte aligned");
-  SVR_CHECK(epilogue == SVR_EPI_NONE || epilogue == SVR_EPI_MASK, SVR_E_BADARG, "linear_bwd_data: epilogue %d", epilogue);
+  LinPlan plan;
+  if (int rc = lin_plan(LinQuery{SVR_LIN_BWD_DATA_F32, M, N, K, lddy, ldw, lddx, ldmask, lo4(dY), lo4(W), lo4(dX), lo4(mask), epilogue, 0, 1}, plan)) return rc;
   if (int rc = check_epi(epilogue, nullptr, mask)) return rc;
-  if (M == 0) return SVR_OK;
   EpiArgs e{dX, lddx, nullptr, mask, ldmask, epilogue};
   dim3 grid((unsigned)cdiv(K, Cfg128::BN), (unsigned)cdiv(M, Cfg128::BM));
   hipLaunchKernelGGL(linear_nn_kernel, grid, dim3(256), 0, (hipStream_t)stream, dY, lddy, W, ldw, e, M, N, K);
@@ -426,24 +410,40 @@ extern "C" int svr_linear_bwd_data(const float *dY, int64_t lddy, const float *W
 
 extern "C" int64_t svr_linear_bwd_weight_workspace(int64_t M, int64_t N, int64_t K) {
   int sps;
-  int splits = tn_splits(M, N, K, &sps);
+  int splits = tn_splits_f32(M, N, K, &sps);
   return ((int64_t)splits * N * K + colsum_workspace_floats(M, N)) * (int64_t)sizeof(float);
 }
 
 extern "C" int svr_linear_bwd_weight(const float *dY, int64_t lddy, const float *X, int64_t ldx, float *dW, int64_t lddw,
                                      float *db, int64_t M, int64_t N, int64_t K, void *workspace, void *stream) {
   SVR_CHECK(dY && X && dW && workspace, SVR_E_BADARG, "linear_bwd_weight: null pointer");
-  SVR_CHECK(M > 0 && N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_weight: M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-  SVR_CHECK(lddy % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)dY | (uintptr_t)X) & 15) == 0, SVR_E_ALIGN, "linear_bwd_weight: operands must be 16-byte aligned");
+  LinPlan plan;
+  if (int rc = lin_plan(LinQuery{SVR_LIN_BWD_WEIGHT_F32, M, N, K, lddy, ldx, lddw, 0, lo4(dY), lo4(X), lo4(dW), 0, SVR_EPI_NONE, db != nullptr, 1}, plan)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int sps;
-  int splits = tn_splits(M, N, K, &sps);
+  const int splits = plan.splits, sps = (int)(plan.rows_per_split / BK);
   float *slab = (float *)workspace;
   dim3 grid((unsigned)cdiv(K, Cfg128::BN), (unsigned)cdiv(N, Cfg128::BM), (unsigned)splits);
   hipLaunchKernelGGL(linear_tn_kernel, grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, M, N, K, sps);
   hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)cdiv(N * K, 256)), dim3(256), 0, s, slab, dW, N, K, lddw, splits);
   if (db) colsum_launch(dY, lddy, db, slab + (int64_t)splits * N * K, M, N, s);
   return launch_status("linear_bwd_weight");
+}
+
+extern "C" int svr_linear_variant(int32_t op, int64_t M, int64_t N, int64_t K, int64_t ld_a, int64_t ld_b, int64_t ld_out, int64_t ld_mask,
+                                  int32_t lo_a, int32_t lo_b, int32_t lo_out, int32_t lo_mask, int32_t epilogue, int32_t want_bias,
+                                  int32_t *kernel, int32_t *coalesced, int32_t *splits, int64_t *rows_per_split, int32_t *bias_form,
+                                  int32_t *status) {
+  SVR_CHECK(op >= SVR_LIN_FWD_F32 && op <= SVR_LIN_BWD_WEIGHT_BF16X3, SVR_E_BADARG, "linear_variant: op %d", op);
+  LinPlan plan;
+  const int rc = lin_plan(LinQuery{op, M, N, K, ld_a, ld_b, ld_out, ld_mask, (unsigned)lo_a & 15, (unsigned)lo_b & 15, (unsigned)lo_out & 15,
+                                   (unsigned)lo_mask & 15, epilogue, want_bias, 1}, plan);
+  if (kernel) *kernel = plan.kernel;
+  if (coalesced) *coalesced = plan.coalesced;
+  if (splits) *splits = plan.splits;
+  if (rows_per_split) *rows_per_split = plan.rows_per_split;
+  if (bias_form) *bias_form = plan.bias;
+  if (status) *status = rc;
+  return SVR_OK;
 }
 
 extern "C" int svr_fc_out_fwd(const float *H, int64_t ldh, const float *w, const float *b, float *logits,

@@ -18,6 +18,8 @@
 // so the fragment reads (ds_read_b128, lane <-> row) and the transposing stores (ds_write_b128) are conflict free.
 // Tiles that share an operand panel are dispatched to one XCD (common.h: xcd_logical).
 #include "common.h"
+#define SVR_GEMM_PLAN_ONLY
+#include "gemm_core.h"
 #include "conv2d_virt.h"
 #include "f16x3.h"
 
@@ -449,9 +451,9 @@ __device__ __forceinline__ bf16x8 tr_frag(const uint32_t *plane, int byte0, int 
 // (768 cycles), and the LDS pipe of a CU is ~80 % busy relative to its matrix pipes.  The two-stage form was dropped.
 // F16 ("f16x3s", svr_linear_bwd_weight_f16x3): the scaled f16 split instead of the bf16 one -- dY is multiplied by 2^s (amax_dy:
 // its |max| brought to [2^13, 2^14), exact), both operands split into hi = rn16(v) and lo' = rn16((v - hi) 2^11), products
-// hi hi + (hi 2^-11) lo' + lo' (hi 2^-11) with the 2^-11 applied to the hi FRAGMENTS in registers (v_pk_mul_f16), result * 2^-s:
+// hi hi + (hi 2^-11) lo' + (lo' 2^-11) hi with both 2^-11 applied to the dY FRAGMENTS in registers (v_pk_mul_f16), result * 2^-s:
 // 22 mantissa bits per operand instead of 16, the same three matrix instructions per block.  X (activations) is not scaled:
-// |x| < 65504, and below |x| ~ 0.1 the correction term carries an absolute error floor of 3e-8 |dY| (gemm_f16x3.hip).
+// |x| < 65504, and only lo'(x) can leave f16's normal range (below |x| ~ 1e-4: an absolute error floor of 1.5e-11 |dY|).
 // CONV (UNet weight gradients as an implicit GEMM, conv2d_igemm.hip): X is not a matrix in memory -- row m is output pixel
 // (b, oy, ox), column j = (tap, c) of the reduction order, and X[m][j] = act(in)[b][oy s - p + ky][ox s - p + kx][c] is
 // gathered from the channels-last input (zero outside the image); a thread's columns, hence its tap and channel, are fixed
@@ -587,7 +589,10 @@ __global__ __launch_bounds__(256, 2) void linear_tn_x3_tr_kernel(const float *__
         bm[j] = tr_frag(lx + TR_XPLANE, boff[ks][j][0], boff[ks][j][1]);
       }
       if constexpr (F16) {   // the same 16-bit lanes read as halves
-        f16x8 fah[2], fam[2], fbh[2], fbm[2], fahs[2], fbhs[2];
+        // both 2^-11 go on the dY side: dY sits in [2^13, 2^14) by its scale, so hi(dY) 2^-11 and lo'(dY) 2^-11 stay normal f16,
+        // while hi(x) 2^-11 is subnormal below |x| = 0.125 (x is not scaled) and lost bits there: 2.3e-7 instead of 8.6e-8 of
+        // a one-row product with x = 0.087
+        f16x8 fah[2], fam[2], fbh[2], fbm[2], fahs[2], fams[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           fah[j] = __builtin_bit_cast(f16x8, ah[j]);
@@ -595,7 +600,7 @@ __global__ __launch_bounds__(256, 2) void linear_tn_x3_tr_kernel(const float *__
           fbh[j] = __builtin_bit_cast(f16x8, bh[j]);
           fbm[j] = __builtin_bit_cast(f16x8, bm[j]);
           fahs[j] = scale_2m11(fah[j]);
-          fbhs[j] = scale_2m11(fbh[j]);
+          fams[j] = scale_2m11(fam[j]);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -604,7 +609,7 @@ __global__ __launch_bounds__(256, 2) void linear_tn_x3_tr_kernel(const float *__
           }
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fam[i], fbhs[j], acc[i][j], 0, 0, 0);   // lo'(dY) hi(x) 2^-11
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fams[i], fbh[j], acc[i][j], 0, 0, 0);   // lo'(dY) 2^-11 hi(x)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fahs[i], fbm[j], acc[i][j], 0, 0, 0);   // hi(dY) 2^-11 lo'(x)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[i], fbh[j], acc[i][j], 0, 0, 0);
           }
@@ -731,15 +736,7 @@ __global__ __launch_bounds__(256) void slab_reduce_x3_kernel(const float *__rest
   }
 }
 
-int tn_splits(int64_t M, int64_t N, int64_t K, int64_t *rows_per_split) {
-  int64_t tiles = cdiv(N, TN_TM) * cdiv(K, TN_TN);
-  int64_t want = cdiv(1536, tiles);  // three 4-wave workgroups per CU, two rounds
-  if (want < 1) want = 1;
-  int64_t rps = cdiv(cdiv(M, want), XK) * XK;  // multiple of the k-step
-  if (rps < XK) rps = XK;
-  *rows_per_split = rps;
-  return (int)cdiv(M, rps);
-}
+static_assert(TN_TM == 128 && TN_TN == 128 && XK == 32, "tn_splits_x3 (gemm_core.h) counts 128 x 128 tiles and k-steps of 32");
 
 }  // namespace
 
@@ -751,16 +748,15 @@ extern "C" int svr_linear_bwd_data_bf16x3(const float *dY, int64_t lddy, const f
   // dY == NULL: PREPARE only (W -> split planes in the workspace);  W == NULL: RUN on a workspace prepared earlier
   if (M == 0 && dY) return SVR_OK;
   SVR_CHECK((dY || W) && (!dY || dX) && workspace, SVR_E_BADARG, "linear_bwd_data_bf16x3: null pointer");
-  SVR_CHECK(M >= 0 && N > 0 && K > 0 && N % XK == 0 && K % 4 == 0, SVR_E_BADSHAPE,
-            "linear_bwd_data_bf16x3: M=%ld N=%ld K=%ld (need N %% 32 == 0, K %% 4 == 0)", (long)M, (long)N, (long)K);
+  LinPlan plan;   // a PREPARE call gets the shape checks alone
+  if (int rc = lin_plan(LinQuery{SVR_LIN_BWD_DATA_BF16X3, M, N, K, lddy, ldw, lddx, ldmask, lo4(dY), lo4(W), lo4(dX), lo4(mask), epilogue, 0,
+                                 dY != nullptr}, plan)) return rc;
+  SVR_CHECK(!dY || epilogue != SVR_EPI_MASK || mask, SVR_E_BADARG, "linear_bwd_data_bf16x3: epilogue %d needs the mask", epilogue);
   hipStream_t s = (hipStream_t)stream;
   uint16_t *hi = (uint16_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   uint16_t *mid = hi + N * K;
   if (W) hipLaunchKernelGGL(pack_planes_kernel, dim3((unsigned)cdiv(K * (N / 2), 256)), dim3(256), 0, s, W, ldw, hi, mid, N, K);
   if (!dY) return launch_status("linear_bwd_data_bf16x3 (prepare)");
-  SVR_CHECK(lddx % 4 == 0 && ldmask % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_data_bf16x3: leading dimensions must be multiples of 4");
-  SVR_CHECK(lddy % 4 == 0 && ((uintptr_t)dY & 15) == 0, SVR_E_ALIGN, "linear_bwd_data_bf16x3: dY must be 16-byte aligned");
-  SVR_CHECK(epilogue == SVR_EPI_NONE || (epilogue == SVR_EPI_MASK && mask), SVR_E_BADARG, "linear_bwd_data_bf16x3: epilogue %d", epilogue);
   dim3 grid(xcd_grid(cdiv(K, NN_TN) * cdiv(M, NN_TM)));
   hipLaunchKernelGGL(linear_nn_x3_kernel<false>, grid, dim3(256), 0, s, dY, lddy, hi, mid, dX, lddx,
                      epilogue == SVR_EPI_MASK ? mask : nullptr, ldmask, M, N, K, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
@@ -795,7 +791,7 @@ int64_t tn_mpad(int64_t M) { return cdiv(M, 64) * 64; }
 
 extern "C" int64_t svr_linear_bwd_weight_bf16x3_workspace(int64_t M, int64_t N, int64_t K) {
   int64_t rps;
-  int splits = tn_splits(M, N, K, &rps);
+  int splits = tn_splits_x3(M, N, K, &rps);
   // slabs | dY planes (hi, mid) | per-row-tile column sums
   const int64_t dbparts = cdiv(M, 64) > splits ? cdiv(M, 64) : splits;  // row tiles (pre-pass) or splits (tr kernel)
   return align256((int64_t)splits * N * K * 4) + 2 * align256(N * tn_mpad(M) * 2) + align256(dbparts * N * 4) + 256;
@@ -805,11 +801,11 @@ extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const
                                             int64_t lddw, float *db, int64_t M, int64_t N, int64_t K, void *workspace,
                                             void *stream) {
   SVR_CHECK(dY && X && dW && workspace, SVR_E_BADARG, "linear_bwd_weight_bf16x3: null pointer");
-  SVR_CHECK(M > 0 && N > 0 && K > 0 && N % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_weight_bf16x3: M=%ld N=%ld K=%ld (N %% 4)", (long)M, (long)N, (long)K);
-  SVR_CHECK(lddy % 4 == 0 && ((uintptr_t)dY & 15) == 0, SVR_E_ALIGN, "linear_bwd_weight_bf16x3: dY must be 16-byte aligned");
+  LinPlan plan;
+  if (int rc = lin_plan(LinQuery{SVR_LIN_BWD_WEIGHT_BF16X3, M, N, K, lddy, ldx, lddw, 0, lo4(dY), lo4(X), lo4(dW), 0, SVR_EPI_NONE, db != nullptr, 1}, plan)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int64_t rps;
-  int splits = tn_splits(M, N, K, &rps);
+  const int64_t rps = plan.rows_per_split;
+  const int splits = plan.splits;
   const int64_t Mpad = tn_mpad(M), parts = cdiv(M, 64);
   char *w = align256(workspace);
   float *slab = (float *)w;
@@ -820,7 +816,7 @@ extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const
   w += align256(N * Mpad * 2);
   float *dbpart = (float *)w;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
-  if (K % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)X & 15) == 0 && N >= 4 && K >= 4) {
+  if (plan.kernel == SVR_LIN_K_TN_TR) {
     // both operands row-major, transposing LDS reads: no pre-pass over dY; db from the K-tile-0 workgroups
     hipLaunchKernelGGL(linear_tn_x3_tr_kernel<>, grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
                        rps, splits, (const uint32_t *)nullptr, CwGeom{});
@@ -844,12 +840,11 @@ extern "C" int svr_linear_bwd_weight_f16x3(const float *dY, int64_t lddy, const 
                                            float *db, int64_t M, int64_t N, int64_t K, const uint32_t *amax_dy, void *workspace,
                                            void *stream) {
   SVR_CHECK(dY && X && dW && workspace, SVR_E_BADARG, "linear_bwd_weight_f16x3: null pointer");
-  SVR_CHECK(M > 0 && N >= 4 && K >= 4 && N % 4 == 0 && K % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_weight_f16x3: M=%ld N=%ld K=%ld (N, K %% 4)", (long)M, (long)N, (long)K);
-  SVR_CHECK(lddy % 4 == 0 && ((uintptr_t)dY & 15) == 0 && ldx % 4 == 0 && ((uintptr_t)X & 15) == 0, SVR_E_ALIGN,
-            "linear_bwd_weight_f16x3: dY and X must be 16-byte aligned with leading dimensions that are multiples of 4");
+  LinPlan plan;
+  if (int rc = lin_plan(LinQuery{SVR_LIN_BWD_WEIGHT_F16X3S, M, N, K, lddy, ldx, lddw, 0, lo4(dY), lo4(X), lo4(dW), 0, SVR_EPI_NONE, db != nullptr, 1}, plan)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int64_t rps;
-  int splits = tn_splits(M, N, K, &rps);
+  const int64_t rps = plan.rows_per_split;
+  const int splits = plan.splits;
   const int64_t Mpad = tn_mpad(M);
   char *w = align256(workspace);
   float *slab = (float *)w;

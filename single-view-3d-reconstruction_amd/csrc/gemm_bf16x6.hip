@@ -14,6 +14,8 @@
 // 128x128 tile, 4 waves x (2x2) v_mfma_f32_32x32x16_bf16 tiles, k-step 16, LDS planes [row][k] with a 40-byte
 // row stride (ds_read_b64 fragment reads conflict free), one 30 KB LDS stage (4 workgroups per CU).
 #include "common.h"
+#define SVR_GEMM_PLAN_ONLY
+#include "gemm_core.h"
 #include "f16x3.h"
 
 using namespace svr;
@@ -169,11 +171,9 @@ extern "C" int svr_linear_fwd_bf16x6(const float *X, int64_t ldx, const float *W
                                      void *stream) {
   if (M == 0) return SVR_OK;  // empty point set
   SVR_CHECK(X && W && Y && workspace, SVR_E_BADARG, "linear_fwd_bf16x6: null pointer");
-  SVR_CHECK(M >= 0 && N > 0 && K > 0 && K % YK == 0, SVR_E_BADSHAPE, "linear_fwd_bf16x6: M=%ld N=%ld K=%ld (K %% 16)", (long)M, (long)N, (long)K);
-  SVR_CHECK(ldx % 4 == 0 && ((uintptr_t)X & 15) == 0, SVR_E_ALIGN, "linear_fwd_bf16x6: X must be 16-byte aligned");
-  SVR_CHECK(epilogue == SVR_EPI_NONE || ((epilogue == SVR_EPI_BIAS || epilogue == SVR_EPI_BIAS_RELU) && bias), SVR_E_BADARG,
-            "linear_fwd_bf16x6: epilogue %d", epilogue);
-  if (M == 0) return SVR_OK;
+  LinPlan plan;
+  if (int rc = lin_plan(LinQuery{SVR_LIN_FWD_BF16X6, M, N, K, ldx, ldw, ldy, 0, lo4(X), lo4(W), lo4(Y), 0, epilogue, 0, 1}, plan)) return rc;
+  SVR_CHECK(epilogue == SVR_EPI_NONE || bias, SVR_E_BADARG, "linear_fwd_bf16x6: epilogue %d needs bias", epilogue);
   hipStream_t s = (hipStream_t)stream;
   uint16_t *p0 = (uint16_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   uint16_t *p1 = p0 + N * K, *p2 = p1 + N * K;

@@ -15,6 +15,165 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "common.h"
+
+// ---- launch plans of the point-MLP GEMMs (host side) -------------------------------------------------------------------------
+// Which kernel, epilogue form, reduction split and bias-sum form a linear entry point of gemm.hip / gemm_f16x3.hip /
+// gemm_bf16x3.hip / gemm_bf16x6.hip takes for a shape, its leading dimensions and the low address bits of its operands, and
+// the refusal it answers with otherwise.  The launchers call lin_plan() and act on the result; svr_linear_variant (gemm.hip)
+// exports the same call, so the answer cannot drift from what runs.  Nothing here touches the device.
+// (gemm_f16x3.hip / gemm_bf16x3.hip have loaders of their own under the names used below: they define SVR_GEMM_PLAN_ONLY.)
+namespace svr {
+
+struct LinQuery {
+  int op;                        // SVR_LIN_*
+  int64_t M, N, K;               // x (M,K), w (N,K), dy (M,N)
+  int64_t lda, ldb, ldo, ldm;    // leading dimensions: first operand (X / dY), second (W; X of backward-weight), output, mask
+  unsigned a_lo, b_lo, o_lo, m_lo;   // low four address bits of the same
+  int epilogue;                  // SVR_EPI_*
+  int want_bias;                 // backward-weight: db asked for
+  int run;                       // 0: a PREPARE call (weights only) -- the shape checks alone
+};
+struct LinPlan {
+  int kernel, coalesced, splits, bias;   // SVR_LIN_K_*, float4 epilogue, reduction splits, SVR_LIN_BIAS_*
+  int64_t rows_per_split;
+};
+
+inline unsigned lo4(const void *p) { return (unsigned)((uintptr_t)p & 15); }
+
+// the float4 epilogue of linear_nt_h3_kernel (gemm_f16x3.hip); N / ldy / Y are the kernel's (backward: N = dX's columns)
+__host__ __device__ inline bool nt_h3_coalesced(int TN, bool bwd, int64_t N, int64_t ldy, uintptr_t Y, bool mask, int64_t ldm,
+                                                uintptr_t maskp) {
+  return TN == 128 && N % 4 == 0 && ldy % 4 == 0 && (Y & 15) == 0 && (!bwd || !mask || (ldm % 4 == 0 && (maskp & 15) == 0));
+}
+// colsum_launch (gemm.hip): the float4 kernel needs N / 4 column quads that divide the workgroup
+inline bool colsum_vec(int64_t N, int64_t ldy, uintptr_t Y) {
+  return N % 4 == 0 && N / 4 <= 256 && 256 % (N / 4) == 0 && ldy % 4 == 0 && (Y & 15) == 0;
+}
+// exact-f32 dW: splits of whole 16-row k-steps, ~2048 workgroups
+inline int tn_splits_f32(int64_t M, int64_t N, int64_t K, int *steps_per_split) {
+  int64_t tiles = cdiv(N, 128) * cdiv(K, 128);
+  int64_t steps = cdiv(M, 16);
+  int64_t want = cdiv(2048, tiles);
+  int64_t splits = want < 1 ? 1 : want;
+  if (splits > steps) splits = steps > 0 ? steps : 1;
+  int64_t sps = cdiv(steps, splits);
+  splits = steps > 0 ? cdiv(steps, sps) : 1;
+  *steps_per_split = (int)sps;
+  return (int)splits;
+}
+// split-precision dW (k-step 32): three 4-wave workgroups per CU, two rounds
+inline int tn_splits_x3(int64_t M, int64_t N, int64_t K, int64_t *rows_per_split) {
+  int64_t tiles = cdiv(N, 128) * cdiv(K, 128);
+  int64_t want = cdiv(1536, tiles);
+  if (want < 1) want = 1;
+  int64_t rps = cdiv(cdiv(M, want), 32) * 32;  // multiple of the k-step
+  if (rps < 32) rps = 32;
+  *rows_per_split = rps;
+  return (int)cdiv(M, rps);
+}
+
+inline int lin_plan(const LinQuery &q, LinPlan &p) {
+  const int64_t M = q.M, N = q.N, K = q.K;
+  const bool a16 = q.lda % 4 == 0 && q.a_lo == 0, b16 = q.ldb % 4 == 0 && q.b_lo == 0, o16 = q.ldo % 4 == 0 && q.o_lo == 0;
+  const bool masked = q.epilogue == SVR_EPI_MASK, m16 = q.ldm % 4 == 0 && q.m_lo == 0;
+  const bool fwd_epi = q.epilogue == SVR_EPI_NONE || q.epilogue == SVR_EPI_BIAS || q.epilogue == SVR_EPI_BIAS_RELU;
+  p = LinPlan{-1, 0, 1, SVR_LIN_BIAS_NONE, M};
+  switch (q.op) {
+    case SVR_LIN_FWD_F32:
+      p.kernel = SVR_LIN_K_NT;
+      if (M == 0) return SVR_OK;  // empty point set
+      SVR_CHECK(M >= 0 && N > 0 && K > 0 && K % 16 == 0, SVR_E_BADSHAPE, "linear_fwd: M=%ld N=%ld K=%ld (K %% 16)", (long)M, (long)N, (long)K);
+      SVR_CHECK(a16 && b16, SVR_E_ALIGN, "linear_fwd: operands must be 16-byte aligned");
+      SVR_CHECK(q.epilogue >= SVR_EPI_NONE && q.epilogue <= SVR_EPI_MASK, SVR_E_BADARG, "bad epilogue %d", q.epilogue);
+      return SVR_OK;
+    case SVR_LIN_BWD_DATA_F32:
+      p.kernel = SVR_LIN_K_NN;
+      if (M == 0) return SVR_OK;
+      SVR_CHECK(M >= 0 && N > 0 && K > 0 && N % 16 == 0 && K % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_data: M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+      SVR_CHECK(a16 && b16, SVR_E_ALIGN, "linear_bwd_data: operands must be 16-byte aligned");
+      SVR_CHECK(q.epilogue == SVR_EPI_NONE || masked, SVR_E_BADARG, "linear_bwd_data: epilogue %d", q.epilogue);
+      return SVR_OK;
+    case SVR_LIN_BWD_WEIGHT_F32: {
+      p.kernel = SVR_LIN_K_TN;
+      SVR_CHECK(M > 0 && N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_weight: M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+      SVR_CHECK(a16 && b16, SVR_E_ALIGN, "linear_bwd_weight: operands must be 16-byte aligned");
+      int sps;
+      p.splits = tn_splits_f32(M, N, K, &sps);
+      p.rows_per_split = (int64_t)sps * 16;
+      if (q.want_bias) p.bias = colsum_vec(N, q.lda, q.a_lo) ? SVR_LIN_BIAS_COLSUM_VEC : SVR_LIN_BIAS_COLSUM_SLOW;
+      return SVR_OK;
+    }
+    case SVR_LIN_FWD_F16X3:
+      p.kernel = N <= 64 ? SVR_LIN_K_NT64 : SVR_LIN_K_NT128;   // narrow outputs: 128 x 64 tiles, two waves, half the wasted columns
+      if (M == 0 && q.run) return SVR_OK;
+      SVR_CHECK(M >= 0 && N > 0 && K > 0 && K % 16 == 0, SVR_E_BADSHAPE, "linear_fwd_f16x3: M=%ld N=%ld K=%ld (K %% 16)", (long)M, (long)N, (long)K);
+      if (!q.run) return SVR_OK;
+      SVR_CHECK(a16, SVR_E_ALIGN, "linear_fwd_f16x3: X must be 16-byte aligned");
+      SVR_CHECK(fwd_epi, SVR_E_BADARG, "linear_fwd_f16x3: epilogue %d", q.epilogue);
+      p.coalesced = nt_h3_coalesced(N <= 64 ? 64 : 128, false, N, q.ldo, q.o_lo, false, 0, 0);
+      return SVR_OK;
+    case SVR_LIN_FWD_BF16X6:
+      p.kernel = SVR_LIN_K_NT_X6;
+      if (M == 0) return SVR_OK;
+      SVR_CHECK(M >= 0 && N > 0 && K > 0 && K % 16 == 0, SVR_E_BADSHAPE, "linear_fwd_bf16x6: M=%ld N=%ld K=%ld (K %% 16)", (long)M, (long)N, (long)K);
+      SVR_CHECK(a16, SVR_E_ALIGN, "linear_fwd_bf16x6: X must be 16-byte aligned");
+      SVR_CHECK(fwd_epi, SVR_E_BADARG, "linear_fwd_bf16x6: epilogue %d", q.epilogue);
+      return SVR_OK;
+    case SVR_LIN_BWD_DATA_F16X3S: {
+      // the k-step-32 kernel of gemm_bf16x3.hip where the shape allows it, else the forward kernel with transposed planes (k-step 16)
+      // (a function of the SHAPE only: PREPARE and RUN calls must agree on the plane layout)
+      const bool nn = N % 32 == 0 && K % 4 == 0;
+      p.kernel = nn ? SVR_LIN_K_NN_X3 : SVR_LIN_K_NT128_BWD;
+      if (M == 0 && q.run) return SVR_OK;
+      SVR_CHECK(M >= 0 && N > 0 && K > 0 && N % 16 == 0, SVR_E_BADSHAPE, "linear_bwd_data_f16x3: M=%ld N=%ld K=%ld (N %% 16)", (long)M, (long)N, (long)K);
+      if (!q.run) return SVR_OK;
+      SVR_CHECK(a16, SVR_E_ALIGN, "linear_bwd_data_f16x3: dY must be 16-byte aligned");
+      SVR_CHECK(q.epilogue == SVR_EPI_NONE || masked, SVR_E_BADARG, "linear_bwd_data_f16x3: epilogue %d", q.epilogue);
+      if (nn) {
+        SVR_CHECK(o16 && (!masked || m16), SVR_E_ALIGN,
+                  "linear_bwd_data_f16x3: dX and the mask must be 16-byte aligned with leading dimensions that are multiples of 4");
+        p.coalesced = 1;
+      } else {
+        p.coalesced = nt_h3_coalesced(128, true, K, q.ldo, q.o_lo, masked, q.ldm, q.m_lo);
+      }
+      return SVR_OK;
+    }
+    case SVR_LIN_BWD_DATA_BF16X3:
+      p.kernel = SVR_LIN_K_NN_X3;
+      p.coalesced = 1;
+      if (M == 0 && q.run) return SVR_OK;
+      SVR_CHECK(M >= 0 && N > 0 && K > 0 && N % 32 == 0 && K % 4 == 0, SVR_E_BADSHAPE,
+                "linear_bwd_data_bf16x3: M=%ld N=%ld K=%ld (need N %% 32 == 0, K %% 4 == 0)", (long)M, (long)N, (long)K);
+      if (!q.run) return SVR_OK;
+      SVR_CHECK(q.ldo % 4 == 0 && q.ldm % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_data_bf16x3: leading dimensions must be multiples of 4");
+      SVR_CHECK(a16, SVR_E_ALIGN, "linear_bwd_data_bf16x3: dY must be 16-byte aligned");
+      SVR_CHECK(q.epilogue == SVR_EPI_NONE || masked, SVR_E_BADARG, "linear_bwd_data_bf16x3: epilogue %d", q.epilogue);
+      // linear_nn_x3_kernel moves both as float4
+      SVR_CHECK(q.o_lo == 0 && (!masked || q.m_lo == 0), SVR_E_ALIGN, "linear_bwd_data_bf16x3: dX and the mask must be 16-byte aligned");
+      return SVR_OK;
+    case SVR_LIN_BWD_WEIGHT_BF16X3:
+      SVR_CHECK(M > 0 && N > 0 && K > 0 && N % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_weight_bf16x3: M=%ld N=%ld K=%ld (N %% 4)", (long)M, (long)N, (long)K);
+      SVR_CHECK(a16, SVR_E_ALIGN, "linear_bwd_weight_bf16x3: dY must be 16-byte aligned");
+      // both operands row-major through the transposing LDS reads, or (X not float4-able) the dY pre-pass + transposing loader
+      p.kernel = (K % 4 == 0 && b16 && N >= 4 && K >= 4) ? SVR_LIN_K_TN_TR : SVR_LIN_K_TN_PREPASS;
+      p.splits = tn_splits_x3(M, N, K, &p.rows_per_split);
+      if (q.want_bias) p.bias = SVR_LIN_BIAS_KERNEL;
+      return SVR_OK;
+    case SVR_LIN_BWD_WEIGHT_F16X3S:
+      p.kernel = SVR_LIN_K_TN_TR;
+      SVR_CHECK(M > 0 && N >= 4 && K >= 4 && N % 4 == 0 && K % 4 == 0, SVR_E_BADSHAPE, "linear_bwd_weight_f16x3: M=%ld N=%ld K=%ld (N, K %% 4)", (long)M, (long)N, (long)K);
+      SVR_CHECK(a16 && b16, SVR_E_ALIGN, "linear_bwd_weight_f16x3: dY and X must be 16-byte aligned with leading dimensions that are multiples of 4");
+      p.splits = tn_splits_x3(M, N, K, &p.rows_per_split);
+      if (q.want_bias) p.bias = SVR_LIN_BIAS_KERNEL;
+      return SVR_OK;
+  }
+  SVR_CHECK(false, SVR_E_BADARG, "linear plan: op %d", q.op);
+}
+
+}  // namespace svr
+
+#ifndef SVR_GEMM_PLAN_ONLY
 
 namespace svr {
 
@@ -165,3 +324,4 @@ __device__ __forceinline__ void gemm_foreach(f32x16 (&acc)[Cfg::TM][Cfg::TN], F 
 }
 
 }  // namespace svr
+#endif  // SVR_GEMM_PLAN_ONLY

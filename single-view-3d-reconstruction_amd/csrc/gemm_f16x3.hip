@@ -22,6 +22,8 @@
 // one v_pk_mul_f16 per fragment register) and both streams are prefetched two k-steps ahead.  A 128x256 tile
 // (X read once) ran one workgroup per CU and was slower (3.1 ms vs 2.4); `nt` loads of X were slower too (3.5).
 #include "common.h"
+#define SVR_GEMM_PLAN_ONLY
+#include "gemm_core.h"
 #include "f16x3.h"
 #include "reduce.h"
 #include <algorithm>
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(2 * TN, 1024 / (2 * TN) >= 4 ? 3 : 2) void linear_n
   // stores of a wave are 32 consecutive dwords per row, the float4 reads 512 contiguous bytes per row: conflict free), so
   // that a thread issues 16 float4 stores (and mask loads) on full 512-byte rows instead of 64 dword ones on 128-byte
   // segments; bias / ReLU / mask / scale / |max| are applied on the way out.
-  const bool coal = TN == 128 && N % 4 == 0 && ldy % 4 == 0 && (((uintptr_t)Y) & 15) == 0 && (!BWD || !mask || (ldm % 4 == 0 && (((uintptr_t)mask) & 15) == 0));
+  const bool coal = nt_h3_coalesced(TN, BWD, N, ldy, (uintptr_t)Y, mask != nullptr, ldm, (uintptr_t)mask);
   if (coal) {
     float *ct = reinterpret_cast<float *>(lds);
 #pragma unroll
@@ -340,7 +342,8 @@ extern "C" int svr_linear_fwd_f16x3(const float *X, int64_t ldx, const float *W,
   // X == NULL: PREPARE only (W -> scale + split planes in the workspace);  W == NULL: RUN on a workspace prepared earlier
   if (M == 0 && X) return SVR_OK;  // empty point set
   SVR_CHECK((X || W) && (!X || Y) && workspace, SVR_E_BADARG, "linear_fwd_f16x3: null pointer");
-  SVR_CHECK(M >= 0 && N > 0 && K > 0 && K % YK == 0, SVR_E_BADSHAPE, "linear_fwd_f16x3: M=%ld N=%ld K=%ld (K %% 16)", (long)M, (long)N, (long)K);
+  LinPlan plan;   // shape checks first (PREPARE), the operand checks of a RUN below
+  if (int rc = lin_plan(LinQuery{SVR_LIN_FWD_F16X3, M, N, K, ldx, ldw, ldy, 0, 0, 0, 0, 0, SVR_EPI_NONE, 0, 0}, plan)) return rc;
   hipStream_t s = (hipStream_t)stream;
   uint32_t *amax = align256<uint32_t>(workspace);
   uint16_t *p0 = (uint16_t *)(amax + 64);
@@ -349,14 +352,13 @@ extern "C" int svr_linear_fwd_f16x3(const float *X, int64_t ldx, const float *W,
     hipLaunchKernelGGL(split_w_kernel, dim3((unsigned)cdiv(N * (K / 2), 256)), dim3(256), 0, s, W, ldw, amax, p0, N, K, 0);
   }
   if (!X) return launch_status("linear_fwd_f16x3 (prepare)");
-  SVR_CHECK(ldx % 4 == 0 && ((uintptr_t)X & 15) == 0, SVR_E_ALIGN, "linear_fwd_f16x3: X must be 16-byte aligned");
-  SVR_CHECK(epilogue == SVR_EPI_NONE || ((epilogue == SVR_EPI_BIAS || epilogue == SVR_EPI_BIAS_RELU) && bias), SVR_E_BADARG,
-            "linear_fwd_f16x3: epilogue %d", epilogue);
+  if (int rc = lin_plan(LinQuery{SVR_LIN_FWD_F16X3, M, N, K, ldx, ldw, ldy, 0, lo4(X), lo4(W), lo4(Y), 0, epilogue, 0, 1}, plan)) return rc;
+  SVR_CHECK(epilogue == SVR_EPI_NONE || bias, SVR_E_BADARG, "linear_fwd_f16x3: epilogue %d needs bias", epilogue);
   const float *eb = epilogue == SVR_EPI_NONE ? nullptr : bias;
   const int relu = epilogue == SVR_EPI_BIAS_RELU ? 1 : 0;
   // SCHED = 2 (one MFMA, a slice of the split, one LDS store, ...): 2.39 ms at 400 000 x 2592 x 256 against 2.49 for
   // the compiler's own order and 2.50 for iglp_opt(0)
-  if (N <= 64) {  // narrow outputs (the UNet's 32- and 64-channel layers): 128 x 64 tiles, two waves, half the wasted columns
+  if (plan.kernel == SVR_LIN_K_NT64) {  // narrow outputs (the UNet's 32- and 64-channel layers): 128 x 64 tiles, two waves, half the wasted columns
     dim3 grid(xcd_grid(cdiv(N, 64) * cdiv(M, TM)));
     hipLaunchKernelGGL((linear_nt_h3_kernel<64, 0, 2>), grid, dim3(128), 0, s, X, ldx, p0, amax, eb, Y, ldy, M, N, K, relu,
                        (const uint32_t *)nullptr, (const float *)nullptr, (int64_t)0, (uint32_t *)nullptr);
@@ -386,18 +388,15 @@ extern "C" int svr_linear_bwd_data_f16x3(const float *dY, int64_t lddy, const fl
   // dY == NULL: PREPARE only (W -> scale + split TRANSPOSED planes in the workspace);  W == NULL: RUN on a prepared workspace
   if (M == 0 && dY) return SVR_OK;
   SVR_CHECK((dY || W) && (!dY || dX) && workspace, SVR_E_BADARG, "linear_bwd_data_f16x3: null pointer");
-  SVR_CHECK(M >= 0 && N > 0 && K > 0 && N % YK == 0, SVR_E_BADSHAPE, "linear_bwd_data_f16x3: M=%ld N=%ld K=%ld (N %% 16)", (long)M, (long)N, (long)K);
+  // the plan: the k-step-32 kernel of gemm_bf16x3.hip where the shape allows it, else the forward kernel with transposed planes
+  // (k-step 16); a PREPARE call gets the shape checks alone
+  LinPlan plan;
+  if (int rc = lin_plan(LinQuery{SVR_LIN_BWD_DATA_F16X3S, M, N, K, lddy, ldw, lddx, ldmask, lo4(dY), lo4(W), lo4(dX), lo4(mask), epilogue, 0,
+                                 dY != nullptr}, plan)) return rc;
+  SVR_CHECK(!dY || epilogue != SVR_EPI_MASK || mask, SVR_E_BADARG, "linear_bwd_data_f16x3: epilogue %d needs the mask", epilogue);
   hipStream_t s = (hipStream_t)stream;
-  // the k-step-32 kernel of gemm_bf16x3.hip where the shape allows it, else the forward kernel with transposed planes (k-step 16)
-  if (N % 32 == 0 && K % 4 == 0) {   // (a function of the SHAPE only: PREPARE and RUN calls must agree on the plane layout)
-    if (dY) {
-      SVR_CHECK(lddy % 4 == 0 && ((uintptr_t)dY & 15) == 0, SVR_E_ALIGN, "linear_bwd_data_f16x3: dY must be 16-byte aligned");
-      SVR_CHECK(epilogue == SVR_EPI_NONE || (epilogue == SVR_EPI_MASK && mask), SVR_E_BADARG, "linear_bwd_data_f16x3: epilogue %d", epilogue);
-      SVR_CHECK(lddx % 4 == 0 && (((uintptr_t)dX) & 15) == 0 && (epilogue != SVR_EPI_MASK || (ldmask % 4 == 0 && (((uintptr_t)mask) & 15) == 0)),
-                SVR_E_ALIGN, "linear_bwd_data_f16x3: dX and the mask must be 16-byte aligned with leading dimensions that are multiples of 4");
-    }
+  if (plan.kernel == SVR_LIN_K_NN_X3)
     return svr::linear_bwd_data_f16_nn(dY, lddy, W, ldw, dX, lddx, M, N, K, epilogue, mask, ldmask, amax_dy, amax_dx, workspace, s);
-  }
   uint32_t *amax = align256<uint32_t>(workspace);
   uint16_t *p0 = (uint16_t *)(amax + 64);
   if (W) {   // planes of W^T: K rows (dX columns) x N reduction elements
@@ -405,8 +404,6 @@ extern "C" int svr_linear_bwd_data_f16x3(const float *dY, int64_t lddy, const fl
     hipLaunchKernelGGL(split_w_kernel, dim3((unsigned)cdiv(K * (N / 2), 256)), dim3(256), 0, s, W, ldw, amax, p0, K, N, 1);
   }
   if (!dY) return launch_status("linear_bwd_data_f16x3 (prepare)");
-  SVR_CHECK(lddy % 4 == 0 && ((uintptr_t)dY & 15) == 0, SVR_E_ALIGN, "linear_bwd_data_f16x3: dY must be 16-byte aligned");
-  SVR_CHECK(epilogue == SVR_EPI_NONE || (epilogue == SVR_EPI_MASK && mask), SVR_E_BADARG, "linear_bwd_data_f16x3: epilogue %d", epilogue);
   const float *mk = epilogue == SVR_EPI_MASK ? mask : nullptr;
   dim3 grid(xcd_grid(cdiv(K, 128) * cdiv(M, TM)));
   hipLaunchKernelGGL((linear_nt_h3_kernel<128, 0, 2, true>), grid, dim3(256), 0, s, dY, lddy, p0, amax, (const float *)nullptr, dX, lddx,

@@ -676,6 +676,73 @@ def _lookup(kind, w, mode, default):
     return _prepared.lookup(kind, w)
 
 
+# ---- which entry point a linear op reaches, and what that entry point does with the call ---------------------------------
+# The three ops below and linear_variant() take the entry point from the same _linear_*_op functions; the kernel, epilogue
+# form, splits and refusal come from the library (svr_linear_variant: the function its launchers call).
+LINEAR_OPS = {"fwd_f32": 0, "fwd_f16x3": 1, "fwd_bf16x6": 2, "bwd_data_f32": 3, "bwd_data_f16x3s": 4, "bwd_data_bf16x3": 5,
+              "bwd_weight_f32": 6, "bwd_weight_f16x3s": 7, "bwd_weight_bf16x3": 8}      # SVR_LIN_* of svr_hip.h
+LINEAR_KERNELS = ("nt", "nn", "tn", "nt128", "nt64", "nt128_bwd", "nn_x3", "tn_tr", "tn_prepass", "nt_x6")      # SVR_LIN_K_*
+LINEAR_BIAS_FORMS = ("none", "kernel", "colsum_vec", "colsum_slow")      # SVR_LIN_BIAS_*
+
+
+def operand_layout(t):
+    """(leading dimension, low four address bits, unit column stride) of a 2-D operand; None -> None."""
+    return None if t is None else (t.stride(0), t.data_ptr() & 15, t.stride(1) == 1)
+
+
+def _al16(lay):
+    """Rows a kernel may move as float4: unit column stride, leading dimension a multiple of 4, 16-byte aligned start."""
+    return lay is None or (lay[2] and lay[0] % 4 == 0 and lay[1] == 0)
+
+
+def _linear_fwd_op(mode, K):
+    mode = mode or FORWARD_GEMM
+    return "fwd_" + mode if mode in ("f16x3", "bf16x6") and K % 16 == 0 else "fwd_f32"
+
+
+def _linear_bwd_data_op(mode, N, dy, out, mask):
+    mode = mode or BACKWARD_GEMM
+    if mode == "f16x3s":      # (shapes and layouts the f16 kernels do not take: exact f32, never a narrower split)
+        return "bwd_data_f16x3s" if N % 16 == 0 and _al16(dy) and _al16(out) and _al16(mask) else "bwd_data_f32"
+    if mode == "bf16x3" and N % 32 == 0 and out[1] == 0 and (mask is None or mask[1] == 0):      # (its float4 epilogue; else f32)
+        return "bwd_data_bf16x3"
+    return "bwd_data_f32"
+
+
+def _linear_bwd_weight_op(mode, M, N, K, dy, x):
+    mode = mode or BACKWARD_GEMM
+    if mode == "f16x3s":
+        return "bwd_weight_f16x3s" if N % 4 == 0 and K % 4 == 0 and N >= 4 and K >= 4 and M > 0 and _al16(dy) and _al16(x) else "bwd_weight_f32"
+    return "bwd_weight_bf16x3" if mode == "bf16x3" and N % 4 == 0 else "bwd_weight_f32"
+
+
+def linear_variant(kind, mode, M, N, K, a=None, b=None, out=None, mask=None, epilogue=None, want_bias=False):
+    """What linear_fwd / linear_bwd_data / linear_bwd_weight (kind "fwd" / "bwd_data" / "bwd_weight") do with a call in `mode`:
+    {"op" (the entry point, a LINEAR_OPS key), "kernel" (LINEAR_KERNELS), "coalesced", "splits", "rows_per_split", "bias"
+    (LINEAR_BIAS_FORMS), "status" (0 or the SVR_E_* the entry point refuses with)}.  x (M,K), w (N,K), dy (M,N); a / b / out /
+    mask: operand_layout() of the first operand (x; dy backward), the second (w; x of bwd_weight), the output and the mask,
+    None = contiguous and aligned (mask: none).  Host only, no GPU needed."""
+    cont = {"fwd": (K, K, N), "bwd_data": (N, K, K), "bwd_weight": (N, K, K)}[kind]
+    a, b, out = [(ld, 0, True) if lay is None else lay for lay, ld in zip((a, b, out), cont)]
+    if kind == "fwd":
+        op = _linear_fwd_op(mode, K)
+    elif kind == "bwd_data":
+        op = _linear_bwd_data_op(mode, N, a, out, mask)
+    else:
+        op = _linear_bwd_weight_op(mode, M, N, K, a, b)
+    if epilogue is None:
+        epilogue = EPI_MASK if mask is not None else EPI_NONE
+    m = mask if mask is not None else (0, 0, True)
+    i32 = [C.c_int32() for _ in range(5)]
+    rows = C.c_int64()
+    kernel, coalesced, splits, bias, status = i32
+    check(_lib.lib().svr_linear_variant(LINEAR_OPS[op], M, N, K, a[0], b[0], out[0], m[0], a[1], b[1], out[1], m[1], epilogue,
+                                        int(want_bias), C.byref(kernel), C.byref(coalesced), C.byref(splits), C.byref(rows),
+                                        C.byref(bias), C.byref(status)), "linear_variant")
+    return {"op": op, "kernel": LINEAR_KERNELS[kernel.value] if kernel.value >= 0 else None, "coalesced": bool(coalesced.value),
+            "splits": splits.value, "rows_per_split": rows.value, "bias": LINEAR_BIAS_FORMS[bias.value], "status": status.value}
+
+
 def linear_fwd(x, w, bias, relu=True, out=None, mode=None):
     """y = [relu](x @ w.T + bias); x (M,K) row stride may exceed K (padded feature rows)."""
     _f32(x, w, bias)
@@ -684,24 +751,27 @@ def linear_fwd(x, w, bias, relu=True, out=None, mode=None):
     assert w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
     if out is None:
         out = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    _f32(out)
+    assert out.shape == (M, N) and out.stride(1) == 1      # a column slice of a wider buffer is fine: its row stride is passed
     epi = EPI_NONE if bias is None else (EPI_BIAS_RELU if relu else EPI_BIAS)
-    if (mode or FORWARD_GEMM) == "f16x3" and K % 16 == 0:
+    op = _linear_fwd_op(mode, K)
+    if op == "fwd_f16x3":
         l = _lib.lib()
         ws = _lookup("lf", w, mode, "f16x3") if w.stride(0) == K else None
         wptr = C.c_void_p(0) if ws is not None else C.c_void_p(w.data_ptr())      # W NULL: the workspace is prepared
         if ws is None:
             ws = torch.empty(l.svr_linear_fwd_f16x3_workspace(N, K), device=x.device, dtype=torch.uint8)
         check(l.svr_linear_fwd_f16x3(C.c_void_p(x.data_ptr()), x.stride(0), wptr, w.stride(0), _p(bias),
-                                     _p(out), out.stride(0), M, N, K, epi, _p(ws), _stream()), "linear_fwd_f16x3")
+                                     _rp(out), out.stride(0), M, N, K, epi, _p(ws), _stream()), "linear_fwd_f16x3")
         return out
-    if (mode or FORWARD_GEMM) == "bf16x6" and K % 16 == 0:
+    if op == "fwd_bf16x6":
         l = _lib.lib()
         ws = torch.empty(l.svr_linear_fwd_bf16x6_workspace(N, K), device=x.device, dtype=torch.uint8)
         check(l.svr_linear_fwd_bf16x6(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(w.data_ptr()), w.stride(0), _p(bias),
-                                      _p(out), out.stride(0), M, N, K, epi, _p(ws), _stream()), "linear_fwd_bf16x6")
+                                      _rp(out), out.stride(0), M, N, K, epi, _p(ws), _stream()), "linear_fwd_bf16x6")
         return out
     check(_lib.lib().svr_linear_fwd(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(w.data_ptr()), w.stride(0),
-                                    _p(bias), _p(out), out.stride(0), M, N, K, epi, C.c_void_p(0), 0, _stream()),
+                                    _p(bias), _rp(out), out.stride(0), M, N, K, epi, C.c_void_p(0), 0, _stream()),
           "linear_fwd")
     return out
 
@@ -792,9 +862,8 @@ def linear_bwd_data(dy, w, mask=None, out=None, mode=None):
     if out is None:
         out = torch.empty(M, K, device=dy.device, dtype=torch.float32)
     epi = EPI_MASK if mask is not None else EPI_NONE
-    if ((mode or BACKWARD_GEMM) == "f16x3s" and N % 16 == 0 and dy.stride(1) == 1 and dy.stride(0) % 4 == 0
-            and dy.data_ptr() % 16 == 0 and out.stride(1) == 1 and out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 0
-            and (mask is None or (mask.stride(1) == 1 and mask.stride(0) % 4 == 0 and mask.data_ptr() % 16 == 0))):
+    op = _linear_bwd_data_op(mode, N, operand_layout(dy), operand_layout(out), operand_layout(mask))
+    if op == "bwd_data_f16x3s":
         l = _lib.lib()
         ws = _lookup("lbh", w, mode, "f16x3s") if (w.stride(0) == K and w.stride(1) == 1) else None
         wptr = C.c_void_p(0) if ws is not None else C.c_void_p(w.data_ptr())      # W NULL: the workspace is prepared
@@ -809,9 +878,7 @@ def linear_bwd_data(dy, w, mask=None, out=None, mode=None):
               "linear_bwd_data_f16x3")
         out._svr_amax = amax_dx        # |max| of what was stored: the next layer's scale, no extra pass
         return out
-    if (mode or BACKWARD_GEMM) == "f16x3s":
-        mode = "f32"                   # (shapes the f16 kernel does not take: exact f32, never a narrower split)
-    if (mode or BACKWARD_GEMM) == "bf16x3" and N % 32 == 0:
+    if op == "bwd_data_bf16x3":
         l = _lib.lib()
         ws = _lookup("lb", w, mode, "bf16x3") if (w.stride(0) == K and w.stride(1) == 1) else None
         wptr = C.c_void_p(0) if ws is not None else C.c_void_p(w.data_ptr())      # W NULL: the workspace is prepared
@@ -836,16 +903,14 @@ def linear_bwd_weight(dy, x, want_bias=True, mode=None):
     l = _lib.lib()
     dw = torch.empty(N, K, device=dy.device, dtype=torch.float32)
     db = torch.empty(N, device=dy.device, dtype=torch.float32) if want_bias else None
-    if ((mode or BACKWARD_GEMM) == "f16x3s" and N % 4 == 0 and K % 4 == 0 and N >= 4 and K >= 4 and M > 0 and dy.stride(1) == 1
-            and x.stride(1) == 1 and dy.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
+    op = _linear_bwd_weight_op(mode, M, N, K, operand_layout(dy), operand_layout(x))
+    if op == "bwd_weight_f16x3s":
         ws = torch.empty(l.svr_linear_bwd_weight_f16x3_workspace(M, N, K), device=dy.device, dtype=torch.uint8)
         check(l.svr_linear_bwd_weight_f16x3(C.c_void_p(dy.data_ptr()), dy.stride(0), C.c_void_p(x.data_ptr()), x.stride(0),
                                             _p(dw), dw.stride(0), _p(db), M, N, K, _p(amax_of(dy)), _p(ws), _stream()),
               "linear_bwd_weight_f16x3")
         return dw, db
-    if (mode or BACKWARD_GEMM) == "f16x3s":
-        mode = "f32"
-    if (mode or BACKWARD_GEMM) == "bf16x3" and N % 4 == 0:
+    if op == "bwd_weight_bf16x3":
         ws = torch.empty(l.svr_linear_bwd_weight_bf16x3_workspace(M, N, K), device=dy.device, dtype=torch.uint8)
         check(l.svr_linear_bwd_weight_bf16x3(C.c_void_p(dy.data_ptr()), dy.stride(0), C.c_void_p(x.data_ptr()), x.stride(0),
                                              _p(dw), dw.stride(0), _p(db), M, N, K, _p(ws), _stream()),

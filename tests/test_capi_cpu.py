@@ -238,3 +238,85 @@ def test_conv3d_variant_refuses_what_the_entry_points_refuse():
     assert q(0, 2, 8, 8, 8, 16, 5) == 0 and q(3, 2, 8, 8, 8, 16, 5) == 0 and q(1, 2, 8, 8, 8, 6, 16) == 0
     assert q(0, 2, 8, 8, 8, 8, 32) == -4 and q(1, 2, 8, 8, 8, 16, 8) == -4 and q(2, 2, 8, 8, 8, 3, 16) == -4
     assert q(4, 2, 8, 8, 8, 16, 16) == -1 and q(-1, 2, 8, 8, 8, 16, 16) == -1 and q(0, 2, 0, 8, 8, 16, 16) == -2
+
+
+def test_linear_variant_table_and_every_launcher_branch_is_reached():
+    """Which kernel, epilogue form and bias form a linear op runs, asked of the library (svr_linear_variant: the function the
+    launchers of csrc/gemm*.hip themselves call) through ops.linear_variant, for every case of tests/test_gpu_gemm_paths.py;
+    the cases, together, reach EVERY (entry point, kernel, epilogue form, bias form) the launchers can produce -- found by
+    sweeping the query over shapes, leading dimensions and address bits, so a launcher branch that gains a variant fails here
+    until a case names it -- and the split regimes of the weight gradient.  A case edit that drops a branch fails here,
+    without a GPU."""
+    import itertools
+    import __graft_entry__ as ge
+    ge.build()
+    from svr_amd import ops
+    from tests import _gemm_cases as GC
+    assert len({c[0] for c in GC.CASES}) == len(GC.CASES)
+    reached, splits = set(), {}
+    for case in GC.CASES:
+        name, kind = case[0], case[1]
+        assert set(case[7]) == set(GC.modes(case)), name
+        for mode in GC.modes(case):
+            v = GC.query(ops, case, mode, want_bias=case[6].get("bias", (True,))[0])
+            assert GC.tag(kind, v) == case[7][mode], (name, mode, v)
+            for want_bias, masked in itertools.product(case[6].get("bias", (True, False)) if kind == "bwd_weight" else (True,),
+                                                       (True, False) if kind == "bwd_data" else (True,)):
+                v = GC.query(ops, case, mode, want_bias=want_bias, masked=masked)
+                if v["status"] == 0:
+                    reached.add((v["op"], v["kernel"], v["coalesced"], v["bias"]))
+                    if v["kernel"] in ("tn_tr", "tn_prepass"):
+                        splits[name] = (v["splits"], case[2] - (v["splits"] - 1) * v["rows_per_split"])      # (splits, rows of the last)
+                else:
+                    assert v["status"] in (-2, -3), (name, mode, v)
+    assert reached == GC.ALL_VARIANTS, sorted(reached ^ GC.ALL_VARIANTS)
+    assert splits["w_1x4x4"] == (1, 1) and splits["w_33x8x36"] == (2, 1), splits
+    # more than 28 splits: the eight-deep walk of slab_reduce_x3_kernel AND its remainder loop (splits % 32 not in 0, 29..31)
+    assert any(s > 28 and 0 < s % 32 <= 28 for s, _ in splits.values()), splits
+    # everything the launchers can answer with, over a sweep of shapes / leading dimensions / address bits
+    seen = set()
+    for kind, modes in GC.MODES.items():
+        for mode, M, N, K, pad, lo, flag in itertools.product(modes, (1, 33, 1100), (4, 16, 32, 48, 64, 72, 130, 256, 1792),
+                                                              (4, 6, 16, 36, 64, 130), (0, 2, 4), (0, 4), (False, True)):
+            cols = {"fwd": (K, K, N), "bwd_data": (N, K, K), "bwd_weight": (N, K, K)}[kind]
+            for which in range(4):      # the operand that is padded / misaligned (3: the mask)
+                lay = [(c + pad if i == which else c, lo if i == which else 0, True) for i, c in enumerate(cols)]
+                mask = (K + pad if which == 3 else K, lo if which == 3 else 0, True) if kind == "bwd_data" and flag else None
+                v = ops.linear_variant(kind, mode, M, N, K, a=lay[0], b=lay[1], out=lay[2], mask=mask, epilogue=2 if kind == "fwd" else None,
+                                       want_bias=flag and kind == "bwd_weight")
+                if v["status"] == 0:
+                    seen.add((v["op"], v["kernel"], v["coalesced"], v["bias"]))
+    assert seen == GC.ALL_VARIANTS, sorted(seen ^ GC.ALL_VARIANTS)
+
+
+def test_linear_variant_refuses_what_the_entry_points_refuse():
+    import svr_amd  # noqa: F401
+    from svr_amd import _lib, ops
+    l = _lib.lib()
+    z = ctypes.c_void_p(0)
+    st = ctypes.c_int32()
+
+    def q(op, M, N, K, lds, los, epi=0):      # lds / los: (a, b, out, mask)
+        rc = l.svr_linear_variant(op, M, N, K, *lds, *los, epi, 0, z, z, z, z, z, ctypes.byref(st))      # (every output may be NULL)
+        return rc, st.value
+    O = ops.LINEAR_OPS
+    assert q(9, 8, 32, 32, (32,) * 4, (0,) * 4)[0] == -1 and q(-1, 8, 32, 32, (32,) * 4, (0,) * 4)[0] == -1
+    assert q(O["fwd_f16x3"], 8, 32, 24, (24, 24, 32, 0), (0,) * 4) == (0, -2)               # K % 16
+    assert q(O["fwd_f16x3"], 8, 32, 32, (32, 32, 32, 0), (4, 0, 0, 0)) == (0, -3)           # X misaligned
+    assert q(O["fwd_f16x3"], 8, 32, 32, (32, 32, 33, 0), (0, 0, 4, 0)) == (0, 0)            # Y: any layout (per-lane epilogue)
+    assert q(O["bwd_data_f32"], 8, 32, 30, (32, 30, 30, 0), (0,) * 4) == (0, -2)            # K % 4
+    # the float4 epilogue of linear_nn_x3_kernel: dX and the mask must be 16-byte aligned, in both splits
+    for op in ("bwd_data_bf16x3", "bwd_data_f16x3s"):
+        assert q(O[op], 8, 32, 36, (32, 36, 40, 40), (0,) * 4, 3) == (0, 0), op
+        assert q(O[op], 8, 32, 36, (32, 36, 40, 40), (0, 0, 4, 0), 3) == (0, -3), op
+        assert q(O[op], 8, 32, 36, (32, 36, 40, 40), (0, 0, 0, 8), 3) == (0, -3), op
+        assert q(O[op], 8, 32, 36, (32, 36, 40, 40), (0, 0, 0, 8), 0) == (0, 0), op        # no mask epilogue: its bits do not matter
+    # ... and ops.linear_bwd_data sends such operands to the exact-f32 kernel, as the f16x3s chain always did
+    for mode in ("bf16x3", "f16x3s"):
+        v = ops.linear_variant("bwd_data", mode, 8, 32, 36, out=(40, 4, True))
+        assert (v["op"], v["kernel"], v["status"]) == ("bwd_data_f32", "nn", 0), (mode, v)
+        v = ops.linear_variant("bwd_data", mode, 8, 32, 36, mask=(40, 12, True))
+        assert (v["op"], v["kernel"], v["status"]) == ("bwd_data_f32", "nn", 0), (mode, v)
+    assert q(O["bwd_weight_f16x3s"], 8, 8, 6, (8, 6, 6, 0), (0,) * 4) == (0, -2)
+    assert q(O["bwd_weight_bf16x3"], 8, 6, 8, (6, 8, 8, 0), (0,) * 4) == (0, -2)            # N % 4
+    assert q(O["bwd_weight_bf16x3"], 8, 8, 6, (8, 6, 6, 0), (0,) * 4) == (0, 0)             # K % 4 != 0: the pre-pass path
