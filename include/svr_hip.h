@@ -964,6 +964,68 @@ int svr_raycast_eval(const double *tri, int64_t F, const float *consts /*[12]*/,
                      float *depth, int32_t *face, float *distance, float *normal, uint8_t *shade, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Vertex colours of a mesh from the image it was reconstructed from (no reference op: the reference shows coloured results
+ * but ships no code for them; util/mesh_color.py drives this, tests/vertex_color_oracle.py restates it in numpy).  Errors,
+ * ownership and streams as for svr_mc_*.  All arithmetic is float64, one rounding per operation (no contraction); a
+ * comparison with NaN is false.
+ *   verts: (V, 3) float32 on the device, grid index space (the space of svr_raycast_*: the caller divides lattice indices
+ *   by inf_res first).  consts: the 12 float32 constants of svr_unproject_fwd in HOST memory, each widened first (dims
+ *   unused).  depth: (H, W) float32 on the device, the SAME mesh seen from the same camera (svr_raycast_eval's depth with
+ *   miss = 0).  image: (Hi, Wi, 3) uint8 on the device.  map: {ax, bx, ay, by}, HOST float64: depth-map pixel (u, v) lies at
+ *   image position (ax*u + bx, ay*v + by), pixel centres at integers in both.  fill: 3 HOST uint8.  bias: metres.
+ *   svr_vertex_color_sample, per vertex g, in this order:
+ *     1. zc = (g2 - t2) / s22;  u = cx + (f*(g0 - t0)) / (s00*zc);  v = cy - (f*(g1 - t1)) / (s11*zc)
+ *        (svr_raycast_face_bounds' projection);
+ *     2. in frame iff zc > 0 and -0.5 <= u <= W - 0.5 and -0.5 <= v <= H - 0.5;
+ *     3. seen iff one of the up to four pixels (floor(u) + a, floor(v) + b), a, b in {0, 1}, that lie inside
+ *        [0, W) x [0, H) has D > 0 and zc <= (double)D + bias.  A miss is 0 in such a map and never counts; neither does a
+ *        negative or NaN D; D = inf sees every vertex in front of it;
+ *     4. x = ax*u + bx;  y = ay*v + by;  inside iff -0.5 <= x <= Wi - 0.5 and -0.5 <= y <= Hi - 0.5 (the border that
+ *        SquarePad adds around the image is outside);
+ *     5. x0 = floor(x), wx = x - x0, columns clamp(x0, 0, Wi-1) and clamp(x0 + 1, 0, Wi-1); rows likewise from y0, wy;
+ *        per channel, p{column}{row} the four pixels: top = p00 + wx*(p10 - p00); bot = p01 + wx*(p11 - p01);
+ *        val = top + wy*(bot - top); the colour is (uint8)rint(val), half to even;
+ *     6. colors (V, 3) uint8 = that colour and state (V) uint8 = 1 when 2, 3 and 4 hold; else colors = fill, state = 0.
+ *     V == 0 is a no-op.  H, W, Hi, Wi outside [1, 32768]: SVR_E_BADSHAPE.
+ *   svr_vertex_color_spread: vertices the camera does not see take colour along mesh edges.  One pass goes over every face
+ *     (i0, i1, i2) and each of its six ordered corner pairs (s, d): if state[s] != 0 and state[d] == 0 AT THE START OF THE
+ *     PASS, colors[s] is added per channel into sum[d] and 1 into count[d] (uint32 both; an edge shared by two faces counts
+ *     twice).  After the pass every vertex with count > 0 gets colors = (2*sum + count) / (2*count) per channel, in integer
+ *     division (the mean, rounded half up), and state = 2.  Passes repeat until one changes nothing or until max_passes
+ *     (negative: no limit; V passes always suffice).  Vertices never reached -- components without a seen vertex, vertices
+ *     of no face -- keep their colour and state 0.  A face with an index outside [0, V) is ignored.  The sums are integers,
+ *     so the order in which the atomics arrive cannot change a bit: the result is the same on every run.
+ *     faces: (F, 3) int32 on the device; colors / state: svr_vertex_color_sample's outputs, updated in place; ws:
+ *     svr_vertex_color_workspace_bytes(V) device bytes (negative = SVR_E_BADSHAPE: V outside [0, 2^31)), need not be
+ *     zeroed.  The host reads a device counter of changed vertices back after every check_every (>= 1) passes and stops when
+ *     it has not moved; passes past the fixed point change nothing, so the result does not depend on check_every.  *passes
+ *     (HOST, optional): the passes launched: whole intervals up to and including the first in which nothing changed, never
+ *     more than max_passes or V + 1.  The call synchronises the stream.
+ *   svr_write_ply: host only; verts (nv, 3) float32, colors (nv, 3) uint8 and faces (nf, 3) int32 HOST arrays -> a binary
+ *     little-endian PLY: the header below (LF line ends, the two counts in decimal), then per vertex 12 + 3 bytes (x, y, z,
+ *     red, green, blue), then per face 1 + 12 bytes (the count 3, three indices, 0-based).  SVR_E_IO on a failed open / write.
+ *       ply
+ *       format binary_little_endian 1.0
+ *       element vertex <nv>
+ *       property float x
+ *       property float y
+ *       property float z
+ *       property uchar red
+ *       property uchar green
+ *       property uchar blue
+ *       element face <nf>
+ *       property list uchar int vertex_indices
+ *       end_header
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_vertex_color_workspace_bytes(int64_t V);
+int svr_vertex_color_sample(const float *verts, int64_t V, const float *consts /*[12]*/, const float *depth, int32_t H, int32_t W,
+                            double bias, const uint8_t *image, int32_t Hi, int32_t Wi, const double *map /*[4]*/,
+                            const uint8_t *fill /*[3]*/, uint8_t *colors, uint8_t *state, void *stream);
+int svr_vertex_color_spread(const int32_t *faces, int64_t F, int64_t V, uint8_t *colors, uint8_t *state, void *ws, int64_t ws_bytes,
+                            int64_t max_passes, int32_t check_every, int64_t *passes, void *stream);
+int svr_write_ply(const char *path, const float *verts, const uint8_t *colors, int64_t nv, const int32_t *faces, int64_t nf);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * Host side (plain C++ + zlib; `out` / `payload` are HOST buffers, ideally pinned):

@@ -177,6 +177,11 @@ SIGNATURES = {
     "svr_raycast_emit": (C.c_int, [P, I64, I32, I32, I32, P, I64, I64, P, I64, P]),
     "svr_raycast_eval": (C.c_int, [P, I64, C.POINTER(F32), I32, I32, I32, C.c_double, C.c_double, F32, P, P, I64, I64, P, P, P,
                                    P, P, P]),
+    "svr_vertex_color_workspace_bytes": (I64, [I64]),
+    "svr_vertex_color_sample": (C.c_int, [P, I64, C.POINTER(F32), P, I32, I32, C.c_double, P, I32, I32, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_uint8), P, P, P]),
+    "svr_vertex_color_spread": (C.c_int, [P, I64, I64, P, P, P, I64, I64, I32, C.POINTER(I64), P]),
+    "svr_write_ply": (C.c_int, [C.c_char_p, P, P, I64, P, I64]),
     "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),

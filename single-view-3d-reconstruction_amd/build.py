@@ -35,6 +35,7 @@ SOURCES = {
     "mesh_eval.hip": ["-ffp-contract=off"],
     "mesh_df.hip": ["-ffp-contract=off"],
     "raycast.hip": ["-ffp-contract=off"],
+    "vertex_color.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "exr_io.cpp": [],
     "raw_sample.hip": ["-ffp-contract=off"],

@@ -25,8 +25,14 @@ predicted mesh's: "grid" = lattice index space as ``--test`` writes it; "normali
 inverse of ``projection._camera_to_grid(intrinsic, scale_factor)`` (vertices / inf_res first when inf_res > 1: the lattice
 index is inf_res times the grid coordinate), in csrc/rgb_preprocess.hip's svr_grid_to_camera.
 
+A ``reconstruct`` result also keeps `image`, the (Hi, Wi, 3) uint8 device tensor the network saw (after the flip, before the
+pad), and `pixel_map` (``input_pixel_map``).  ``colorize()`` puts that image back onto the predicted mesh: `colors` (V, 3)
+uint8 and `color_state` (V,) uint8 (util/mesh_color.py).  ``save(prefix, color=True)`` also writes
+``<prefix>_predicted.ply`` (key "predicted_ply"): the vertices in `space` with those colours; without `color` nothing changes.
+
 ``python -m svr_amd.reconstruct --checkpoint C (--rgb a.png [b.png ...] | --distance d.exr) --out DIR [--inf_res n]
-[--block s] [--space grid|normalized|camera] [--flip]`` prints one line per view: the written paths, vertex and face counts."""
+[--block s] [--space grid|normalized|camera] [--flip] [--color [--color_bias metres]]`` prints one line per view: the written
+paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour state."""
 import argparse
 import os
 from pathlib import Path
@@ -39,7 +45,8 @@ from . import ops
 from .data_processing import sample_io
 from .data_processing.distance_to_depth import FromDistanceToDepth, get_intrinsic
 from .model.ifnet import implicit_to_vertices
-from .util.visualize import export_obj, visualize_depthmap, visualize_grid
+from .util.mesh_color import DEFAULT_FILL, IDENTITY_MAP, vertex_colors
+from .util.visualize import export_obj, export_ply, visualize_depthmap, visualize_grid
 
 SPACES = ("grid", "normalized", "camera")
 
@@ -47,11 +54,19 @@ SPACES = ("grid", "normalized", "camera")
 class Reconstruction:
     """One view's result (module docstring)."""
 
-    def __init__(self, depth, point_cloud, voxel_occupancy, vertices, faces, scale_factor, inf_res, scale_shift, intrinsic=None):
+    def __init__(self, depth, point_cloud, voxel_occupancy, vertices, faces, scale_factor, inf_res, scale_shift, intrinsic=None,
+                 image=None, pixel_map=None):
         self.depth, self.point_cloud, self.voxel_occupancy = depth, point_cloud, voxel_occupancy
         self.vertices, self.faces = vertices, faces
         self._scale_factor, self._inf_res, self._scale_shift = scale_factor, int(inf_res), scale_shift
         self._intrinsic = intrinsic                     # 4x4 of the input camera; None: the pipeline's default
+        self.image = image                              # (Hi, Wi, 3) uint8 on the device: what the network saw; None: a depth-only result
+        self.pixel_map = IDENTITY_MAP if pixel_map is None else tuple(pixel_map)      # depth-map pixel -> image position
+        self.colors = self.color_state = None           # colorize()'s results
+
+    def _camera_consts(self):
+        K = self._intrinsic if self._intrinsic is not None else get_intrinsic()
+        return [float(K[0][0]), float(K[0][2]), float(K[1][2])] + [float(v) for v in self._scale_shift] + [0.0, 0.0, 0.0]
 
     def render_depth(self, size=None, **kw):
         """The predicted mesh ray-cast from the input camera (data_processing.render_view.render_depth; `kw` goes there):
@@ -60,8 +75,7 @@ class Reconstruction:
         from .data_processing.render_view import render_depth
         if self.faces is None or int(self.faces.shape[0]) == 0:
             return None
-        K = self._intrinsic if self._intrinsic is not None else get_intrinsic()
-        consts = [float(K[0][0]), float(K[0][2]), float(K[1][2])] + [float(v) for v in self._scale_shift] + [0.0, 0.0, 0.0]
+        consts = self._camera_consts()
         if size is None:
             size = tuple(self.depth.shape[-2:]) if self.depth is not None else (240, 320)
         v = self.vertices if self._inf_res == 1 else self.vertices / float(self._inf_res)
@@ -84,7 +98,35 @@ class Reconstruction:
             return ops.grid_to_camera(v, self._scale_shift)
         raise ValueError(f"space must be one of {SPACES}, got {space!r}")
 
-    def save(self, prefix, space="grid"):
+    def colorize(self, image=None, bias=None, spread=True, fill=DEFAULT_FILL, max_passes=None, pixel_map=None):
+        """Colour the predicted mesh's vertices from the input image (util.mesh_color.vertex_colors):
+        the mesh is ray-cast from the input camera at the depth map's size (``render_depth``), a vertex that render sees takes
+        the image's bilinear sample at its projection, and with `spread` the others take colour along mesh edges.  Stores and
+        returns `colors` (V, 3) uint8 and `color_state` (V,) uint8 (1 seen, 2 spread, 0 unreached = `fill`) on the device.
+        `image` (anything ``reconstruct`` takes) replaces the stored image and then maps through `pixel_map` (ax, bx, ay, by;
+        default the identity); a ``reconstruct_depth`` result stores no image and needs it.  `bias`: vertex_colors' (None: one
+        grid cell)."""
+        if image is not None:
+            img = _pixels(image)
+            img = (img if torch.is_tensor(img) else torch.from_numpy(img)).to(self.vertices.device).contiguous()
+            pm = IDENTITY_MAP if pixel_map is None else tuple(pixel_map)
+        elif self.image is not None:
+            img, pm = self.image, self.pixel_map if pixel_map is None else tuple(pixel_map)
+        else:
+            raise RuntimeError("colorize: this result was reconstructed from a depth map and holds no image to take colours "
+                               "from; pass image= (and pixel_map= unless its pixels are the depth map's)")
+        V = int(self.vertices.shape[0])
+        depth = self.render_depth()
+        if depth is None:                                # no face: nothing is seen, nothing spreads
+            self.colors = torch.tensor(fill, dtype=torch.uint8, device=self.vertices.device).repeat(V, 1)
+            self.color_state = torch.zeros(V, dtype=torch.uint8, device=self.vertices.device)
+            return self.colors, self.color_state
+        v = self.vertices if self._inf_res == 1 else self.vertices / float(self._inf_res)
+        self.colors, self.color_state = vertex_colors(v, self.faces, img, depth, self._camera_consts(), pixel_map=pm, bias=bias,
+                                                      spread=spread, fill=fill, max_passes=max_passes)
+        return self.colors, self.color_state
+
+    def save(self, prefix, space="grid", color=False):
         vertices = self.vertices_in(space)
         prefix = os.fspath(prefix)
         if os.path.dirname(prefix):
@@ -97,7 +139,26 @@ class Reconstruction:
         visualize_depthmap(self.depth, prefix + "_depthmap", flip=True)
         if not os.path.exists(paths["voxelized"]):
             del paths["voxelized"]
+        if color:
+            if self.colors is None:
+                self.colorize()
+            paths["predicted_ply"] = prefix + "_predicted.ply"
+            export_ply(vertices, self.faces, self.colors, paths["predicted_ply"])
         return paths
+
+
+def input_pixel_map(Hi, Wi, resize_input):
+    """(ax, bx, ay, by): where depth-map pixel (u, v) of the 240 x 320 output lies in the (Hi, Wi) image the network saw.
+    Without resize_input the two grids coincide.  With it, ops.rgb_preprocess pads the image to a square (pad = (m - n) // 2 on
+    both sides of the shorter axis), the network works on the resized square, and the depth map is rows 40..279 of the
+    320 x 320 square: pixel centres map linearly, centre (v + 40 + 0.5) / 320 of the square to the same share of the padded
+    image.  Positions in the padded border come out outside [-0.5, n - 0.5]."""
+    if not resize_input:
+        return IDENTITY_MAP
+    m = max(Hi, Wi)
+    pad_y, pad_x = (m - Hi) // 2, (m - Wi) // 2
+    ay, ax = (Hi + 2 * pad_y) / 320, (Wi + 2 * pad_x) / 320
+    return (ax, 0.5 * ax - 0.5 - pad_x, ay, 40.5 * ay - 0.5 - pad_y)
 
 
 def _pixels(image):
@@ -135,7 +196,7 @@ class Reconstructor:
     def device(self):
         return next(self.model.ifnet.parameters()).device
 
-    def _views(self, depth, point_cloud, voxel_occupancy):
+    def _views(self, depth, point_cloud, voxel_occupancy, images=None):
         m, h = self.model, self.model.hparams
         dims = m.dims.cpu().numpy().astype(np.int32)
         inf_res = int(getattr(h, "inf_res", 1))
@@ -144,8 +205,10 @@ class Reconstructor:
         for i in range(depth.shape[0]):
             vox = voxel_occupancy[i]
             vertices, faces = implicit_to_vertices(m.ifnet, vox.reshape(1, 1, *vox.shape[-3:]), dims, 0.5, inf_res, self.block)
+            image = None if images is None else images[i]
+            pixel_map = None if images is None else input_pixel_map(int(image.shape[0]), int(image.shape[1]), bool(h.resize_input))
             views.append(Reconstruction(depth[i], point_cloud[i], vox, vertices, faces, h.scale_factor, inf_res, scale_shift,
-                                        m.project.intrinsic))
+                                        m.project.intrinsic, image, pixel_map))
         return views
 
     def preprocess(self, pixels, flip=False):
@@ -169,7 +232,8 @@ class Reconstructor:
             for indices in groups.values():
                 batch = torch.stack([torch.as_tensor(pixels[i]).to(self.device) for i in indices])
                 depth = self.model._predict_depth(self.preprocess(batch, flip))
-                for i, view in zip(indices, self._views(depth, *self.model._voxels_from_depth(depth))):
+                seen = batch.flip(2) if flip else batch                # what the network saw, before the pad
+                for i, view in zip(indices, self._views(depth, *self.model._voxels_from_depth(depth), images=seen)):
                     out[i] = view
         return out[0] if single else out
 
@@ -202,16 +266,25 @@ def main(argv=None):
     parser.add_argument("--block", type=int, default=None, help="sparse lattice block edge, 0 = dense (default: SVR_INF_BLOCK)")
     parser.add_argument("--space", choices=SPACES, default="grid", help="space of the predicted mesh")
     parser.add_argument("--flip", action="store_true", help="mirror the images left-right first")
+    parser.add_argument("--color", action="store_true", help="also write <name>_predicted.ply with vertex colours from the image")
+    parser.add_argument("--color_bias", type=float, default=None, help="visibility bias in metres (default: one grid cell)")
     args = parser.parse_args(argv)
-    rec = Reconstructor.from_checkpoint(args.checkpoint, inf_res=args.inf_res, skip_unet=True if args.distance else None,
+    if args.color and args.distance:
+        parser.error("--color needs --rgb: a distance map carries no colours")
+    rec =Reconstructor.from_checkpoint(args.checkpoint, inf_res=args.inf_res, skip_unet=True if args.distance else None,
                                         block=args.block)
     if args.distance:
         names, views = [Path(args.distance).stem], [rec.reconstruct_depth(args.distance)]
     else:
         names, views = [Path(p).stem for p in args.rgb], rec.reconstruct(list(args.rgb), flip=args.flip)
     for name, view in zip(names, views):
-        paths = view.save(Path(args.out) / name, space=args.space)
-        print(" ".join(paths.values()), f"vertices={view.vertices.shape[0]} faces={view.faces.shape[0]}")
+        counts = ""
+        if args.color:
+            _, state = view.colorize(bias=args.color_bias)
+            n = torch.bincount(state.long(), minlength=3).tolist()
+            counts = f" seen={n[1]} spread={n[2]} unreached={n[0]}"
+        paths = view.save(Path(args.out) / name, space=args.space, color=args.color)
+        print(" ".join(paths.values()), f"vertices={view.vertices.shape[0]} faces={view.faces.shape[0]}" + counts)
     return 0
 
 

@@ -11,6 +11,7 @@ face order, outward winding, open surfaces at the lattice border) are in include
 
 ``export_obj(vertices, faces, path)``: `v x y z` lines (%.9g: float32 round trip), then 1-based `f a b c` lines,
 written by the library's C++ host code.  ``visualize_sdf(sdf, output_path, level=0.75)``: the two together.
+``export_ply(vertices, faces, colors, path)``: the same mesh with one uint8 RGB colour per vertex, as a binary PLY.
 
 The other functions of the reference's util/visualize.py (:10-20,28-49), which the scene trainer's validation / test
 steps call (kernels and host writers in csrc/voxel_mesh.hip):
@@ -82,6 +83,18 @@ def export_obj(vertices, faces, path):
     f = _host(faces, np.int32).reshape(-1, 3)
     check(_lib.lib().svr_write_obj(os.fsencode(path), v.ctypes.data_as(C.c_void_p), len(v), f.ctypes.data_as(C.c_void_p),
                                    len(f)), "write_obj")
+
+
+def export_ply(vertices, faces, colors, path):
+    """A binary little-endian PLY with per-vertex `uchar red green blue` (the header text is in include/svr_hip.h):
+    `colors` is (V, 3) uint8, one row per vertex; host arrays or device tensors, like export_obj."""
+    v = _host(vertices, np.float32).reshape(-1, 3)
+    f = _host(faces, np.int32).reshape(-1, 3)
+    c = _host(colors, np.uint8).reshape(-1, 3)
+    if len(c) != len(v):
+        raise ValueError(f"export_ply: {len(c)} colours for {len(v)} vertices")
+    check(_lib.lib().svr_write_ply(os.fsencode(path), v.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), len(v),
+                                   f.ctypes.data_as(C.c_void_p), len(f)), "write_ply")
 
 
 def visualize_sdf(sdf, output_path, level=0.75):
