@@ -735,8 +735,6 @@ int svr_mesh_contains(const void *points, int32_t points_f64, int64_t n, const d
  *   svr_mc_emit:   fills verts / faces from the same field, level and workspace (after svr_mc_count on the stream).
  *   svr_mc_case_table: host only; out[256 * 16] = the kernels' case table, 3 edge ids per triangle, -1 padded
  *                  (edge 4 * axis + (o_u | o_v << 1), corner c at offset (c & 1, c >> 1 & 1, c >> 2 & 1)).
- *   svr_write_obj: host only; verts (nv, 3) float32 and faces (nf, 3) int32 HOST arrays -> `v x y z` lines (%.9g,
- *                  float32 round trip) then `f a b c` lines (1-based).  SVR_E_IO on a failed open / write.
  * ------------------------------------------------------------------------------------- */
 int64_t svr_mc_workspace_bytes(int32_t X, int32_t Y, int32_t Z);
 int svr_mc_count(const float *field, int32_t X, int32_t Y, int32_t Z, double level, void *ws, int64_t ws_bytes,
@@ -744,7 +742,6 @@ int svr_mc_count(const float *field, int32_t X, int32_t Y, int32_t Z, double lev
 int svr_mc_emit(const float *field, int32_t X, int32_t Y, int32_t Z, double level, void *ws, float *verts, int32_t *faces,
                 void *stream);
 int svr_mc_case_table(int8_t *out);
-int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf);
 
 /* ---------------------------------------------------------------------------------------
  * Block-sparse evaluation of the occupancy lattice in front of svr_mc_* (not a reference op: a coarse-to-fine
@@ -1001,21 +998,6 @@ int svr_raycast_eval(const double *tri, int64_t F, const float *consts /*[12]*/,
  *     it has not moved; passes past the fixed point change nothing, so the result does not depend on check_every.  *passes
  *     (HOST, optional): the passes launched: whole intervals up to and including the first in which nothing changed, never
  *     more than max_passes or V + 1.  The call synchronises the stream.
- *   svr_write_ply: host only; verts (nv, 3) float32, colors (nv, 3) uint8 and faces (nf, 3) int32 HOST arrays -> a binary
- *     little-endian PLY: the header below (LF line ends, the two counts in decimal), then per vertex 12 + 3 bytes (x, y, z,
- *     red, green, blue), then per face 1 + 12 bytes (the count 3, three indices, 0-based).  SVR_E_IO on a failed open / write.
- *       ply
- *       format binary_little_endian 1.0
- *       element vertex <nv>
- *       property float x
- *       property float y
- *       property float z
- *       property uchar red
- *       property uchar green
- *       property uchar blue
- *       element face <nf>
- *       property list uchar int vertex_indices
- *       end_header
  * ------------------------------------------------------------------------------------- */
 int64_t svr_vertex_color_workspace_bytes(int64_t V);
 int svr_vertex_color_sample(const float *verts, int64_t V, const float *consts /*[12]*/, const float *depth, int32_t H, int32_t W,
@@ -1023,14 +1005,11 @@ int svr_vertex_color_sample(const float *verts, int64_t V, const float *consts /
                             const uint8_t *fill /*[3]*/, uint8_t *colors, uint8_t *state, void *stream);
 int svr_vertex_color_spread(const int32_t *faces, int64_t F, int64_t V, uint8_t *colors, uint8_t *state, void *ws, int64_t ws_bytes,
                             int64_t max_passes, int32_t check_every, int64_t *passes, void *stream);
-int svr_write_ply(const char *path, const float *verts, const uint8_t *colors, int64_t nv, const int32_t *faces, int64_t nf);
 
 /* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
- * Host side (plain C++ + zlib; `out` / `payload` are HOST buffers, ideally pinned):
- *   .df  = 3 x uint64 dims (X, Y, Z) + X*Y*Z float32, x fastest;
- *   .npz = zip of .npy members (stored by np.savez, deflated by np.savez_compressed; zip64 local headers).
+ * The files are read on the host (svr_df_* / svr_npz_*: File formats, below).
  * Device side: x-fastest -> C-order transpose of a .df payload, casts to float32, and the random row subset of
  * implicit_dataset.py:40-43 as a gather with cast (idx: device int64; rows outside [0, n_rows) set *bad_flag).
  * ------------------------------------------------------------------------------------- */
@@ -1040,15 +1019,6 @@ int svr_write_ply(const char *path, const float *verts, const uint8_t *colors, i
 #define SVR_DT_U8 3
 #define SVR_DT_I32 4
 #define SVR_DT_I64 5
-int svr_df_dims(const char *path, int64_t *dims /*[3]*/);
-int svr_df_read(const char *path, float *payload, int64_t n);
-/* svr_df_write: host only; the inverse of svr_df_dims + svr_df_read: three little-endian uint64 extents, then the X*Y*Z
- *   float32 values of `payload` (HOST, x fastest).  SVR_E_IO on a failed open or write, SVR_E_BADARG for an extent outside [1, 2^20), the range
- *   svr_df_dims accepts. */
-int svr_df_write(const char *path, const float *payload, int64_t X, int64_t Y, int64_t Z);
-int svr_npz_member_info(const char *path, const char *member, int32_t *dtype, int32_t *ndim, int64_t *shape /*[8]*/,
-                        int32_t *fortran_order);
-int svr_npz_member_read(const char *path, const char *member, void *out, int64_t nbytes);
 int svr_df_to_grid(const float *payload, float *out /*(X,Y,Z) C order*/, int32_t X, int32_t Y, int32_t Z, void *stream);
 int svr_cast_to_f32(const void *in, int32_t dtype, float *out, int64_t n, void *stream);
 int svr_subsample_rows(const void *rows, int32_t dtype, int64_t n_rows, int32_t cols, const int64_t *idx, int64_t n_idx,
@@ -1075,20 +1045,8 @@ int svr_subsample_rows_batched(const svr_row_segment *segments, const int64_t *e
                                const int64_t *idx, float *out, int32_t *bad_flag, void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * Raw views (data_processing/distance_to_depth.py, process_sample.py:17-21, dataset/scene_net_data.py:77-84).
- *
- * OpenEXR subset, host side (plain C++ + zlib; errors through svr_last_error):
- *   read: single-part scanline files; compression NONE (0), ZIPS (2), ZIP (3); pixel types UINT (0), HALF (1),
- *   FLOAT (2); any channel count (the file's alphabetical order); lineOrder 0 / 1; any data-window origin; blocks stored
- *   raw because deflate did not shrink them.  Refused by name: tiled / multi-part / deep files, subsampled channels, every
- *   other compression.  A truncated file or an offset beyond it is SVR_E_IO, never a read outside the file's bytes.
- *   svr_exr_info: width, height, origin[2] = the data window's (x, y) minimum, the channel count, compression, lineOrder;
- *     names (optional) receives the channel names, each NUL terminated, back to back (names_bytes of room);
- *     pixel_types (optional) one code per channel; both need max_channels >= the channel count.
- *   svr_exr_read_channel: one channel as float32 (HALF widened, UINT converted), (H, W) row major, top scanline of the
- *     data window first, into `out` (host, n = W * H values; pinned memory is fine).  Unknown name: SVR_E_NOTFOUND.
- *   svr_exr_write: data = (n_channels, H, W) float32 planes in the order of `names` (NUL terminated, back to back) ->
- *     an uncompressed FLOAT scanline file, data window (0,0)-(W-1,H-1), channels sorted by name.
+ * Raw views (data_processing/distance_to_depth.py, process_sample.py:17-21, dataset/scene_net_data.py:77-84).  The .exr
+ * files are read on the host (svr_exr_*: File formats, below).
  *
  * Device side (raw_sample.hip):
  *   svr_distance_to_depth: depth = sqrt(d*d / ((r*r + c*c) / (f*f) + 1)) over (B, H, W), r = row - H/2, c = col - W/2
@@ -1100,10 +1058,6 @@ int svr_subsample_rows_batched(const svr_row_segment *segments, const int64_t *e
  *     A pixel whose rounded index leaves [0, D) on any axis (NaN / inf included; indices in [-D, 0) are NOT wrapped) is
  *     not written and adds 1 to *out_of_range (device int32, zeroed by the caller).  coords (optional): (H*W, 3) float32.
  * ------------------------------------------------------------------------------------- */
-int svr_exr_info(const char *path, int32_t *width, int32_t *height, int32_t *origin /*[2]*/, int32_t *n_channels, char *names,
-                 int64_t names_bytes, int32_t *pixel_types, int32_t max_channels, int32_t *compression, int32_t *line_order);
-int svr_exr_read_channel(const char *path, const char *name, float *out, int64_t n);
-int svr_exr_write(const char *path, const float *data, int32_t H, int32_t W, const char *names, int32_t n_channels);
 int svr_distance_to_depth(const float *distance, float *depth, int32_t B, int32_t H, int32_t W, float focal, void *stream);
 int svr_depth_grid_mark(const float *map, int32_t is_distance, float focal, int32_t H, int32_t W, const float *consts /*[12]*/,
                         uint8_t *grid, int32_t D0, int32_t D1, int32_t D2, int32_t *out_of_range, float *coords, void *stream);
@@ -1137,12 +1091,6 @@ int svr_depth_grid_mark(const float *map, int32_t is_distance, float focal, int3
  *   svr_depth_planes: plane_f32[r][c] = d = map[r][flip ? W-1-c : c]; plane_u8[r][c] = (uint8)(255.0f / max * (d - min)):
  *     float32 division, subtraction and product, each rounded on its own, then truncation toward zero (a value past 255
  *     keeps its low 8 bits).  min / max are read from `stats` on the device.
- *
- * Host only:
- *   svr_write_png_gray8: data (H, W) uint8 -> a PNG file: signature, IHDR (bit depth 8, colour type 0, no interlace), one
- *     zlib-deflated IDAT with filter type 0 on every scanline, IEND, CRC-32 on every chunk.
- *   svr_write_obj_points: pts (n, 3) float32 -> one line `v %f %f %f %f %f %f` per point: the coordinates + 0.5 (added in
- *     float32, then widened) and the colour 1 1 1 (visualize_point_list, util/visualize.py:14-20).  n == 0: an empty file.
  * ------------------------------------------------------------------------------------- */
 int64_t svr_voxel_mesh_workspace_bytes(int32_t X, int32_t Y, int32_t Z);
 int svr_voxel_mesh_count(const float *field, int32_t X, int32_t Y, int32_t Z, double threshold, void *ws, int64_t ws_bytes,
@@ -1152,8 +1100,6 @@ int svr_voxel_mesh_emit(const float *field, int32_t X, int32_t Y, int32_t Z, dou
 int svr_depth_minmax(const float *map, int64_t n, uint32_t *stats /*[4]*/, void *stream);
 int svr_depth_planes(const float *map, int32_t H, int32_t W, int32_t flip, const uint32_t *stats, float *plane_f32,
                      uint8_t *plane_u8, void *stream);
-int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W);
-int svr_write_obj_points(const char *path, const float *pts, int64_t n);
 
 /* ---------------------------------------------------------------------------------------
  * Depth head of the UNet regressor (replaces trainer/trainer_unet.py:43-61: F.interpolate(size=S, bilinear) -> crop of
@@ -1219,6 +1165,71 @@ int svr_rgb_preprocess(const uint8_t *src, int32_t B, int32_t H, int32_t W, int3
                        const int32_t *table_x, int32_t Kx, const int32_t *table_y, int32_t Ky, const float *norm, uint8_t *tmp,
                        uint8_t *out_u8, float *out_f32, void *stream);
 int svr_grid_to_camera(const float *src, float *dst, int64_t n, const float *scale_shift, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * File formats (csrc/io_*.cpp, plain C++ + zlib): the readers and writers of the files the project shares with the
+ * reference's tools.  One contract for every entry point of this section: HOST pointers only (pinned memory is fine), no
+ * stream, no GPU needed -- nothing of ROCm is called and the files build with any C++17 compiler; the return value is 0
+ * or a negative SVR_E_* code with its text in svr_last_error() (thread local); no C++ exception crosses the ABI, and a
+ * malformed file is an error code, never a read outside the file's bytes or the caller's buffers.
+ *
+ * Meshes and images, written (svr_mc_*, svr_voxel_mesh_*, svr_vertex_color_*, svr_depth_planes make the arrays):
+ *   svr_write_obj: host only; verts (nv, 3) float32 and faces (nf, 3) int32 HOST arrays -> `v x y z` lines (%.9g,
+ *                  float32 round trip) then `f a b c` lines (1-based).  SVR_E_IO on a failed open / write.
+ *   svr_write_ply: host only; verts (nv, 3) float32, colors (nv, 3) uint8 and faces (nf, 3) int32 HOST arrays -> a binary
+ *     little-endian PLY: the header below (LF line ends, the two counts in decimal), then per vertex 12 + 3 bytes (x, y, z,
+ *     red, green, blue), then per face 1 + 12 bytes (the count 3, three indices, 0-based).  SVR_E_IO on a failed open / write.
+ *       ply
+ *       format binary_little_endian 1.0
+ *       element vertex <nv>
+ *       property float x
+ *       property float y
+ *       property float z
+ *       property uchar red
+ *       property uchar green
+ *       property uchar blue
+ *       element face <nf>
+ *       property list uchar int vertex_indices
+ *       end_header
+ *   svr_write_png_gray8: data (H, W) uint8 -> a PNG file: signature, IHDR (bit depth 8, colour type 0, no interlace), one
+ *     zlib-deflated IDAT with filter type 0 on every scanline, IEND, CRC-32 on every chunk.
+ *   svr_write_obj_points: pts (n, 3) float32 -> one line `v %f %f %f %f %f %f` per point: the coordinates + 0.5 (added in
+ *     float32, then widened) and the colour 1 1 1 (visualize_point_list, util/visualize.py:14-20).  n == 0: an empty file.
+ *
+ * Samples (`out` / `payload` ideally pinned; dtype codes: SVR_DT_*, above):
+ *   .df  = 3 x uint64 dims (X, Y, Z) + X*Y*Z float32, x fastest;
+ *   .npz = zip of .npy members (stored by np.savez, deflated by np.savez_compressed; zip64 local headers).
+ *
+ * OpenEXR subset:
+ *   read: single-part scanline files; compression NONE (0), ZIPS (2), ZIP (3); pixel types UINT (0), HALF (1),
+ *   FLOAT (2); any channel count (the file's alphabetical order); lineOrder 0 / 1; any data-window origin; blocks stored
+ *   raw because deflate did not shrink them.  Refused by name: tiled / multi-part / deep files, subsampled channels, every
+ *   other compression.  A truncated file or an offset beyond it is SVR_E_IO, never a read outside the file's bytes.
+ *   svr_exr_info: width, height, origin[2] = the data window's (x, y) minimum, the channel count, compression, lineOrder;
+ *     names (optional) receives the channel names, each NUL terminated, back to back (names_bytes of room);
+ *     pixel_types (optional) one code per channel; both need max_channels >= the channel count.
+ *   svr_exr_read_channel: one channel as float32 (HALF widened, UINT converted), (H, W) row major, top scanline of the
+ *     data window first, into `out` (host, n = W * H values; pinned memory is fine).  Unknown name: SVR_E_NOTFOUND.
+ *   svr_exr_write: data = (n_channels, H, W) float32 planes in the order of `names` (NUL terminated, back to back) ->
+ *     an uncompressed FLOAT scanline file, data window (0,0)-(W-1,H-1), channels sorted by name.
+ * ------------------------------------------------------------------------------------- */
+int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf);
+int svr_write_ply(const char *path, const float *verts, const uint8_t *colors, int64_t nv, const int32_t *faces, int64_t nf);
+int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W);
+int svr_write_obj_points(const char *path, const float *pts, int64_t n);
+int svr_df_dims(const char *path, int64_t *dims /*[3]*/);
+int svr_df_read(const char *path, float *payload, int64_t n);
+/* svr_df_write: host only; the inverse of svr_df_dims + svr_df_read: three little-endian uint64 extents, then the X*Y*Z
+ *   float32 values of `payload` (HOST, x fastest).  SVR_E_IO on a failed open or write, SVR_E_BADARG for an extent outside [1, 2^20), the range
+ *   svr_df_dims accepts. */
+int svr_df_write(const char *path, const float *payload, int64_t X, int64_t Y, int64_t Z);
+int svr_npz_member_info(const char *path, const char *member, int32_t *dtype, int32_t *ndim, int64_t *shape /*[8]*/,
+                        int32_t *fortran_order);
+int svr_npz_member_read(const char *path, const char *member, void *out, int64_t nbytes);
+int svr_exr_info(const char *path, int32_t *width, int32_t *height, int32_t *origin /*[2]*/, int32_t *n_channels, char *names,
+                 int64_t names_bytes, int32_t *pixel_types, int32_t max_channels, int32_t *compression, int32_t *line_order);
+int svr_exr_read_channel(const char *path, const char *name, float *out, int64_t n);
+int svr_exr_write(const char *path, const float *data, int32_t H, int32_t W, const char *names, int32_t n_channels);
 
 #ifdef __cplusplus
 }

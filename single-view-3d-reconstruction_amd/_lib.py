@@ -181,12 +181,10 @@ SIGNATURES = {
     "svr_vertex_color_sample": (C.c_int, [P, I64, C.POINTER(F32), P, I32, I32, C.c_double, P, I32, I32, C.POINTER(C.c_double),
                                           C.POINTER(C.c_uint8), P, P, P]),
     "svr_vertex_color_spread": (C.c_int, [P, I64, I64, P, P, P, I64, I64, I32, C.POINTER(I64), P]),
-    "svr_write_ply": (C.c_int, [C.c_char_p, P, P, I64, P, I64]),
     "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),
     "svr_mc_case_table": (C.c_int, [P]),
-    "svr_write_obj": (C.c_int, [C.c_char_p, P, I64, P, I64]),
     "svr_sl_workspace_bytes": (I64, [I32, I32, I32, I32]),
     "svr_sl_coarse_points": (C.c_int, [P, P, P, I32, I32, I32, I32, P, P]),
     "svr_sl_fill_seed": (C.c_int, [P, I32, I32, I32, I32, C.c_double, P, P, P, I64, P]),
@@ -194,18 +192,10 @@ SIGNATURES = {
     "svr_sl_block_points": (C.c_int, [P, P, P, I32, I32, I32, I32, P, I64, P, P]),
     "svr_sl_scatter": (C.c_int, [P, I32, I32, I32, I32, P, I64, I32, P, P, P]),
     "svr_sl_leak_check": (C.c_int, [P, I32, I32, I32, I32, C.c_double, P, P, I64, P, P]),
-    "svr_df_dims": (C.c_int, [C.c_char_p, P]),
-    "svr_df_read": (C.c_int, [C.c_char_p, P, I64]),
-    "svr_df_write": (C.c_int, [C.c_char_p, P, I64, I64, I64]),
-    "svr_npz_member_info": (C.c_int, [C.c_char_p, C.c_char_p, P, P, P, P]),
-    "svr_npz_member_read": (C.c_int, [C.c_char_p, C.c_char_p, P, I64]),
     "svr_df_to_grid": (C.c_int, [P, P, I32, I32, I32, P]),
     "svr_cast_to_f32": (C.c_int, [P, I32, P, I64, P]),
     "svr_subsample_rows": (C.c_int, [P, I32, I64, I32, P, I64, P, P, P]),
     "svr_subsample_rows_batched": (C.c_int, [P, P, I32, I64, P, P, P, P]),
-    "svr_exr_info": (C.c_int, [C.c_char_p, P, P, P, P, P, I64, P, I32, P, P]),
-    "svr_exr_read_channel": (C.c_int, [C.c_char_p, C.c_char_p, P, I64]),
-    "svr_exr_write": (C.c_int, [C.c_char_p, P, I32, I32, C.c_char_p, I32]),
     "svr_distance_to_depth": (C.c_int, [P, P, I32, I32, I32, F32, P]),
     "svr_depth_grid_mark": (C.c_int, [P, I32, F32, I32, I32, C.POINTER(F32), P, I32, I32, I32, P, P, P]),
     "svr_unproject_fwd": (C.c_int, [P, P, I32, I32, I32, C.POINTER(F32), C.c_int, P]),
@@ -225,8 +215,6 @@ SIGNATURES = {
     "svr_voxel_mesh_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),
     "svr_depth_minmax": (C.c_int, [P, I64, P, P]),
     "svr_depth_planes": (C.c_int, [P, I32, I32, I32, P, P, P, P]),
-    "svr_write_png_gray8": (C.c_int, [C.c_char_p, P, I32, I32]),
-    "svr_write_obj_points": (C.c_int, [C.c_char_p, P, I64]),
     "svr_depth_head_workspace": (I64, [I32, I32, I32]),
     "svr_depth_head_fwd": (C.c_int, [P, P, P, P, P, I32, I32, I32, I32, I32, I32, C.c_double, C.c_double, P, P]),
     "svr_depth_head_bwd": (C.c_int, [P, P, I32, I32, I32, I32, I32, I32, P]),
@@ -234,6 +222,19 @@ SIGNATURES = {
     "svr_rgb_resize_table": (C.c_int, [I32, I32, I32, P]),
     "svr_rgb_preprocess": (C.c_int, [P, I32, I32, I32, I32, I32, I32, P, I32, P, I32, P, P, P, P, P]),
     "svr_grid_to_camera": (C.c_int, [P, P, I64, C.POINTER(F32), P]),
+    # file formats (csrc/io_*.cpp): host pointers only, no stream, no GPU needed
+    "svr_write_obj": (C.c_int, [C.c_char_p, P, I64, P, I64]),
+    "svr_write_ply": (C.c_int, [C.c_char_p, P, P, I64, P, I64]),
+    "svr_write_png_gray8": (C.c_int, [C.c_char_p, P, I32, I32]),
+    "svr_write_obj_points": (C.c_int, [C.c_char_p, P, I64]),
+    "svr_df_dims": (C.c_int, [C.c_char_p, P]),
+    "svr_df_read": (C.c_int, [C.c_char_p, P, I64]),
+    "svr_df_write": (C.c_int, [C.c_char_p, P, I64, I64, I64]),
+    "svr_npz_member_info": (C.c_int, [C.c_char_p, C.c_char_p, P, P, P, P]),
+    "svr_npz_member_read": (C.c_int, [C.c_char_p, C.c_char_p, P, I64]),
+    "svr_exr_info": (C.c_int, [C.c_char_p, P, P, P, P, P, I64, P, I32, P, P]),
+    "svr_exr_read_channel": (C.c_int, [C.c_char_p, C.c_char_p, P, I64]),
+    "svr_exr_write": (C.c_int, [C.c_char_p, P, I32, I32, C.c_char_p, I32]),
 }
 
 _lib = None

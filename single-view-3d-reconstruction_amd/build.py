@@ -37,13 +37,22 @@ SOURCES = {
     "raycast.hip": ["-ffp-contract=off"],
     "vertex_color.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
-    "exr_io.cpp": [],
+    "io_npz.cpp": [],
+    "io_df.cpp": [],
+    "io_exr.cpp": [],
+    "io_mesh.cpp": [],
+    "io_png.cpp": [],
     "raw_sample.hip": ["-ffp-contract=off"],
     "conv2d.hip": [],
     "conv2d_igemm.hip": [],
     "depth_head.hip": ["-ffp-contract=off"],
     "rgb_preprocess.hip": ["-ffp-contract=off"],
 }
+# The host set: plain C++ (error plumbing, file formats), no device code and nothing from ROCm included; still compiled by
+# hipcc, so one toolchain builds the library, but as C++ and with HOST_COMMON.  Contraction is off for all of them
+# (svr_write_obj_points adds 0.5 in float32: one rounding per operation).  tests/test_fileio_host.py builds the same files with g++.
+HOST = ("capi.cpp", "io_npz.cpp", "io_df.cpp", "io_exr.cpp", "io_mesh.cpp", "io_png.cpp")
+HOST_COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-I" + INCLUDE, "-I" + CSRC]
 COMMON = ["-O3", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-std=c++17", "-I" + INCLUDE, "-I" + CSRC,
           # per-kernel register / scratch report into build/<file>.log (resource_usage() parses it: a kernel that starts to
           # spill is caught on the CPU, tests/test_capi_cpu.py -- round 3 lost 4.5x on the fused gather to 260 B/lane of scratch)
@@ -77,7 +86,7 @@ def build(force=False, verbose=False):
             continue
         obj = os.path.join(objdir, src.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
-        cmd = [_hipcc()] + COMMON + extra + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", path, "-o", obj]
+        cmd = [_hipcc()] + (HOST_COMMON if src in HOST else COMMON) + extra + ["-c", path, "-o", obj]
         # an object built with another command line (other COMMON flags, another compiler) is stale even if the source did not change
         flagfile = obj[:-2] + ".flags"
         same_flags = os.path.exists(flagfile) and open(flagfile).read() == " ".join(cmd)

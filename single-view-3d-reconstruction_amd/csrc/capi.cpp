@@ -1,5 +1,6 @@
 // Error plumbing + version for the C ABI (include/svr_hip.h).
-#include "common.h"
+#include "error.h"
+#include "svr_hip.h"
 #include <string.h>
 
 namespace svr {

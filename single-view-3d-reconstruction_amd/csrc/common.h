@@ -1,13 +1,9 @@
 // Shared host-side helpers for libsvr_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdarg.h>
-#include "svr_hip.h"
+#include "error.h"  // set_error, SVR_CHECK, svr_hip.h
 
 namespace svr {
-void set_error(const char *fmt, ...);
 inline int launch_status(const char *what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -80,11 +76,3 @@ __device__ __forceinline__ void svr_amax_publish(uint32_t *amax, float vmax) {
   }
 }
 #endif
-
-#define SVR_CHECK(cond, code, ...)      \
-  do {                                  \
-    if (!(cond)) {                      \
-      svr::set_error(__VA_ARGS__);      \
-      return (code);                    \
-    }                                   \
-  } while (0)

@@ -1,4 +1,4 @@
-// OpenEXR subset reader / writer (host C++ + zlib), next to the .df / .npz readers of sample_io.hip.
+// OpenEXR subset reader / writer (plain C++ + zlib), next to the .df / .npz readers (io_df.cpp, io_npz.cpp).
 //
 // The reference opens a view's distance.exr through pyexr (data_processing/distance_to_depth.py:84, dataset/
 // scene_net_data.py:77).  Read here: single-part scanline files, compression NONE / ZIPS / ZIP, pixel types HALF / FLOAT /
@@ -12,12 +12,9 @@
 // scanline channel by channel in the file's (alphabetical) order.  A ZIP(S) payload is zlib-deflated after the bytes were
 // split into even / odd halves and delta coded (t[i] = t[i-1] + d[i] - 128); a block that deflate did not shrink is
 // stored raw (packed size == raw size).
-#include "common.h"
+#include "io_bytes.h"
 #include <zlib.h>
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
-#include <exception>
 #include <string>
 #include <vector>
 
@@ -27,10 +24,6 @@ namespace {
 
 enum { PT_UINT = 0, PT_HALF = 1, PT_FLOAT = 2 };
 const char *kCompression[] = {"NONE", "RLE", "ZIPS", "ZIP", "PIZ", "PXR24", "B44", "B44A", "DWAA", "DWAB"};
-
-uint32_t rd16(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-uint32_t rd32(const unsigned char *p) { return rd16(p) | (rd16(p + 2) << 16); }
-uint64_t rd64(const unsigned char *p) { return (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32); }
 
 float half_to_float(uint32_t h) {
   const uint32_t s = (h & 0x8000u) << 16;
@@ -78,7 +71,8 @@ size_t cstring(const Exr &x, size_t p, size_t end, std::string &out) {
 
 int exr_open(const char *path, Exr &x, const char *what) {
   SVR_CHECK(path, SVR_E_BADARG, "%s: null path", what);
-  FILE *f = fopen(path, "rb");
+  File fh(path);
+  FILE *const f = fh.f;
   SVR_CHECK(f != nullptr, SVR_E_IO, "%s: cannot open %s", what, path);
   bool ok = fseek(f, 0, SEEK_END) == 0;
   const long size = ok ? ftell(f) : -1;
@@ -87,7 +81,6 @@ int exr_open(const char *path, Exr &x, const char *what) {
     x.b.resize((size_t)size);
     ok = fread(x.b.data(), 1, (size_t)size, f) == (size_t)size;
   }
-  fclose(f);
   SVR_CHECK(ok, SVR_E_IO, "%s: cannot read %s", what, path);
   SVR_CHECK(x.b.size() >= 8 && rd32(&x.b[0]) == 20000630u, SVR_E_IO, "%s: %s: not an OpenEXR file (bad magic)", what, path);
   const uint32_t ver = rd32(&x.b[4]);
@@ -157,7 +150,7 @@ int exr_open(const char *path, Exr &x, const char *what) {
               c.type);
   }
   x.lines = x.comp == 3 ? 16 : 1;
-  x.nblocks = cdiv(x.H, x.lines);
+  x.nblocks = (x.H + x.lines - 1) / x.lines;
   x.table = p;
   SVR_CHECK(x.has(p, 8 * (uint64_t)x.nblocks), SVR_E_IO, "%s: %s: truncated offset table (%ld blocks)", what, path, (long)x.nblocks);
   return SVR_OK;
@@ -256,8 +249,8 @@ int exr_read_channel_impl(const char *path, const char *name, float *out, int64_
   return SVR_OK;
 }
 
-void put32(std::vector<unsigned char> &b, uint32_t v) { for (int i = 0; i < 4; ++i) b.push_back((unsigned char)(v >> (8 * i))); }
-void put64(std::vector<unsigned char> &b, uint64_t v) { for (int i = 0; i < 8; ++i) b.push_back((unsigned char)(v >> (8 * i))); }
+void put32(std::vector<unsigned char> &b, uint32_t v) { b.resize(b.size() + 4); wr_le32(&b[b.size() - 4], v); }
+void put64(std::vector<unsigned char> &b, uint64_t v) { b.resize(b.size() + 8); wr_le64(&b[b.size() - 8], v); }
 void put_str(std::vector<unsigned char> &b, const char *s) { b.insert(b.end(), s, s + strlen(s) + 1); }
 void put_attr(std::vector<unsigned char> &b, const char *name, const char *type, const std::vector<unsigned char> &payload) {
   put_str(b, name);
@@ -265,11 +258,7 @@ void put_attr(std::vector<unsigned char> &b, const char *name, const char *type,
   put32(b, (uint32_t)payload.size());
   b.insert(b.end(), payload.begin(), payload.end());
 }
-void put_f32(std::vector<unsigned char> &b, float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  put32(b, u);
-}
+void put_f32(std::vector<unsigned char> &b, float f) { uint32_t u; memcpy(&u, &f, 4); put32(b, u); }
 
 int exr_write_impl(const char *path, const float *data, int32_t H, int32_t W, const char *names, int32_t n_channels) {
   SVR_CHECK(path && data && names, SVR_E_BADARG, "exr_write: null argument");
@@ -316,48 +305,33 @@ int exr_write_impl(const char *path, const float *data, int32_t H, int32_t W, co
   b.push_back(0);
   const uint64_t line = (uint64_t)W * 4 * ch.size(), first = b.size() + 8 * (uint64_t)H;
   for (int y = 0; y < H; ++y) put64(b, first + (uint64_t)y * (8 + line));
-  FILE *f = fopen(path, "wb");
-  SVR_CHECK(f != nullptr, SVR_E_IO, "exr_write: cannot open %s", path);
-  bool ok = fwrite(b.data(), 1, b.size(), f) == b.size();
-  for (int y = 0; y < H && ok; ++y) {
+  OutFile out(path);
+  SVR_CHECK(out.f != nullptr, SVR_E_IO, "exr_write: cannot open %s", path);
+  out.write(b.data(), 1, b.size());
+  for (int y = 0; y < H && out.ok; ++y) {
     b.clear();
     put32(b, (uint32_t)y);
     put32(b, (uint32_t)line);
-    ok = fwrite(b.data(), 1, 8, f) == 8;
-    for (size_t c = 0; c < ch.size() && ok; ++c)
-      ok = fwrite(data + ((int64_t)ch[c].second * H + y) * W, 4, (size_t)W, f) == (size_t)W;
+    out.write(b.data(), 1, 8);
+    for (size_t c = 0; c < ch.size(); ++c) out.write(data + ((int64_t)ch[c].second * H + y) * W, 4, (size_t)W);
   }
-  ok = (fclose(f) == 0) && ok;
-  SVR_CHECK(ok, SVR_E_IO, "exr_write: %s: write failed", path);
+  SVR_CHECK(out.close(), SVR_E_IO, "exr_write: %s: write failed", path);
   return SVR_OK;
-}
-
-// never throw across the ABI (std::bad_alloc on a garbage size, ...)
-template <typename F>
-int guard(const char *what, F &&body) {
-  try {
-    return body();
-  } catch (const std::exception &ex) {
-    SVR_CHECK(false, SVR_E_IO, "%s: malformed file (%s)", what, ex.what());
-  } catch (...) {
-    SVR_CHECK(false, SVR_E_IO, "%s: malformed file", what);
-  }
-  return SVR_E_IO;
 }
 
 }  // namespace
 
 extern "C" int svr_exr_info(const char *path, int32_t *width, int32_t *height, int32_t *origin, int32_t *n_channels, char *names,
                             int64_t names_bytes, int32_t *pixel_types, int32_t max_channels, int32_t *compression, int32_t *line_order) {
-  return guard("exr_info", [&] {
+  return io_guard("exr_info", [&] {
     return exr_info_impl(path, width, height, origin, n_channels, names, names_bytes, pixel_types, max_channels, compression, line_order);
   });
 }
 
 extern "C" int svr_exr_read_channel(const char *path, const char *name, float *out, int64_t n) {
-  return guard("exr_read_channel", [&] { return exr_read_channel_impl(path, name, out, n); });
+  return io_guard("exr_read_channel", [&] { return exr_read_channel_impl(path, name, out, n); });
 }
 
 extern "C" int svr_exr_write(const char *path, const float *data, int32_t H, int32_t W, const char *names, int32_t n_channels) {
-  return guard("exr_write", [&] { return exr_write_impl(path, data, H, W, names, n_channels); });
+  return io_guard("exr_write", [&] { return exr_write_impl(path, data, H, W, names, n_channels); });
 }

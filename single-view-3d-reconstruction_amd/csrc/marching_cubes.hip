@@ -16,16 +16,11 @@
 // cell's triangles; a triangle's edge resolves to (owner point, axis) -> owner's vertex offset + popcount of its lower
 // owned-edge bits).  The caller reads the two totals back (the only host synchronisation) to size the outputs.  While
 // V < 2^31 and F < 2^31 neither 32-bit half of the scan can carry into the other.
-//
-// Also here: svr_write_obj, the host-side .obj writer.
 #include "common.h"
 #include "mc_table.h"
 #include "reduce.h"
 #include <algorithm>
-#include <charconv>
 #include <cmath>
-#include <cstdio>
-#include <vector>
 
 using namespace svr;
 
@@ -214,47 +209,5 @@ extern "C" int svr_mc_case_table(int8_t *out) {
   SVR_CHECK(out, SVR_E_BADARG, "mc_case_table: null pointer");
   for (int c = 0; c < 256; ++c)
     for (int m = 0; m < 16; ++m) out[c * 16 + m] = kHostTable.edge[c][m];
-  return SVR_OK;
-}
-
-extern "C" int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf) {
-  SVR_CHECK(path && nv >= 0 && nf >= 0 && (verts || nv == 0) && (faces || nf == 0), SVR_E_BADARG, "write_obj: bad argument");
-  FILE *fp = fopen(path, "wb");
-  SVR_CHECK(fp, SVR_E_IO, "write_obj: cannot open %s", path);
-  std::vector<char> buf(1 << 20);
-  size_t used = 0;
-  bool ok = true;
-  auto flush = [&]() {
-    ok = ok && fwrite(buf.data(), 1, used, fp) == used;
-    used = 0;
-  };
-  // %.9g: every float32 reads back exactly, also through a float64 parse and a cast
-  for (int64_t i = 0; i < nv; ++i) {
-    if (used + 64 > buf.size()) flush();
-    char *c = buf.data() + used;
-    char *end = buf.data() + buf.size();
-    *c++ = 'v';
-    for (int a = 0; a < 3; ++a) {
-      *c++ = ' ';
-      c = std::to_chars(c, end, verts[i * 3 + a], std::chars_format::general, 9).ptr;
-    }
-    *c++ = '\n';
-    used = c - buf.data();
-  }
-  for (int64_t i = 0; i < nf; ++i) {
-    if (used + 48 > buf.size()) flush();
-    char *c = buf.data() + used;
-    char *end = buf.data() + buf.size();
-    *c++ = 'f';
-    for (int a = 0; a < 3; ++a) {
-      *c++ = ' ';
-      c = std::to_chars(c, end, (int64_t)faces[i * 3 + a] + 1).ptr;
-    }
-    *c++ = '\n';
-    used = c - buf.data();
-  }
-  flush();
-  ok = (fclose(fp) == 0) && ok;
-  SVR_CHECK(ok, SVR_E_IO, "write_obj: write to %s failed", path);
   return SVR_OK;
 }

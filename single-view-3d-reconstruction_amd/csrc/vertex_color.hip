@@ -1,4 +1,4 @@
-// Vertex colours of a mesh from the image it was reconstructed from, gfx950, and the .ply writer that carries them.
+// Vertex colours of a mesh from the image it was reconstructed from, gfx950 (the .ply writer that carries them: io_mesh.cpp).
 //
 // The rule is written down in include/svr_hip.h and restated in numpy by tests/vertex_color_oracle.py; the file is built
 // with -ffp-contract=off, so every float64 operation below rounds once, as numpy's does.
@@ -14,9 +14,6 @@
 #include "common.h"
 #include "reduce.h"
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <vector>
 
 using namespace svr;
 
@@ -216,41 +213,5 @@ extern "C" int svr_vertex_color_spread(const int32_t *faces, int64_t F, int64_t 
     seen = now;
   }
   if (passes) *passes = done;
-  return SVR_OK;
-}
-
-extern "C" int svr_write_ply(const char *path, const float *verts, const uint8_t *colors, int64_t nv, const int32_t *faces, int64_t nf) {
-  SVR_CHECK(path && nv >= 0 && nf >= 0 && ((verts && colors) || nv == 0) && (faces || nf == 0), SVR_E_BADARG, "write_ply: bad argument");
-  FILE *fp = fopen(path, "wb");
-  SVR_CHECK(fp, SVR_E_IO, "write_ply: cannot open %s", path);
-  char header[512];
-  const int hn = snprintf(header, sizeof(header),
-                          "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
-                          "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %lld\n"
-                          "property list uchar int vertex_indices\nend_header\n",
-                          (long long)nv, (long long)nf);
-  bool ok = fwrite(header, 1, (size_t)hn, fp) == (size_t)hn;
-  // gfx950's host is little-endian x86-64: floats and ints go out as they lie in memory
-  std::vector<unsigned char> buf;
-  constexpr int64_t kChunk = 1 << 16;
-  buf.resize((size_t)kChunk * 15);
-  for (int64_t i0 = 0; ok && i0 < nv; i0 += kChunk) {
-    const int64_t n = nv - i0 < kChunk ? nv - i0 : kChunk;
-    for (int64_t i = 0; i < n; ++i) {
-      memcpy(&buf[(size_t)i * 15], verts + (i0 + i) * 3, 12);
-      memcpy(&buf[(size_t)i * 15 + 12], colors + (i0 + i) * 3, 3);
-    }
-    ok = fwrite(buf.data(), 15, (size_t)n, fp) == (size_t)n;
-  }
-  for (int64_t i0 = 0; ok && i0 < nf; i0 += kChunk) {
-    const int64_t n = nf - i0 < kChunk ? nf - i0 : kChunk;
-    for (int64_t i = 0; i < n; ++i) {
-      buf[(size_t)i * 13] = 3;
-      memcpy(&buf[(size_t)i * 13 + 1], faces + (i0 + i) * 3, 12);
-    }
-    ok = fwrite(buf.data(), 13, (size_t)n, fp) == (size_t)n;
-  }
-  const bool closed = fclose(fp) == 0;
-  SVR_CHECK(ok && closed, SVR_E_IO, "write_ply: %s: write failed", path);
   return SVR_OK;
 }

@@ -1,5 +1,5 @@
 // Stage visualisation of the scene trainer, device side (gfx950): the voxel-box mesher behind visualize_grid and the two
-// image planes behind visualize_depthmap; host side: the 8-bit grayscale .png writer and the point-list .obj writer.
+// image planes behind visualize_depthmap (the .png and point-list .obj writers are io_png.cpp and io_mesh.cpp).
 //
 // Replaces the reference's util/visualize.py:10-20,28-49 (to_point_list + trimesh.voxel.ops.multibox + Trimesh's vertex
 // merge + export; numpy + PIL + pyexr for the depth map), called by SceneNetTrainer.visualize_intermediates
@@ -36,11 +36,7 @@
 // numpy 2 applies to a float32 array).
 #include "common.h"
 #include "reduce.h"
-#include <zlib.h>
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
-#include <vector>
 
 using namespace svr;
 
@@ -219,23 +215,6 @@ __global__ __launch_bounds__(kBlock) void depth_planes_kernel(const float *__res
   plane_u8[i] = (uint8_t)((int32_t)r & 0xff);
 }
 
-void put_be32(unsigned char *p, uint32_t v) {
-  p[0] = (unsigned char)(v >> 24);
-  p[1] = (unsigned char)(v >> 16);
-  p[2] = (unsigned char)(v >> 8);
-  p[3] = (unsigned char)v;
-}
-
-bool write_chunk(FILE *fp, const char *type, const unsigned char *data, uint32_t len) {
-  unsigned char head[8], tail[4];
-  put_be32(head, len);
-  memcpy(head + 4, type, 4);
-  uLong crc = crc32(0L, head + 4, 4);
-  if (len) crc = crc32(crc, data, len);
-  put_be32(tail, (uint32_t)crc);
-  return fwrite(head, 1, 8, fp) == 8 && (len == 0 || fwrite(data, 1, len, fp) == len) && fwrite(tail, 1, 4, fp) == 4;
-}
-
 }  // namespace
 
 extern "C" int64_t svr_voxel_mesh_workspace_bytes(int32_t X, int32_t Y, int32_t Z) {
@@ -305,49 +284,4 @@ extern "C" int svr_depth_planes(const float *map, int32_t H, int32_t W, int32_t 
   hipLaunchKernelGGL(depth_planes_kernel, dim3((unsigned)cdiv((int64_t)H * W, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, map, H, W,
                      flip ? 1 : 0, stats, plane_f32, plane_u8);
   return launch_status("depth_planes");
-}
-
-extern "C" int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W) {
-  SVR_CHECK(path && data, SVR_E_BADARG, "write_png_gray8: null pointer");
-  SVR_CHECK(H > 0 && W > 0 && ((int64_t)W + 1) * H < (1LL << 30), SVR_E_BADSHAPE, "write_png_gray8: image %d x %d", H, W);
-  // scanlines, each behind its filter-type byte 0 (None)
-  std::vector<unsigned char> raw((size_t)(W + 1) * H);
-  for (int r = 0; r < H; ++r) {
-    raw[(size_t)r * (W + 1)] = 0;
-    memcpy(&raw[(size_t)r * (W + 1) + 1], data + (size_t)r * W, (size_t)W);
-  }
-  uLongf zlen = compressBound((uLong)raw.size());
-  std::vector<unsigned char> z(zlen);
-  SVR_CHECK(compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) == Z_OK, SVR_E_IO, "write_png_gray8: deflate failed");
-  FILE *fp = fopen(path, "wb");
-  SVR_CHECK(fp, SVR_E_IO, "write_png_gray8: cannot open %s", path);
-  static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-  unsigned char ihdr[13];
-  put_be32(ihdr, (uint32_t)W);
-  put_be32(ihdr + 4, (uint32_t)H);
-  ihdr[8] = 8;   // bit depth
-  ihdr[9] = 0;   // colour type: grayscale
-  ihdr[10] = 0;  // compression: deflate
-  ihdr[11] = 0;  // filter method 0
-  ihdr[12] = 0;  // no interlace
-  bool ok = fwrite(sig, 1, 8, fp) == 8 && write_chunk(fp, "IHDR", ihdr, 13) && write_chunk(fp, "IDAT", z.data(), (uint32_t)zlen) &&
-            write_chunk(fp, "IEND", nullptr, 0);
-  ok = (fclose(fp) == 0) && ok;
-  SVR_CHECK(ok, SVR_E_IO, "write_png_gray8: write to %s failed", path);
-  return SVR_OK;
-}
-
-extern "C" int svr_write_obj_points(const char *path, const float *pts, int64_t n) {
-  SVR_CHECK(path && n >= 0 && (pts || n == 0), SVR_E_BADARG, "write_obj_points: bad argument");
-  FILE *fp = fopen(path, "wb");
-  SVR_CHECK(fp, SVR_E_IO, "write_obj_points: cannot open %s", path);
-  bool ok = true;
-  for (int64_t i = 0; i < n && ok; ++i) {
-    // + 0.5 in float32, widened for %f: the reference's '%f' % (x + 0.5) on a float32 coordinate
-    const float x = pts[i * 3] + 0.5f, y = pts[i * 3 + 1] + 0.5f, z = pts[i * 3 + 2] + 0.5f;
-    ok = fprintf(fp, "v %f %f %f %f %f %f\n", (double)x, (double)y, (double)z, 1.0, 1.0, 1.0) > 0;
-  }
-  ok = (fclose(fp) == 0) && ok;
-  SVR_CHECK(ok, SVR_E_IO, "write_obj_points: write to %s failed", path);
-  return SVR_OK;
 }

@@ -1,5 +1,6 @@
 """Native readers for the sample wire formats: thin numpy-level wrappers over the C ABI's host
-functions (svr_df_*, svr_npz_member_*, svr_exr_*: C++ + zlib inside libsvr_hip.so; no GPU involved) and the device-side helpers
+functions (svr_df_*, svr_npz_member_*, svr_exr_*: plain C++ + zlib, csrc/io_df.cpp / io_npz.cpp / io_exr.cpp, linked into
+libsvr_hip.so; no GPU involved) and the device-side helpers of csrc/sample_io.hip
 (transpose / cast / row subset).  `out=` lets the caller pass a pinned buffer so the H2D copy can be asynchronous."""
 import ctypes as C
 import os

@@ -14,7 +14,7 @@ written by the library's C++ host code.  ``visualize_sdf(sdf, output_path, level
 ``export_ply(vertices, faces, colors, path)``: the same mesh with one uint8 RGB colour per vertex, as a binary PLY.
 
 The other functions of the reference's util/visualize.py (:10-20,28-49), which the scene trainer's validation / test
-steps call (kernels and host writers in csrc/voxel_mesh.hip):
+steps call (kernels in csrc/voxel_mesh.hip, host writers in csrc/io_png.cpp and io_mesh.cpp):
 
 ``voxel_mesh(grid, threshold=0.5) -> (vertices (V,3) float32, faces (F,3) int32)``: the boundary surface of the union of
 unit cubes centred on the occupied indices of an (X, Y, Z) grid, same input convention as `marching_cubes`.  The

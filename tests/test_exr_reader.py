@@ -1,15 +1,15 @@
-"""CPU: the library's OpenEXR subset reader / writer (csrc/exr_io.cpp through data_processing.sample_io) against the real
+"""CPU: the library's OpenEXR subset reader / writer (csrc/io_exr.cpp through data_processing.sample_io) against the real
 distance map of the reference's sample and against a numpy + zlib writer / reader of the tests' own (tests/_exr.py)."""
 import os
-import struct
 
 import numpy as np
 import pytest
 
+from tests import _damage as D
 from tests import _exr as X
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-W, H = 37, 23                      # 37 x 23 pixels: under ZIP one block of 16 scanlines and a last block of 7
+W, H = D.W, D.H                    # 37 x 23 pixels: under ZIP one block of 16 scanlines and a last block of 7
 
 
 @pytest.fixture(scope="module")
@@ -101,9 +101,9 @@ def test_blocks_that_deflate_did_not_shrink_are_read_raw(io, tmp_path):
 
 
 def _smooth_file(tmp_path, name="r.exr", **kw):
-    a = np.add.outer(np.arange(H), np.arange(W)).astype(np.float32)
     path = tmp_path / name
-    return path, X.write_exr(path, {"R": a, "G": a}, **kw), a
+    made, a = D.smooth_exr(path, **kw)
+    return path, made, a
 
 
 def test_refusals_name_the_reason(io, tmp_path):
@@ -135,62 +135,23 @@ def test_refusals_name_the_reason(io, tmp_path):
 
 
 def test_damaged_files_are_errors_not_wild_reads(io, tmp_path):
+    """The named damages of tests/_damage.py (a cut offset table, attribute list, block payload and block header; table
+    entries past the end, wrapping, and naming a block twice; blocks that inflate to the wrong size or not at all)."""
     path, made, a = _smooth_file(tmp_path, "whole.exr", compression=X.ZIP)
     whole = path.read_bytes()
     assert np.array_equal(io.exr_read(path, "R"), a)
-    n = len(made["offsets"])
-    assert n == 2
-
-    cut = tmp_path / "cut_table.exr"                      # ends in the middle of the second offset
-    cut.write_bytes(whole[:made["table"] + 8 + 3])
-    with pytest.raises(RuntimeError, match="truncated offset table"):
-        io.exr_read(cut, "R")
-    with pytest.raises(RuntimeError, match="truncated offset table"):
-        io.exr_info(cut)
-
-    cut = tmp_path / "cut_header.exr"                     # ends inside the attribute list
-    cut.write_bytes(whole[:40])
-    with pytest.raises(RuntimeError, match="truncated header"):
-        io.exr_info(cut)
-
-    cut = tmp_path / "cut_block.exr"                      # ends in the middle of the last block's payload
-    last = max(made["offsets"])
-    size = struct.unpack("<i", whole[last + 4:last + 8])[0]
-    cut.write_bytes(whole[:last + 8 + size // 2])
-    with pytest.raises(RuntimeError, match="is truncated"):
-        io.exr_read(cut, "R")
-    cut.write_bytes(whole[:last + 5])                     # ... and in the middle of its 8-byte block header
-    with pytest.raises(RuntimeError, match="beyond the file"):
-        io.exr_read(cut, "R")
-
-    far = tmp_path / "far_offset.exr"                     # second table entry points past the end
-    t = made["table"] + 8
-    far.write_bytes(whole[:t] + struct.pack("<Q", len(whole) + 1000) + whole[t + 8:])
-    with pytest.raises(RuntimeError, match="beyond the file"):
-        io.exr_read(far, "R")
-    far.write_bytes(whole[:t] + struct.pack("<Q", (1 << 64) - 4) + whole[t + 8:])      # ... and one that would wrap a sum
-    with pytest.raises(RuntimeError, match="beyond the file"):
-        io.exr_read(far, "R")
-
-    twice = tmp_path / "twice.exr"                        # two table entries name the same block
-    twice.write_bytes(whole[:t] + struct.pack("<Q", made["offsets"][0]) + whole[t + 8:])
-    with pytest.raises(RuntimeError, match="appears twice"):
-        io.exr_read(twice, "R")
-
-    # a block whose deflate stream is sound but inflates to the wrong size (4 bytes short, then 4 bytes long)
-    assert last == made["offsets"][-1] and last + 8 + size == len(whole)       # the last block ends the file
-    nl = H - 16
-    raw = b"".join(a[16 + l].tobytes() * 2 for l in range(nl))
-    assert X._unpack(whole[last + 8:], len(raw)) == raw
-    for wrong in (raw[:-4], raw + b"\0\0\0\0"):
-        packed = X._pack(wrong)
-        bad = tmp_path / "bad_size.exr"
-        bad.write_bytes(whole[:last] + struct.pack("<ii", 16, len(packed)) + packed)
-        with pytest.raises(RuntimeError, match="wrong inflated size"):
+    damages = D.exr_damages(whole, made, a)
+    assert [d[2] for d in damages] == ["truncated offset table", "truncated header", "is truncated", "beyond the file", "beyond the file",
+                                       "beyond the file", "appears twice", "wrong inflated size", "wrong inflated size",
+                                       "corrupt deflate stream"]
+    for name, data, message, info_too in damages:
+        bad = tmp_path / (name + ".exr")
+        bad.write_bytes(data)
+        with pytest.raises(RuntimeError, match=message):
             io.exr_read(bad, "R")
-    bad.write_bytes(whole[:last + 8] + bytes(size))        # zeros are no deflate stream
-    with pytest.raises(RuntimeError, match="corrupt deflate stream"):
-        io.exr_read(bad, "R")
+        if info_too:
+            with pytest.raises(RuntimeError, match=message):
+                io.exr_info(bad)
     assert np.array_equal(io.exr_read(path, "R"), a)       # the process is alive and well
 
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import dataset_oracle as DO
+from tests import _damage as D
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -99,34 +100,17 @@ def test_malformed_npz_returns_an_error_instead_of_crashing(tmp_path):
     raw = good.read_bytes()
     assert np.array_equal(io.npz_load(good, "points"), np.load(good)["points"])
     bad = tmp_path / "bad.npz"
-    for cut in (0, 10, 30, len(raw) // 3, len(raw) // 2, len(raw) - 40, len(raw) - 22, len(raw) - 1):
-        bad.write_bytes(raw[:cut])
+    damages = D.npz_damages(raw)
+    assert [n for n, _ in damages] == [f"cut_{c}" for c in D.npz_cuts(raw)] + ["eocd_12_7ffffff0", "eocd_16_7ffffff0", "eocd_12_fffffffe",
+                                                                               "name_length"]
+    for _, data in damages:
+        bad.write_bytes(data)
         with pytest.raises(RuntimeError):
             io.npz_load(bad, "points")
-    eocd = raw.rfind(b"PK\x05\x06")
-    assert eocd > 0
-    for off, val in ((12, 0x7FFFFFF0), (16, 0x7FFFFFF0), (12, 0xFFFFFFFE)):      # cd_size / cd_offset far past the file
-        b = bytearray(raw)
-        b[eocd + off: eocd + off + 4] = int(val).to_bytes(4, "little")
-        bad.write_bytes(bytes(b))
-        with pytest.raises(RuntimeError):
-            io.npz_load(bad, "points")
-    cd = raw.find(b"PK\x01\x02")
-    b = bytearray(raw)
-    b[cd + 28: cd + 30] = (0xFFFF).to_bytes(2, "little")                          # file-name length past the directory
-    bad.write_bytes(bytes(b))
-    with pytest.raises(RuntimeError):
-        io.npz_load(bad, "points")
     # stored member with a damaged .npy header: nothing but spaces behind 'fortran_order':
     plain = tmp_path / "plain.npz"
     np.savez(plain, a=np.arange(6.0).reshape(2, 3))
-    r = plain.read_bytes()
-    k = r.find(b"'fortran_order': False")
-    assert k > 0
-    hdr_end = r.find(b"\n", k)
-    b = bytearray(r)
-    b[k + len(b"'fortran_order':"): hdr_end] = b" " * (hdr_end - k - len(b"'fortran_order':"))
-    bad.write_bytes(bytes(b))
+    bad.write_bytes(D.npy_header_without_fortran_value(plain.read_bytes()))
     with pytest.raises(RuntimeError):
         io.npz_load(bad, "a")
     assert np.array_equal(io.npz_load(plain, "a"), np.arange(6.0).reshape(2, 3))  # the library is still usable afterwards
