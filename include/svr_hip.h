@@ -1007,6 +1007,58 @@ int svr_vertex_color_spread(const int32_t *faces, int64_t F, int64_t V, uint8_t 
                             int64_t max_passes, int32_t check_every, int64_t *passes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Connected components of a mesh, their statistics, and the filter that keeps some of them (no reference op: the reference
+ * writes raw marching-cubes output, floaters included; util/mesh_clean.py drives this, tests/mesh_components_oracle.py restates
+ * it in numpy).  Errors, ownership and streams as for svr_mc_*.  No float operation takes part: every
+ * output is the same bits on every run, whichever way the atomics arrive.
+ *   verts: (V, 3) float32, faces: (F, 3) int32, on the device, 0 <= V, F < 2^31 (else SVR_E_BADSHAPE).
+ *   The rule:
+ *     1. a face is VALID iff its three indices lie in [0, V).  An invalid face joins nothing; its face label is -1.  A face
+ *        that repeats an index ((a, a, b), (a, a, a)) is valid and joins what it names; duplicate faces change nothing.
+ *     2. two vertices are in one COMPONENT iff a chain of valid faces connects them; a vertex of no valid face is a
+ *        component of its own, with 0 faces.
+ *     3. a component's ROOT is its smallest vertex index; components are numbered 0 .. C-1 in ascending order of root.
+ *        vertex_label[i] = the number of i's component; face_label[f] = vertex_label[first index of f], -1 when f is invalid.
+ *     4. per component, int32: root; vertex_count; face_count = its valid faces; marked_count = its vertices with
+ *        mark[i] != 0 (mark: (V) uint8, NULL = all 0).
+ *     5. per component, float32 x 3: bbox_min = fmin, bbox_max = fmax over its vertices' coordinates, per axis: a NaN
+ *        coordinate is skipped, +-inf take part, an axis without a non-NaN value holds +inf / -inf.  Computed as the unsigned
+ *        minimum / maximum of key(bits) = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000), whose order is the floats' (so of
+ *        -0.0 and +0.0 the minimum is -0.0 and the maximum +0.0: compare the box by value), and decoded.
+ *     6. FILTER, given keep[c] (uint8, nonzero = keep) per component: a face is kept iff it is valid and keep[its label];
+ *        a vertex is kept iff keep[its label] and it lies in at least one valid face.  Kept vertices and kept faces keep
+ *        their relative order; out_faces holds the new indices; vertex_index[j] = the old index of kept vertex j, so any
+ *        per-vertex attribute follows as attr[vertex_index]; out_verts[j] = the three words of verts[vertex_index[j]], copied.
+ *     7. SELECTION is the host's, over the C rows read back once (util/mesh_clean.py select_components; no entry point
+ *        here): a component is kept iff face_count >= max(1, min_faces) and extent >= min_extent and, if require_mark,
+ *        marked_count >= 1; with keep_largest only the one with the most faces among those, the lowest label on a tie.
+ *        extent = sqrt(sum over the axes of (max - min)^2) in float64 from the float32 box; an axis with max <= min (one
+ *        value, or none: +inf / -inf) adds 0.  Keeping nothing is an empty mesh, not an error.
+ *        Face area is deliberately no statistic: a float sum per component would depend on the order of arrival.
+ *   ws: svr_mesh_components_workspace_bytes(V, F) device bytes (negative = SVR_E_BADSHAPE); one buffer serves the three
+ *   stages in turn, needs no zeroing, and must be the same, untouched, between svr_mesh_filter_count and svr_mesh_filter_emit.
+ *   svr_mesh_components_label: vertex_label (V), face_label (F) int32; *count (DEVICE int64) = C.  V == 0: C = 0 and every
+ *     face label is -1; F == 0: C = V, vertex_label[i] = i.  Lock-free union-find, then one scan: no host synchronisation.
+ *   svr_mesh_components_stats: C = what the label call counted; the six outputs hold C rows.  C == 0 is a no-op.  A label
+ *     outside [0, C) adds nothing.  uniform_path: nonzero lets a wave whose vertices (faces) share one label fold its values
+ *     before it issues atomics; 0 issues them per lane.  The outputs are the same bits either way.
+ *   svr_mesh_filter_count: totals (DEVICE int64 x 2) = kept vertices, kept faces; V == 0 or F == 0: both 0.
+ *   svr_mesh_filter_emit: out_verts (V', 3), out_faces (F', 3), vertex_index (V') as the totals size them; call it only
+ *     when they are not 0.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_mesh_components_workspace_bytes(int64_t V, int64_t F);
+int svr_mesh_components_label(const int32_t *faces, int64_t F, int64_t V, void *ws, int64_t ws_bytes, int32_t *vertex_label,
+                              int32_t *face_label, int64_t *count, void *stream);
+int svr_mesh_components_stats(const float *verts, int64_t V, const int32_t *vertex_label, const int32_t *face_label, int64_t F,
+                              const uint8_t *mark, int64_t C, void *ws, int64_t ws_bytes, int32_t *root, int32_t *vertex_count,
+                              int32_t *face_count, int32_t *marked_count, float *bbox_min, float *bbox_max, int32_t uniform_path,
+                              void *stream);
+int svr_mesh_filter_count(const int32_t *faces, int64_t F, int64_t V, const int32_t *vertex_label, const uint8_t *keep, int64_t C,
+                          void *ws, int64_t ws_bytes, int64_t *totals, void *stream);
+int svr_mesh_filter_emit(const float *verts, int64_t V, const int32_t *faces, int64_t F, void *ws, int64_t ws_bytes, float *out_verts,
+                         int32_t *out_faces, int32_t *vertex_index, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * The files are read on the host (svr_df_* / svr_npz_*: File formats, below).

@@ -36,6 +36,7 @@ SOURCES = {
     "mesh_df.hip": ["-ffp-contract=off"],
     "raycast.hip": ["-ffp-contract=off"],
     "vertex_color.hip": ["-ffp-contract=off"],
+    "mesh_components.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "io_npz.cpp": [],
     "io_df.cpp": [],

@@ -31,8 +31,16 @@ uint8 and `color_state` (V,) uint8 (util/mesh_color.py).  
 ``<prefix>_predicted.ply`` (key "predicted_ply"): the vertices in `space` with those colours; without `color` nothing changes.
 
 ``python -m svr_amd.reconstruct --checkpoint C (--rgb a.png [b.png ...] | --distance d.exr) --out DIR [--inf_res n]
-[--block s] [--space grid|normalized|camera] [--flip] [--color [--color_bias metres]]`` prints one line per view: the written
-paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour state."""
+[--block s] [--space grid|normalized|camera] [--flip] [--color [--color_bias metres]] [--keep_largest]
+[--min_component_faces N] [--min_component_extent CELLS] [--drop_unseen]`` prints one line per view: the written
+paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour state.
+
+``clean(keep_largest=False, min_faces=0, min_extent=0.0, drop_unseen=False)`` drops connected components of the predicted
+mesh, the floaters an occupancy network leaves beside the surface (util/mesh_clean.py), and keeps
+`components` and `kept`.  Nothing calls it by default.  On the command line the size criteria (``--keep_largest``,
+``--min_component_faces``, ``--min_component_extent``) run first; ``--drop_unseen`` (needs ``--color``) then colours the mesh
+and drops the components the camera sees no vertex of; ``--color`` finally colours the mesh that is written.  With any of
+the four the line ends in ``components=C kept=K``: the components of the raw mesh and how many of them were written."""
 import argparse
 import os
 from pathlib import Path
@@ -63,6 +71,7 @@ class Reconstruction:
         self.image = image                              # (Hi, Wi, 3) uint8 on the device: what the network saw; None: a depth-only result
         self.pixel_map = IDENTITY_MAP if pixel_map is None else tuple(pixel_map)      # depth-map pixel -> image position
         self.colors = self.color_state = None           # colorize()'s results
+        self.components = self.kept = None              # clean()'s: the statistics before the filter, the flag per component
 
     def _camera_consts(self):
         K = self._intrinsic if self._intrinsic is not None else get_intrinsic()
@@ -125,6 +134,30 @@ class Reconstruction:
         self.colors, self.color_state = vertex_colors(v, self.faces, img, depth, self._camera_consts(), pixel_map=pm, bias=bias,
                                                       spread=spread, fill=fill, max_passes=max_passes)
         return self.colors, self.color_state
+
+    def clean(self, keep_largest=False, min_faces=0, min_extent=0.0, drop_unseen=False):
+        """Drop connected components of the predicted mesh (util.mesh_clean): the closed blobs an
+        occupancy network leaves in free space.  A component stays iff it has at least max(1, `min_faces`) faces, its bounding
+        box's diagonal is at least `min_extent` grid cells (multiplied by inf_res here: the vertices are lattice indices) and,
+        with `drop_unseen`, the camera sees at least one of its vertices (``color_state == 1``; runs ``colorize()`` first when
+        no state is stored, so a depth-only result without colours raises "holds no image"); with `keep_largest` only the one
+        with the most faces among those.  Replaces `vertices` and `faces`, stores `components` (the statistics BEFORE the
+        filter) and `kept` (the flag per component), and returns self; keeping nothing leaves an empty mesh.
+        `colors` and `color_state`, when stored, are carried along by index: they stay those of the UNFILTERED mesh's render,
+        in which a dropped component may have hidden what is now visible; a second ``colorize()`` recomputes them."""
+        from .util.mesh_clean import clean_mesh
+        mark = None
+        if drop_unseen:
+            if self.color_state is None:
+                self.colorize()
+            mark = (self.color_state == 1).to(torch.uint8)
+        vertices, faces, index, self.components, self.kept = clean_mesh(
+            self.vertices, self.faces, mark, keep_largest=keep_largest, min_faces=min_faces,
+            min_extent=float(min_extent) * self._inf_res, require_mark=bool(drop_unseen))
+        self.vertices, self.faces = vertices, faces
+        if self.colors is not None:
+            self.colors, self.color_state = self.colors[index.long()], self.color_state[index.long()]
+        return self
 
     def save(self, prefix, space="grid", color=False):
         vertices = self.vertices_in(space)
@@ -268,9 +301,18 @@ def main(argv=None):
     parser.add_argument("--flip", action="store_true", help="mirror the images left-right first")
     parser.add_argument("--color", action="store_true", help="also write <name>_predicted.ply with vertex colours from the image")
     parser.add_argument("--color_bias", type=float, default=None, help="visibility bias in metres (default: one grid cell)")
+    parser.add_argument("--keep_largest", action="store_true", help="keep only the connected component with the most faces")
+    parser.add_argument("--min_component_faces", type=int, default=None, metavar="N", help="drop components with fewer than N faces")
+    parser.add_argument("--min_component_extent", type=float, default=None, metavar="CELLS",
+                        help="drop components whose bounding-box diagonal is shorter than CELLS grid cells")
+    parser.add_argument("--drop_unseen", action="store_true", help="drop components the camera sees no vertex of (needs --color)")
     args = parser.parse_args(argv)
     if args.color and args.distance:
         parser.error("--color needs --rgb: a distance map carries no colours")
+    if args.drop_unseen and not args.color:
+        parser.error("--drop_unseen needs --color: what the camera sees is decided while colouring")
+    by_size = args.keep_largest or args.min_component_faces is not None or args.min_component_extent is not None
+    cleaning = by_size or args.drop_unseen
     rec =Reconstructor.from_checkpoint(args.checkpoint, inf_res=args.inf_res, skip_unet=True if args.distance else None,
                                         block=args.block)
     if args.distance:
@@ -278,13 +320,24 @@ def main(argv=None):
     else:
         names, views = [Path(p).stem for p in args.rgb], rec.reconstruct(list(args.rgb), flip=args.flip)
     for name, view in zip(names, views):
-        counts = ""
-        if args.color:
+        counts = parts = ""
+        if cleaning:
+            total = None                                  # the components of the raw mesh
+            if by_size:                                   # the size criteria first ...
+                view.clean(keep_largest=args.keep_largest, min_faces=args.min_component_faces or 0,
+                           min_extent=args.min_component_extent or 0.0)
+                total = view.components.count
+            if args.drop_unseen:                          # ... then what the camera sees of the rest
+                view.colorize(bias=args.color_bias)
+                view.clean(drop_unseen=True)
+                total = view.components.count if total is None else total
+            parts = f" components={total} kept={int(view.kept.sum())}"
+        if args.color:                                    # on the mesh that is written
             _, state = view.colorize(bias=args.color_bias)
             n = torch.bincount(state.long(), minlength=3).tolist()
             counts = f" seen={n[1]} spread={n[2]} unreached={n[0]}"
         paths = view.save(Path(args.out) / name, space=args.space, color=args.color)
-        print(" ".join(paths.values()), f"vertices={view.vertices.shape[0]} faces={view.faces.shape[0]}" + counts)
+        print(" ".join(paths.values()), f"vertices={view.vertices.shape[0]} faces={view.faces.shape[0]}" + counts + parts)
     return 0
 
 
