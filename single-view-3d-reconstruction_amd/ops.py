@@ -270,6 +270,7 @@ def gather_project_bwd(points, dh, dims, items, displacement, align_corners=Fals
     # out: a ZEROED (B, D*H*W, 7, 256) buffer of the caller (the training step zero-fills it on the side stream during the forward)
     dP = out if out is not None else torch.zeros(B, dims[0] * dims[1] * dims[2], 7, 256, device=points.device, dtype=torch.float32)
     assert tuple(dP.shape) == (B, dims[0] * dims[1] * dims[2], 7, 256) and dP.is_contiguous()
+    amax_forget(out)
     check(_lib.lib().svr_gather_project_bwd(_p(points), _rp(dh), dh.stride(0), B, N, dims[0], dims[1], dims[2],
                                             int(align_corners), displacement, _p(items), _p(dP), _stream()), "gather_project_bwd")
     return dP
@@ -325,6 +326,7 @@ def gather_fwd(vols, points, layout, displacement, align_corners, out=None, orde
     d = make_gather_desc(vols, None, layout, B, N, displacement, align_corners, order, flags=flags | GATHER_FLAGS)
     if out is None:   # the kernel writes every column (padding columns as zeros): no memset of the 4 GB buffer
         out = torch.empty(B * N, layout.row_stride, device=points.device, dtype=torch.float32)
+    amax_forget(out)
     check(_lib.lib().svr_gather_trilinear_fwd(C.byref(d), _p(points), _p(out), _stream()), "gather_fwd")
     return out
 
@@ -393,6 +395,7 @@ def gather_fc0_run(prep, points, bias, relu=True, rows_out=None):
             if tuple(rows_out.shape) != (B * N, prep.stride) or not rows_out.is_contiguous():
                 raise RuntimeError(f"gather_fc0: rows_out must be contiguous ({B * N}, {prep.stride})")
             _f32(rows_out)
+            amax_forget(rows_out)
             rows = rows_out
         else:
             rows = torch.empty(B * N, prep.stride, device=points.device, dtype=torch.float32)
@@ -429,6 +432,8 @@ def gather_bwd(vols, gvols, points, gfeat, layout, displacement, align_corners, 
     d = make_gather_desc(vols, gvols, layout, B, N, displacement, align_corners, order, level_orders,
                          flags=flags | GATHER_FLAGS, level_plans=level_plans, skip_levels=skip_levels)
     gp = torch.empty_like(points) if want_gpoints else None
+    for g in gvols or ():      # accumulated into / overwritten through their raw pointers
+        amax_forget(g)
     check(_lib.lib().svr_gather_trilinear_bwd(C.byref(d), _p(points), _p(gfeat), _p(gp), _stream()), "gather_bwd")
     return gp
 
@@ -752,6 +757,7 @@ def linear_fwd(x, w, bias, relu=True, out=None, mode=None):
     if out is None:
         out = torch.empty(M, N, device=x.device, dtype=torch.float32)
     _f32(out)
+    amax_forget(out)
     assert out.shape == (M, N) and out.stride(1) == 1      # a column slice of a wider buffer is fine: its row stride is passed
     epi = EPI_NONE if bias is None else (EPI_BIAS_RELU if relu else EPI_BIAS)
     op = _linear_fwd_op(mode, K)
@@ -832,12 +838,58 @@ def amax_slot(device):
     return _amax_slots.take(device)
 
 
-def amax_of(t):
+def _amax_stamp(t):
+    """What a remembered |max| word is valid for: (version counter, storage address) of the tensor when the word was taken."""
+    try:
+        return (t._version, t.data_ptr())
+    except RuntimeError:      # an inference tensor keeps no version counter: nothing to check a word against, never reused
+        return None
+
+
+def amax_remember(t, a):
+    """Leave the word `a` (max |t| as t stands NOW) on the tensor object, stamped with t's version counter and address."""
+    t._svr_amax = a
+    t._svr_amax_stamp = _amax_stamp(t)
+
+
+def amax_forget(t):
+    """Drop the |max| word remembered on `t` (None: nothing to do).  For a caller that has written into t behind torch's
+    back -- through `t.data`, or from a kernel of its own with the raw pointer -- and for every op here that does so."""
+    if t is not None and getattr(t, "_svr_amax", None) is not None:
+        t.__dict__.pop("_svr_amax", None)
+        t.__dict__.pop("_svr_amax_stamp", None)
+
+
+def amax_cached(t, force=False):
+    """The word remembered on `t` if it may stand for t's present contents, else None.  Host only: reads attributes of the
+    tensor object, never the device (tests/test_amax_cache_cpu.py runs it on CPU tensors).  A hit needs all of:
+      - a word and its stamp on this tensor object (a new view or slice of the same memory is another object: miss);
+      - the stamp equal to (t._version, t.data_ptr()) now: every in-place op torch knows of -- copy_, mul_, add_ (autograd's
+        in-place accumulation of a second gradient contribution), t[...] = ..., _foreach_*, a write through a view of t (views
+        share the counter), set_ -- moves the counter, and `t.data = other` moves the address;
+      - the word not older than the ring allows (_AmaxSlots.fresh);
+      - not `force`."""
+    a = getattr(t, "_svr_amax", None)
+    if a is None or force:
+        return None
+    stamp = getattr(t, "_svr_amax_stamp", None)
+    if stamp is None or stamp != _amax_stamp(t) or not _AmaxSlots.fresh(a):
+        return None
+    return a
+
+
+def amax_of(t, force=False):
     """(1,) int32 tensor = bit pattern of max |t| on the device (the power-of-two scale of a gradient operand of the
     "f16x3s" kernels).  Kernels that produce a gradient leave it on the tensor they return (attribute `_svr_amax`: no extra
-    pass); otherwise one pass over t on the current stream, remembered on the tensor object."""
-    a = getattr(t, "_svr_amax", None)
-    if a is not None and _AmaxSlots.fresh(a):
+    pass); otherwise one pass over t on the current stream, remembered on the tensor object -- the two products of one dy
+    share one pass.  The remembered word is reused only while amax_cached() holds: it is stamped with the tensor's version
+    counter and address, and recomputed after any in-place change torch has seen.
+    What the stamp CANNOT see: a write through `t.data` (a detached alias with a counter of its own) and a write by a kernel
+    outside this module that was handed the raw pointer.  After either, call amax_forget(t) or amax_of(t, force=True) before
+    the next op that consumes t; otherwise t is scaled by its earlier contents' |max| (overflow to inf / NaN when it grew
+    by more than ~4x, lost mantissa bits or zeros when it shrank)."""
+    a = amax_cached(t, force)
+    if a is not None:
         return a
     _f32(t)
     a = amax_slot(t.device)
@@ -850,7 +902,7 @@ def amax_of(t):
             raise RuntimeError("amax_of: tensor must have a multiple of 4 elements and be 16-byte aligned")
         M, N, ld = n // 4, 4, 4
     check(_lib.lib().svr_amax_f32(C.c_void_p(src.data_ptr()), ld, M, N, _p(a), _stream()), "amax_f32")
-    t._svr_amax = a
+    amax_remember(t, a)
     return a
 
 
@@ -863,6 +915,7 @@ def linear_bwd_data(dy, w, mask=None, out=None, mode=None):
         out = torch.empty(M, K, device=dy.device, dtype=torch.float32)
     epi = EPI_MASK if mask is not None else EPI_NONE
     op = _linear_bwd_data_op(mode, N, operand_layout(dy), operand_layout(out), operand_layout(mask))
+    amax_forget(out)      # (a caller's `out` is overwritten through its raw pointer; the f16x3s kernel leaves the new word)
     if op == "bwd_data_f16x3s":
         l = _lib.lib()
         ws = _lookup("lbh", w, mode, "f16x3s") if (w.stride(0) == K and w.stride(1) == 1) else None
@@ -876,7 +929,7 @@ def linear_bwd_data(dy, w, mask=None, out=None, mode=None):
                                           C.c_void_p(out.data_ptr()), out.stride(0), M, N, K, epi,
                                           _rp(mask), mask.stride(0) if mask is not None else 0, _p(amax_dy), _p(amax_dx), _p(ws), _stream()),
               "linear_bwd_data_f16x3")
-        out._svr_amax = amax_dx        # |max| of what was stored: the next layer's scale, no extra pass
+        amax_remember(out, amax_dx)    # |max| of what was stored: the next layer's scale, no extra pass
         return out
     if op == "bwd_data_bf16x3":
         l = _lib.lib()
@@ -943,7 +996,7 @@ def fc_out_bwd(h, w, dlogits, row_map=None):
     check(l.svr_fc_out_bwd(_p(h), h.stride(0), _p(w), _p(dlogits), _p(row_map), _p(dh), dh.stride(0), _p(dw), _p(db), M, K,
                            _p(amax), _p(ws), _stream()), "fc_out_bwd")
     if amax is not None:
-        dh._svr_amax = amax
+        amax_remember(dh, amax)
     return dh, dw, db
 
 
@@ -1085,7 +1138,7 @@ def conv3d_k3_bwd_data(dout, w, mask=None, mode=None):
         check(l.svr_conv3d_k3_bwd_data_f16x3(_p(dout), wptr, _p(din), B, D, H, W, Ci, Co,
                                              EPI_MASK if mask is not None else EPI_NONE, _p(mask), _p(amax_of(dout)), _p(amax_din),
                                              _p(ws), _stream()), "conv3d_bwd_data_f16x3")
-        din._svr_amax = amax_din
+        amax_remember(din, amax_din)
         return din
     if (mode or BACKWARD_CONV) == "f16x3s":
         mode = "f32"                   # (shapes the f16 kernel does not take: exact f32, never a narrower split)
@@ -1181,6 +1234,8 @@ def bn_forward(x, gamma, beta, running_mean, running_var, training, eps=1e-5, mo
                          f"torch.Size([{B}, {Cc}, {D}, {H}, {W}])")
     l = _lib.lib()
     dev = x.device
+    amax_forget(running_mean)      # (training: the running statistics are updated through their raw pointers)
+    amax_forget(running_var)
     ss = torch.empty(3 * Cc, device=dev, dtype=torch.float32)
     own_stats = training and stats is None
     mean = torch.empty(2 * Cc if own_stats else Cc, device=dev, dtype=torch.float32)
@@ -1229,7 +1284,7 @@ def bn_backward(x, dy, dpooled, argmax, mean, ss, relu_mask=True, training=True)
                              _p(dgamma), _p(dbeta), B, D, H, W, Cc, int(relu_mask) | (0 if training else 2), _p(amax), _stream()),
           "bn_bwd_apply")
     if amax is not None:
-        dx._svr_amax = amax         # |max| of dx: the scale of the convolution gradients' scaled f16 split, no extra pass
+        amax_remember(dx, amax)     # |max| of dx: the scale of the convolution gradients' scaled f16 split, no extra pass
     return dx, dgamma, dbeta
 
 
@@ -1255,6 +1310,8 @@ def stage1_fwd(x, w, bias, gamma, beta, running_mean, running_var, training, eps
         raise ValueError(f"Expected more than 1 value per channel when training, got input size torch.Size([{B}, {Co}, {D}, {H}, {W}])")
     l = _lib.lib()
     dev = x.device
+    amax_forget(running_mean)      # (training: the running statistics are updated through their raw pointers)
+    amax_forget(running_var)
     wp, _ = conv3d_pack_weight(w, want_bwd=False)
     y = torch.empty(B, D, H, W, Co, device=dev, dtype=torch.float32)
     pooled = argmax = None
@@ -1535,7 +1592,7 @@ def conv2d_fwd(src0, src1, k, stride, act, planes, bias, amax_x=None, want_amax=
     check(_lib.lib().svr_conv2d_fwd(C.byref(d), planes.planes_ptr(), planes.amax_ptr(), _p(bias), _p(y), planes.Cout, _p(amax_x),
                                     _p(amax_y), _p(ws), _stream()), "conv2d_fwd")
     if want_amax:
-        y._svr_amax = amax_y
+        amax_remember(y, amax_y)
     return y
 
 
@@ -1544,14 +1601,19 @@ def linear_bwd_data_splitk(dy, wt):
     split over workgroups and the partial tiles are summed in a fixed order (few output tiles, long reduction).  f16x3s
     arithmetic.  Measured on IF-Net's projected levels' voxel GEMMs (reduction 1 792, 128 outputs): 22 + 26 us against 96 at
     4 096 rows, 77 + 41 against 104 at 32 768 rows -- and no change of the step's median (the GEMMs sit in the shadow of the
-    projected scatter), so the step keeps linear_bwd_data; kept as an op for callers with that shape (tools/exp/dbg_splitk.py)."""
+    projected scatter), so the step keeps linear_bwd_data; kept as an op for callers with that shape (tools/exp/dbg_splitk.py).
+    K in 1..4 with K * N <= 8192 is refused (ValueError): that weight is the 2-D convolution's plain-FMA class, which has no k = 1 form."""
     _f32(dy, wt)
     M, N = dy.shape
     K = wt.shape[0]
     planes = Conv2dPlanes(wt.view(K, N, 1, 1), 1, want_bwd=False)
+    if planes.small:      # 1..4 outputs with K * N <= 8192 weights: the plain-FMA class, which has no k = 1 form and leaves no word
+        raise ValueError(f"linear_bwd_data_splitk: K = {K} output columns over a reduction of N = {N}: the split-reduction kernel "
+                         f"takes K >= 5, or K * N > 8192 (K <= 4 with K * N <= 8192 is the plain-FMA class of conv2d.hip, which has "
+                         f"no 1x1 form); use linear_bwd_data")
     y = conv2d_fwd(dy.view(1, 1, M, N), None, 1, 1, ACT_NONE, planes, None, amax_x=amax_of(dy), want_amax=True)
     out = y.view(M, K)
-    out._svr_amax = y._svr_amax
+    amax_remember(out, y._svr_amax)
     return out
 
 
