@@ -581,7 +581,8 @@ int svr_voxelize_splat_fwd(const float *pts, float *acc, int32_t *base, uint8_t 
 int svr_voxelize_splat_bwd(const float *pts, const float *gacc, float *gpts, int32_t B, int32_t N,
                            int32_t D0, int32_t D1, int32_t D2, void *stream);
 /* out = clamp(scale*in, 0, 1): scale 8 = the reference's x8 alias quirk (projection.py:75-80),
- * scale 1 = the final clamp of the blur (:116).  bwd: gin = scale*gout where 0 <= scale*in <= 1. */
+ * scale 1 = the final clamp of the blur (:116).  bwd: gin = scale*gout where 0 <= scale*in <= 1.
+ * NaN is loud, as in torch.clamp: fwd gives NaN for a NaN input (never a clean 0), bwd gives 0.  */
 int svr_scale_clamp01_fwd(const float *in, float *out, int64_t n, float scale, void *stream);
 int svr_scale_clamp01_bwd(const float *in, const float *gout, float *gin, int64_t n, float scale,
                           void *stream);

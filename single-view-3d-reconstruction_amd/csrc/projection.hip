@@ -120,9 +120,16 @@ __global__ void splat_bwd_kernel(const float *__restrict__ pts, const float *__r
   gpts[i * 3] = g0; gpts[i * 3 + 1] = g1; gpts[i * 3 + 2] = g2;
 }
 
+// clamp(scale * v, 0, 1) like torch.clamp: NaN stays NaN (fminf / fmaxf alone return the other operand, which turned a NaN
+// grid into a clean all-zero occupancy with zero gradients); every other value as fminf(fmaxf(., 0), 1)
+__device__ __forceinline__ float scale_clamp01(float v, float scale) {
+  const float s = v * scale;
+  return s != s ? s : fminf(fmaxf(s, 0.f), 1.f);
+}
+
 __global__ void scale_clamp_fwd_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t n, float scale) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = fminf(fmaxf(in[i] * scale, 0.f), 1.f);
+  if (i < n) out[i] = scale_clamp01(in[i], scale);
 }
 
 __global__ void scale_clamp_bwd_kernel(const float *__restrict__ in, const float *__restrict__ gout,
@@ -345,7 +352,7 @@ __global__ __launch_bounds__(256) void splat_pull_kernel(float *__restrict__ acc
     if (x0 + i < D2) {
       const float v = ((P[i][0] + P[i][1]) + (P[i][2] + P[i][3])) + ((P[i][4] + P[i][5]) + (P[i][6] + P[i][7]));
       acc[out + i] = v;
-      if (vox) vox[out + i] = fminf(fmaxf(v * 8.f, 0.f), 1.f);
+      if (vox) vox[out + i] = scale_clamp01(v, 8.f);
     }
 }
 

@@ -1,6 +1,7 @@
 """GPU parity of the projection HIP path (unproject / splat / blur) against the reference's own
 outputs (tests/golden/project_*.npz) and the CPU oracle.  Voxel indices and the validity mask are
-bit-exact; floating point within the written tolerances (f32 atomics reorder the splat sums)."""
+bit-exact; floating point within the written tolerances (f32 atomics reorder the splat sums).
+The per-kernel gates (every forward and backward kernel on its own against float64): tests/test_gpu_projection_kernels.py."""
 import numpy as np
 import pytest
 import torch
