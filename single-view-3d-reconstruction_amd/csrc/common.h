@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "error.h"  // set_error, SVR_CHECK, svr_hip.h
+#include "workspace.h"  // WsCursor: one layout function per multi-piece workspace
 
 namespace svr {
 inline int launch_status(const char *what) {
@@ -24,6 +25,12 @@ __device__ __forceinline__ int64_t xcd_logical(int64_t bid, int64_t grid) { retu
 template <class T = char>
 inline T *align256(const void *p) { return (T *)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 inline int64_t align256(int64_t bytes) { return (bytes + 255) / 256 * 256; }   // ... and the size of a piece of it
+// The weight-plane workspaces of the split GEMMs and convs (PREPARE fills them, RUN reads them).  bf16 split: `n` planes of
+// `elems` uint16 back to back, on a cursor with base alignment 16.  Scaled f16 split: the |max| word of W on a 256-byte line of
+// its own, then the two planes.
+inline uint16_t *planes_layout(WsCursor &c, int64_t elems, int n) { return c.take<uint16_t>(n * elems, 2); }
+struct ScaledPlanesWs { uint32_t *amax; uint16_t *planes; };
+inline ScaledPlanesWs scaled_planes_layout(WsCursor &c, int64_t elems) { return {c.take<uint32_t>(64), c.take<uint16_t>(2 * elems, 2)}; }
 
 // ---- functions shared between translation units, each declared once here ----
 // gemm.hip: out[n] = sum_m Y[m][n] (part: colsum_workspace_floats(M, N) floats), and the ordered f64 sum of partials it ends

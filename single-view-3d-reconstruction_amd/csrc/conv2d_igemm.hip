@@ -439,13 +439,16 @@ bool vec4_ok(const CvSrc &S) {
   return S.C0 % 4 == 0 && S.C1 % 4 == 0 && (((uintptr_t)S.p0 | (uintptr_t)S.p1) & 15) == 0;
 }
 
+// a layer's weight planes (hi, lo): the forward's, then the backward-data's
+struct IgPlanes { uint16_t *pf, *pb; };
+IgPlanes ig_planes_layout(WsCursor &c, int Cout, int C, int k) {
+  return {c.take<uint16_t>(2LL * Cout * k * k * pad16(C)), c.take<uint16_t>(2LL * C * k * k * pad16(Cout))};
+}
+
 }  // namespace
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------
-extern "C" int64_t svr_conv2d_planes_bytes(int32_t Cout, int32_t C, int32_t k) {
-  const int64_t fwd = 4LL * Cout * k * k * pad16(C), bwd = 4LL * C * k * k * pad16(Cout);
-  return align256(fwd) + align256(bwd) + 256;
-}
+extern "C" int64_t svr_conv2d_planes_bytes(int32_t Cout, int32_t C, int32_t k) { return ws_measure(ig_planes_layout, Cout, C, k); }
 
 extern "C" int svr_conv2d_prepare(const float *W, int32_t Cout, int32_t C, int32_t k, int32_t stride, int32_t want_bwd,
                                   uint32_t *amax, void *planes, void *stream) {
@@ -454,8 +457,8 @@ extern "C" int svr_conv2d_prepare(const float *W, int32_t Cout, int32_t C, int32
             "conv2d_prepare: k=%d stride=%d (k = 1: forward planes only)", k, stride);
   hipStream_t s = (hipStream_t)stream;
   const int64_t numel = (int64_t)Cout * C * k * k;
-  uint16_t *pf = align256<uint16_t>(planes);
-  uint16_t *pb = (uint16_t *)((char *)pf + align256(4LL * Cout * k * k * pad16(C)));
+  WsCursor c(planes);
+  const auto [pf, pb] = ig_planes_layout(c, Cout, C, k);
   if ((((uintptr_t)W) & 15) == 0) {
     (void)hipMemsetAsync(amax, 0, sizeof(uint32_t), s);
     hipLaunchKernelGGL(ig_amax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(numel, 4096), 256)), dim3(256), 0, s, W, numel, amax);
@@ -485,8 +488,8 @@ extern "C" int svr_conv2d_prepare_many(int32_t n, const float *const *W, const i
     SVR_CHECK(W[i] && planes[i] && Cout[i] > 0 && C[i] > 0, SVR_E_BADARG, "conv2d_prepare_many: layer %d", i);
     SVR_CHECK((k[i] == 4 && stride[i] == 2) || (k[i] == 3 && stride[i] == 1), SVR_E_UNSUPPORTED, "conv2d_prepare_many: layer %d k=%d stride=%d",
               i, k[i], stride[i]);
-    uint16_t *pf = align256<uint16_t>(planes[i]);
-    uint16_t *pb = (uint16_t *)((char *)pf + align256(4LL * Cout[i] * k[i] * k[i] * pad16(C[i])));
+    WsCursor c(planes[i]);
+    const auto [pf, pb] = ig_planes_layout(c, Cout[i], C[i], k[i]);
     T.it[i] = IgPrepItem{W[i], pf, want_bwd[i] ? pb : nullptr, Cout[i], C[i], k[i], stride[i]};
     const int64_t items = (int64_t)Cout[i] * k[i] * k[i] * pad16(C[i]) / 2 + (want_bwd[i] ? (int64_t)C[i] * k[i] * k[i] * pad16(Cout[i]) / 2 : 0);
     maxitems = std::max(maxitems, items);
@@ -536,7 +539,8 @@ extern "C" int svr_conv2d_fwd(const svr_conv2d_desc *d, const void *planes, cons
     SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_fwd: %d reduction splits need the workspace", splits);
     partial = align256<float>(workspace);
   }
-  const uint16_t *pf = align256<const uint16_t>(planes);
+  WsCursor c(planes);
+  const uint16_t *pf = ig_planes_layout(c, Cout, C, d->k).pf;
   hipStream_t s = (hipStream_t)stream;
   if (vec4_ok(G.S)) ig_launch<true>(G, 1, mtiles, splits, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
   else ig_launch<false>(G, 1, mtiles, splits, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
@@ -568,8 +572,8 @@ extern "C" int svr_conv2d_bwd_data(const svr_conv2d_desc *d, const void *planes,
     SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_bwd_data: %d reduction splits need the workspace", splits);
     partial = align256<float>(workspace);
   }
-  const uint16_t *pf = align256<const uint16_t>(planes);
-  const uint16_t *pb = (const uint16_t *)((const char *)pf + align256(4LL * Cout * d->k * d->k * pad16(C)));
+  WsCursor c(planes);
+  const uint16_t *pb = ig_planes_layout(c, Cout, C, d->k).pb;
   hipStream_t s = (hipStream_t)stream;
   if (vec4_ok(G.S)) ig_launch<true>(G, ncls, mtiles, splits, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);
   else ig_launch<false>(G, ncls, mtiles, splits, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);

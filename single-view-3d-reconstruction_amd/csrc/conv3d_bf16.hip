@@ -705,7 +705,7 @@ ConvVariant conv_variant(int op, int B, int D, int H, int Wd, int k, int cols) {
 
 }  // namespace
 
-extern "C" int64_t svr_conv3d_bwd_data_bf16x3_workspace(int32_t Ci, int32_t Co) { return 2LL * 27 * Ci * Co * (int64_t)sizeof(uint16_t) + 256; }
+extern "C" int64_t svr_conv3d_bwd_data_bf16x3_workspace(int32_t Ci, int32_t Co) { return ws_measure(planes_layout, (int64_t)27 * Ci * Co, 2); }
 
 // dIn(B,D,H,W,Ci) = epi( conv^T(dOut(B,D,H,W,Co), W(Co,Ci,3,3,3)) ), epilogue NONE or MASK (mask shaped like dIn).
 extern "C" int svr_conv3d_k3_bwd_data_bf16x3(const float *dout, const float *W, float *din, int32_t B, int32_t D, int32_t H,
@@ -715,8 +715,9 @@ extern "C" int svr_conv3d_k3_bwd_data_bf16x3(const float *dout, const float *W, 
   SVR_CHECK((dout || W) && (!dout || din) && workspace, SVR_E_BADARG, "conv3d_bwd_data_bf16x3: null pointer");
   SVR_CHECK(Co % 16 == 0 && Ci % 2 == 0 && Ci >= 2, SVR_E_UNSUPPORTED, "conv3d_bwd_data_bf16x3: need Co %% 16 == 0, Ci even (Ci=%d Co=%d)", Ci, Co);
   hipStream_t s = (hipStream_t)stream;
-  uint16_t *hi = (uint16_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   const int64_t ps = (int64_t)27 * Ci * Co;
+  WsCursor c(workspace, 16);
+  uint16_t *hi = planes_layout(c, ps, 2);
   // the transposed conv reads dOut (Co channels = its K) and writes Ci channels: planes [27][Ci][Co]
   if (W) hipLaunchKernelGGL((pack_planes_kernel<false, true>), dim3(cdiv(27 * Ci * (Co / 2), 256)), dim3(256), 0, s, W, (const uint32_t *)nullptr, hi, ps, Ci, Co);
   if (!dout) return launch_status("conv3d_bwd_data_bf16x3 (prepare)");
@@ -742,7 +743,7 @@ extern "C" int svr_conv3d_k3_bwd_data_bf16x3(const float *dout, const float *W, 
 }
 
 // ---- backward-data on the scaled f16 split ("f16x3s": f32 level at the bf16x3 cost; see svr_linear_bwd_data_f16x3) -------------
-extern "C" int64_t svr_conv3d_bwd_data_f16x3_workspace(int32_t Ci, int32_t Co) { return 2LL * 27 * Ci * Co * (int64_t)sizeof(uint16_t) + 512; }
+extern "C" int64_t svr_conv3d_bwd_data_f16x3_workspace(int32_t Ci, int32_t Co) { return ws_measure(scaled_planes_layout, (int64_t)27 * Ci * Co); }
 
 extern "C" int svr_conv3d_k3_bwd_data_f16x3(const float *dout, const float *W, float *din, int32_t B, int32_t D, int32_t H,
                                             int32_t Wd, int32_t Ci, int32_t Co, int epilogue, const float *mask,
@@ -751,9 +752,9 @@ extern "C" int svr_conv3d_k3_bwd_data_f16x3(const float *dout, const float *W, f
   SVR_CHECK((dout || W) && (!dout || din) && workspace, SVR_E_BADARG, "conv3d_bwd_data_f16x3: null pointer");
   SVR_CHECK(Co % 16 == 0 && Ci % 2 == 0 && Ci >= 2, SVR_E_UNSUPPORTED, "conv3d_bwd_data_f16x3: need Co %% 16 == 0, Ci even (Ci=%d Co=%d)", Ci, Co);
   hipStream_t s = (hipStream_t)stream;
-  uint32_t *amax = align256<uint32_t>(workspace);
-  uint16_t *hi = (uint16_t *)(amax + 64);
   const int64_t ps = (int64_t)27 * Ci * Co;
+  WsCursor c(workspace);
+  const auto [amax, hi] = scaled_planes_layout(c, ps);
   if (W) {
     w_amax_launch(W, ps, 1, ps, amax, s, (unsigned)cdiv(ps, 1024));
     hipLaunchKernelGGL((pack_planes_kernel<true, true>), dim3(cdiv(27 * Ci * (Co / 2), 256)), dim3(256), 0, s, W, (const uint32_t *)amax, hi, ps, Ci, Co);
@@ -780,7 +781,7 @@ extern "C" int svr_conv3d_k3_bwd_data_f16x3(const float *dout, const float *W, f
   return launch_status("conv3d_bwd_data_f16x3");
 }
 
-extern "C" int64_t svr_conv3d_fwd_bf16x6_workspace(int32_t Ci, int32_t Co) { return 3LL * 27 * Ci * Co * (int64_t)sizeof(uint16_t) + 256; }
+extern "C" int64_t svr_conv3d_fwd_bf16x6_workspace(int32_t Ci, int32_t Co) { return ws_measure(planes_layout, (int64_t)27 * Ci * Co, 3); }
 
 // out(B,D,H,W,Co) = epi( conv(in(B,D,H,W,Ci), W(Co,Ci,3,3,3)) ) at f32 accuracy; epilogue NONE / BIAS / BIAS_RELU.
 extern "C" int svr_conv3d_k3_fwd_bf16x6(const float *in, const float *W, const float *bias, float *out, int32_t B, int32_t D,
@@ -792,8 +793,9 @@ extern "C" int svr_conv3d_k3_fwd_bf16x6(const float *in, const float *W, const f
   SVR_CHECK(epilogue == SVR_EPI_NONE || ((epilogue == SVR_EPI_BIAS || epilogue == SVR_EPI_BIAS_RELU) && bias), SVR_E_BADARG,
             "conv3d_fwd_bf16x6: epilogue %d", epilogue);
   hipStream_t s = (hipStream_t)stream;
-  uint16_t *p0 = (uint16_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   const int64_t ps = (int64_t)27 * Ci * Co;
+  WsCursor c(workspace, 16);
+  uint16_t *p0 = planes_layout(c, ps, 3);
   hipLaunchKernelGGL((pack_planes_kernel<false, false>), dim3(cdiv(27 * Co * (Ci / 2), 256)), dim3(256), 0, s, W, (const uint32_t *)nullptr, p0, ps, Ci, Co);
   ConvShape sh{B, D, H, Wd, Ci, Co};
   const ConvVariant v = conv_variant(SVR_CONV_FWD_BF16X6, B, D, H, Wd, Ci, Co);
@@ -805,7 +807,7 @@ extern "C" int svr_conv3d_k3_fwd_bf16x6(const float *in, const float *W, const f
   return launch_status("conv3d_fwd_bf16x6");
 }
 
-extern "C" int64_t svr_conv3d_fwd_f16x3_workspace(int32_t Ci, int32_t Co) { return 2LL * 27 * Ci * Co * (int64_t)sizeof(uint16_t) + 512; }
+extern "C" int64_t svr_conv3d_fwd_f16x3_workspace(int32_t Ci, int32_t Co) { return ws_measure(scaled_planes_layout, (int64_t)27 * Ci * Co); }
 
 // out(B,D,H,W,Co) = epi( conv(in(B,D,H,W,Ci), W(Co,Ci,3,3,3)) ) with the 3-product f16 split: f32-level accuracy for
 // |in| < 65504 (see gemm_f16x3.hip); epilogue NONE / BIAS / BIAS_RELU.
@@ -846,9 +848,9 @@ int fwd_f16x3(const float *in, const float *W, const float *bias, float *out, in
   SVR_CHECK((in || W) && (!in || out) && workspace, SVR_E_BADARG, "conv3d_fwd_f16x3: null pointer");
   SVR_CHECK(Ci % 16 == 0 && Co >= 1, SVR_E_UNSUPPORTED, "conv3d_fwd_f16x3: need Ci %% 16 == 0 (Ci=%d Co=%d)", Ci, Co);
   hipStream_t s = (hipStream_t)stream;
-  uint32_t *amax = align256<uint32_t>(workspace);
-  uint16_t *p0 = (uint16_t *)(amax + 64);
   const int64_t ps = (int64_t)27 * Ci * Co;
+  WsCursor c(workspace);
+  const auto [amax, p0] = scaled_planes_layout(c, ps);
   if (W) {
     w_amax_launch(W, ps, 1, ps, amax, s, (unsigned)cdiv(ps, 1024));
     hipLaunchKernelGGL((pack_planes_kernel<true, false>), dim3(cdiv(27 * Co * (Ci / 2), 256)), dim3(256), 0, s, W, (const uint32_t *)amax, p0, ps, Ci, Co);

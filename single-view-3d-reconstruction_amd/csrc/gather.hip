@@ -1317,17 +1317,33 @@ extern "C" int svr_gather_corner_indices(const svr_gather_desc *d, int32_t level
   return svr::launch_status("corner_indices");
 }
 
+namespace {
+// The pull plan's workspace is a cells part (raw cell ends, at most 2^31 cells, and the scan's temp) followed by an items part;
+// each has its own exported size and callers add both.  Sort temp pieces are sized for 32-bit keys, the widest any plan sorts.
+struct PullCellsWs { int32_t *ends; char *scan_tmp; size_t scan_bytes; };
+PullCellsWs pull_cells_layout(svr::WsCursor &c, int64_t cells) {
+  const size_t scan_bytes = svr::scan_max_i32_temp_bytes(cells + 1);
+  return {c.take<int32_t>(cells + 1), c.take<char>((int64_t)scan_bytes), scan_bytes};
+}
+struct PullItemsWs { uint32_t *keys_in; int32_t *vals_in, *items; char *sort_tmp; };
+PullItemsWs pull_items_layout(svr::WsCursor &c, int64_t T) {
+  return {c.take<uint32_t>(T), c.take<int32_t>(T), c.take<int32_t>(T), c.take<char>((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32))};
+}
+// svr_gather_item_order / _xblock are handed a buffer of svr_gather_pull_plan_workspace bytes
+struct ItemOrderWs { uint32_t *keys_in; int32_t *vals_in; uint32_t *keys_out; char *sort_tmp; };
+ItemOrderWs item_order_layout(svr::WsCursor &c, int64_t T) {
+  return {c.take<uint32_t>(T), c.take<int32_t>(T), c.take<uint32_t>(T), c.take<char>((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32))};
+}
+}  // namespace
+
 extern "C" int64_t svr_gather_pull_plan_workspace(int32_t B, int32_t N) {
-  // items: 3 x uint32 arrays + radix temp; the raw cell ends (cells + 1 ints, at most 2^31 cells) are sized by
-  // svr_gather_pull_plan_workspace_cells below -- callers add both
   const int64_t T = (int64_t)7 * B * N;
   if (T <= 0) return 256;
-  return 3 * svr::align256(T * 4) + svr::align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32)) + 256;
+  return std::max(svr::ws_measure(pull_items_layout, T), svr::ws_measure(item_order_layout, T));
 }
 
 extern "C" int64_t svr_gather_pull_plan_workspace_cells(int32_t B, int32_t D, int32_t H, int32_t W) {
-  const int64_t cells = pull_cells(B, D, H, W);
-  return svr::align256((cells + 1) * 4) + svr::align256((int64_t)svr::scan_max_i32_temp_bytes(cells + 1)) + 256;
+  return svr::ws_measure(pull_cells_layout, pull_cells(B, D, H, W));
 }
 
 extern "C" int svr_gather_pull_plan(const float *points, int32_t B, int32_t N, int32_t D, int32_t H, int32_t W, int32_t C,
@@ -1342,32 +1358,24 @@ extern "C" int svr_gather_pull_plan(const float *points, int32_t B, int32_t N, i
   SVR_CHECK(cells < (1LL << 31) - 1 && T < (1LL << 31) && (int64_t)B * N * row_stride < (1LL << 31), SVR_E_UNSUPPORTED,
             "pull_plan: %ld cells / %ld items / %ld gradient floats exceed 32-bit offsets", (long)cells, (long)T,
             (long)((int64_t)B * N * row_stride));
-  char *w = svr::align256(workspace);
-  int32_t *ends = (int32_t *)w;   // raw cell ends, then the running maximum goes to `heads`
-  w += svr::align256((cells + 1) * 4);
-  void *scan_tmp = (void *)w;
-  const size_t scan_bytes = svr::scan_max_i32_temp_bytes(cells + 1);
-  w += svr::align256((int64_t)scan_bytes);
-  hipError_t e = hipMemsetAsync(ends, 0, (size_t)(cells + 1) * sizeof(int32_t), s);
+  svr::WsCursor c(workspace);
+  const PullCellsWs wc = pull_cells_layout(c, cells);   // raw cell ends, then the running maximum goes to `heads`
+  hipError_t e = hipMemsetAsync(wc.ends, 0, (size_t)(cells + 1) * sizeof(int32_t), s);
   SVR_CHECK(e == hipSuccess, (int)e, "pull_plan: memset failed: %s", hipGetErrorString(e));
   if (T > 0) {
     SVR_CHECK(points && keys && recs, SVR_E_BADARG, "pull_plan: null pointer");
-    uint32_t *keys_in = (uint32_t *)w;
-    w += svr::align256(T * 4);
-    int32_t *vals_in = (int32_t *)w;
-    w += svr::align256(T * 4);
-    int32_t *items = items_out ? items_out : (int32_t *)w;   // the sorted item ids double as svr_level.item_order
-    w += svr::align256(T * 4);
+    const PullItemsWs w = pull_items_layout(c, T);
+    int32_t *items = items_out ? items_out : w.items;   // the sorted item ids double as svr_level.item_order
     const uint32_t sentinel = (uint32_t)cells;
     const int bits = pull_key_bits(cells);
-    hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys_in, vals_in, T, N, D,
+    hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, w.keys_in, w.vals_in, T, N, D,
                        H, W, displacement, align_corners, sentinel, 0);
-    e = svr::sort_pairs_u32((void *)w, svr::sort_pairs_u32_temp_bytes(T, bits), keys_in, keys, vals_in, items, T, bits, s);
+    e = svr::sort_pairs_u32(w.sort_tmp, svr::sort_pairs_u32_temp_bytes(T, bits), w.keys_in, keys, w.vals_in, items, T, bits, s);
     SVR_CHECK(e == hipSuccess, (int)e, "pull_plan: radix sort failed: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(pull_record_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys, items,
-                       (PullRec *)recs, ends, T, N, D, H, W, C, col, row_stride, displacement, align_corners, sentinel);
+                       (PullRec *)recs, wc.ends, T, N, D, H, W, C, col, row_stride, displacement, align_corners, sentinel);
   }
-  e = svr::scan_max_i32(scan_tmp, scan_bytes, ends, heads, cells + 1, s);
+  e = svr::scan_max_i32(wc.scan_tmp, wc.scan_bytes, wc.ends, heads, cells + 1, s);
   SVR_CHECK(e == hipSuccess, (int)e, "pull_plan: scan failed: %s", hipGetErrorString(e));
   if (stats) {
     e = hipMemsetAsync(stats, 0, 2 * sizeof(int32_t), s);
@@ -1394,17 +1402,12 @@ int item_order_impl(const float *points, int32_t B, int32_t N, int32_t D, int32_
   SVR_CHECK(nkeys < (1LL << 31) - 1 && T < (1LL << 31), SVR_E_UNSUPPORTED, "item_order: %ld keys / %ld items exceed 32 bits",
             (long)nkeys, (long)T);
   hipStream_t s = (hipStream_t)stream;
-  char *w = svr::align256(workspace);
-  uint32_t *keys_in = (uint32_t *)w;
-  w += svr::align256(T * 4);
-  int32_t *vals_in = (int32_t *)w;
-  w += svr::align256(T * 4);
-  uint32_t *keys_out = (uint32_t *)w;
-  w += svr::align256(T * 4);
+  svr::WsCursor c(workspace);
+  const ItemOrderWs w = item_order_layout(c, T);
   const int bits = pull_key_bits(nkeys);
-  hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys_in, vals_in, T, N, D, H,
+  hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, w.keys_in, w.vals_in, T, N, D, H,
                      W, displacement, align_corners, (uint32_t)nkeys, kblk);
-  hipError_t e = svr::sort_pairs_u32((void *)w, svr::sort_pairs_u32_temp_bytes(T, bits), keys_in, keys_out, vals_in, items, T,
+  hipError_t e = svr::sort_pairs_u32(w.sort_tmp, svr::sort_pairs_u32_temp_bytes(T, bits), w.keys_in, w.keys_out, w.vals_in, items, T,
                                      bits, s);
   SVR_CHECK(e == hipSuccess, (int)e, "item_order: radix sort failed: %s", hipGetErrorString(e));
   return svr::launch_status("item_order");
@@ -1441,11 +1444,18 @@ extern "C" int svr_gather_project_bwd(const float *points, const float *dh, int6
 }
 
 // ---- two-pass projected scatter (see gather_bwd_proj_store_kernel)
+namespace {
+struct ProjectPlanWs { uint32_t *keys_in; int32_t *vals_in; char *sort_tmp; int32_t *flags; char *scan_tmp; size_t scan_bytes; char *pad; };
+ProjectPlanWs project_plan_layout(svr::WsCursor &c, int64_t T) {
+  const size_t scan_bytes = svr::scan_sum_excl_i32_temp_bytes(T + 1);
+  return {c.take<uint32_t>(T), c.take<int32_t>(T), c.take<char>((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32)), c.take<int32_t>(T + 1),
+          c.take<char>((int64_t)scan_bytes), scan_bytes, c.take<char>(256)};   // pad: unused, the size has always carried it
+}
+}  // namespace
+
 extern "C" int64_t svr_gather_project_plan_workspace(int32_t B, int32_t N) {
   const int64_t T = (int64_t)7 * B * N;
-  if (T <= 0) return 256;
-  return 2 * svr::align256(T * 4) + svr::align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32)) + svr::align256((T + 1) * 4) +
-         svr::align256((int64_t)svr::scan_sum_excl_i32_temp_bytes(T + 1)) + 512;
+  return T <= 0 ? 256 : svr::ws_measure(project_plan_layout, T);
 }
 
 extern "C" int64_t svr_gather_project_slots(int32_t B, int32_t N, int32_t D, int32_t H, int32_t W) {
@@ -1464,23 +1474,16 @@ extern "C" int svr_gather_project_plan(const float *points, int32_t B, int32_t N
   SVR_CHECK(nkeys < (1LL << 31) - 1 && T < (1LL << 31) - 1, SVR_E_UNSUPPORTED, "project_plan: %ld keys / %ld items exceed 32 bits",
             (long)nkeys, (long)T);
   hipStream_t s = (hipStream_t)stream;
-  char *w = svr::align256(workspace);
-  uint32_t *keys_in = (uint32_t *)w;
-  w += svr::align256(T * 4);
-  int32_t *vals_in = (int32_t *)w;
-  w += svr::align256(T * 4);
+  svr::WsCursor c(workspace);
+  const ProjectPlanWs w = project_plan_layout(c, T);
   const int bits = pull_key_bits(nkeys);
-  void *sort_tmp = w;
-  w += svr::align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32));
-  int32_t *flags = (int32_t *)w;
-  w += svr::align256((T + 1) * 4);
-  hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, keys_in, vals_in, T, N, D, H,
+  hipLaunchKernelGGL(pull_key_kernel, dim3((unsigned)svr::cdiv(T, 256)), dim3(256), 0, s, points, w.keys_in, w.vals_in, T, N, D, H,
                      W, displacement, align_corners, (uint32_t)nkeys, 1);
-  hipError_t e = svr::sort_pairs_u32(sort_tmp, svr::sort_pairs_u32_temp_bytes(T, bits), keys_in, keys, vals_in, items, T, bits, s);
+  hipError_t e = svr::sort_pairs_u32(w.sort_tmp, svr::sort_pairs_u32_temp_bytes(T, bits), w.keys_in, keys, w.vals_in, items, T, bits, s);
   SVR_CHECK(e == hipSuccess, (int)e, "project_plan: radix sort failed: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(proj_flag_kernel, dim3((unsigned)svr::cdiv(T + 1, 256)), dim3(256), 0, s, (const uint32_t *)keys, flags, T,
+  hipLaunchKernelGGL(proj_flag_kernel, dim3((unsigned)svr::cdiv(T + 1, 256)), dim3(256), 0, s, (const uint32_t *)keys, w.flags, T,
                      2 * 64 * kProjReps, (uint32_t)nkeys);
-  e = svr::scan_sum_excl_i32((void *)w, svr::scan_sum_excl_i32_temp_bytes(T + 1), flags, sidx, T + 1, s);
+  e = svr::scan_sum_excl_i32(w.scan_tmp, w.scan_bytes, w.flags, sidx, T + 1, s);
   SVR_CHECK(e == hipSuccess, (int)e, "project_plan: scan failed: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(proj_table_kernel, dim3((unsigned)svr::cdiv(nkeys + 1, 256)), dim3(256), 0, s, (const uint32_t *)keys,
                      (const int32_t *)sidx, first_slot, nkeys, T);

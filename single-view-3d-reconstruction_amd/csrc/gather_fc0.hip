@@ -718,6 +718,17 @@ int check_desc(const svr_gather_desc *d, const char *who) {
   return SVR_OK;
 }
 
+// amax line | W planes (hi, lo) | the slab table | boxes [tiles][FC_NSTAGE].  The planes are taken at their exact size: for the
+// only n_out the launchers accept (FTN) that is a multiple of 256, so the table and the boxes start on 256-byte lines.
+struct FcWorkspace { uint32_t *amax; uint16_t *p0; FcArgs *Ad; FcBox *boxes; };
+static_assert(FTN * 2 * sizeof(uint16_t) % 256 == 0, "fc0_layout: the planes end on a 256-byte line");
+FcWorkspace fc0_layout(WsCursor &c, int64_t points, int32_t n_out, int KF) {
+  const FcWorkspace w{c.take<uint32_t>(64), c.take<uint16_t>(2 * (int64_t)n_out * KF, 2), c.take<FcArgs>(1),
+                      c.take<FcBox>(cdiv(points, FTM) * FC_NSTAGE, sizeof(FcBox))};
+  c.take<char>(768 - (256 - sizeof(FcArgs) % 256) % 256, 1);   // pad: unused; the size has always been planes + table + boxes + 1280
+  return w;
+}
+
 }  // namespace
 
 extern "C" int32_t svr_gather_fc0_supported(const svr_gather_desc *d) {
@@ -732,28 +743,10 @@ extern "C" int32_t svr_gather_fc0_supported(const svr_gather_desc *d) {
 extern "C" int64_t svr_gather_fc0_workspace(const svr_gather_desc *d, int32_t n_out) {
   FcArgs A;
   if (!d || !build_slabs(d, 0, A)) return 0;
-  const int64_t tiles = cdiv((int64_t)d->B * d->N, FTM);
-  return 2 * (int64_t)n_out * A.KF * (int64_t)sizeof(uint16_t) + 1024 + (int64_t)sizeof(FcArgs) + 256 +
-         tiles * FC_NSTAGE * (int64_t)sizeof(FcBox);
+  return ws_measure(fc0_layout, (int64_t)d->B * d->N, n_out, A.KF);
 }
 
 namespace {
-
-struct FcWorkspace {
-  uint32_t *amax;
-  uint16_t *p0;
-  FcArgs *Ad;
-  FcBox *boxes;   // [tiles][FC_NSTAGE]
-};
-FcWorkspace carve(void *workspace, int32_t n_out, int KF) {
-  FcWorkspace w;
-  w.amax = align256<uint32_t>(workspace);
-  w.p0 = (uint16_t *)(w.amax + 64);
-  uint16_t *p1 = w.p0 + (int64_t)n_out * KF;
-  w.Ad = align256<FcArgs>(p1 + (int64_t)n_out * KF);
-  w.boxes = align256<FcBox>(w.Ad + 1);
-  return w;
-}
 
 // validates the kept-matrix arguments; kend = end of the last kept level's columns
 int check_keep(const svr_gather_desc *d, const FcArgs &A, const float *feat, int64_t ldf, uint32_t keep_levels, int64_t *kend) {
@@ -792,7 +785,8 @@ extern "C" int svr_gather_fc0_prepare(const svr_gather_desc *d, const float *W, 
   int64_t kend;
   if ((rc = check_keep(d, A, feat, ldf, keep_levels, &kend)) != SVR_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const FcWorkspace ws = carve(workspace, n_out, A.KF);
+  WsCursor c(workspace);
+  const FcWorkspace ws = fc0_layout(c, (int64_t)d->B * d->N, n_out, A.KF);
   // W's columns: every column of the layout the slabs cover (the row's padding columns never enter the product)
   int64_t kw = 0;
   for (int l = 0; l < d->n_levels; ++l) kw = std::max<int64_t>(kw, d->level[l].col + 7 * d->level[l].C);
@@ -825,7 +819,8 @@ extern "C" int svr_gather_fc0_run(const svr_gather_desc *d, const float *points,
   for (int l = 0; l < d->n_levels; ++l) kw = std::max<int64_t>(kw, d->level[l].col + 7 * d->level[l].C);
   // kept matrix in the full row layout: the padding starts behind the last LEVEL (kept or not), as svr_gather_trilinear_fwd
   const int64_t pad_start = keep_cols ? kend : kw;
-  const FcWorkspace ws = carve(workspace, n_out, A.KF);
+  WsCursor c(workspace);
+  const FcWorkspace ws = fc0_layout(c, (int64_t)d->B * d->N, n_out, A.KF);
   static const hipError_t lds_attr =  // once per process (an immutable kernel attribute, the library's only global state)
       hipFuncSetAttribute((const void *)gather_fc0_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FC_LDS_BYTES);
   SVR_CHECK(lds_attr == hipSuccess, (int)lds_attr, "gather_fc0_run: cannot reserve %d bytes of LDS: %s", FC_LDS_BYTES,
@@ -865,7 +860,8 @@ extern "C" int svr_gather_fc0_bf16_prepare(const svr_gather_desc *d, const float
   for (int l = 0; l < d->n_levels; ++l)
     SVR_CHECK(((uintptr_t)d->level[l].vol & 7) == 0 || d->level[l].C == 1, SVR_E_ALIGN, "gather_fc0_bf16_prepare: level %d: 8-byte alignment", l);
   hipStream_t s = (hipStream_t)stream;
-  const FcWorkspace ws = carve(workspace, n_out, A.KF);
+  WsCursor c(workspace);
+  const FcWorkspace ws = fc0_layout(c, (int64_t)d->B * d->N, n_out, A.KF);
   hipLaunchKernelGGL(split_w_fused_bf16_kernel, dim3((unsigned)cdiv(A.KF, 64), (unsigned)n_out), dim3(64), 0, s, A, W, ldw, ws.p0, (int)n_out);
   hipLaunchKernelGGL(args_store_kernel, dim3(1), dim3(256), 0, s, A, ws.Ad);
   return launch_status("gather_fc0_bf16_prepare");
@@ -883,7 +879,8 @@ extern "C" int svr_gather_fc0_bf16_run(const svr_gather_desc *d, const float *po
             "gather_fc0_bf16_run: epilogue %d", epilogue);
   FcArgs A;
   SVR_CHECK(build_slabs(d, 0, A), SVR_E_UNSUPPORTED, "gather_fc0_bf16_run: a level's channel count has no slab shape (1, 16, 32, 64 k)");
-  const FcWorkspace ws = carve(workspace, n_out, A.KF);
+  WsCursor c(workspace);
+  const FcWorkspace ws = fc0_layout(c, (int64_t)d->B * d->N, n_out, A.KF);
   static const hipError_t lds_attr =
       hipFuncSetAttribute((const void *)gather_fc0_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FC_LDS_BYTES);
   SVR_CHECK(lds_attr == hipSuccess, (int)lds_attr, "gather_fc0_bf16_run: cannot reserve %d bytes of LDS: %s", FC_LDS_BYTES,

@@ -740,7 +740,7 @@ static_assert(TN_TM == 128 && TN_TN == 128 && XK == 32, "tn_splits_x3 (gemm_core
 
 }  // namespace
 
-extern "C" int64_t svr_linear_bwd_data_bf16x3_workspace(int64_t N, int64_t K) { return 2 * N * K * (int64_t)sizeof(uint16_t) + 256; }
+extern "C" int64_t svr_linear_bwd_data_bf16x3_workspace(int64_t N, int64_t K) { return ws_measure(planes_layout, N * K, 2); }
 
 extern "C" int svr_linear_bwd_data_bf16x3(const float *dY, int64_t lddy, const float *W, int64_t ldw, float *dX, int64_t lddx,
                                           int64_t M, int64_t N, int64_t K, int epilogue, const float *mask, int64_t ldmask,
@@ -753,8 +753,8 @@ extern "C" int svr_linear_bwd_data_bf16x3(const float *dY, int64_t lddy, const f
                                  dY != nullptr}, plan)) return rc;
   SVR_CHECK(!dY || epilogue != SVR_EPI_MASK || mask, SVR_E_BADARG, "linear_bwd_data_bf16x3: epilogue %d needs the mask", epilogue);
   hipStream_t s = (hipStream_t)stream;
-  uint16_t *hi = (uint16_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-  uint16_t *mid = hi + N * K;
+  WsCursor c(workspace, 16);
+  uint16_t *hi = planes_layout(c, N * K, 2), *mid = hi + N * K;
   if (W) hipLaunchKernelGGL(pack_planes_kernel, dim3((unsigned)cdiv(K * (N / 2), 256)), dim3(256), 0, s, W, ldw, hi, mid, N, K);
   if (!dY) return launch_status("linear_bwd_data_bf16x3 (prepare)");
   dim3 grid(xcd_grid(cdiv(K, NN_TN) * cdiv(M, NN_TM)));
@@ -771,8 +771,9 @@ namespace svr {
 int linear_bwd_data_f16_nn(const float *dY, int64_t lddy, const float *W, int64_t ldw, float *dX, int64_t lddx, int64_t M, int64_t N,
                            int64_t K, int epilogue, const float *mask, int64_t ldmask, const uint32_t *amax_dy, uint32_t *amax_dx,
                            void *workspace, hipStream_t s) {
-  uint32_t *amax = align256<uint32_t>(workspace);
-  uint16_t *hi = (uint16_t *)(amax + 64), *lo = hi + N * K;
+  WsCursor c(workspace);
+  const auto [amax, hi] = scaled_planes_layout(c, N * K);
+  uint16_t *lo = hi + N * K;
   if (W) {
     w_amax_launch(W, ldw, N, K, amax, s);
     hipLaunchKernelGGL(pack_planes_f16_kernel, dim3((unsigned)cdiv(K * (N / 2), 256)), dim3(256), 0, s, W, ldw, amax, hi, lo, N, K);
@@ -787,14 +788,18 @@ int linear_bwd_data_f16_nn(const float *dY, int64_t lddy, const float *W, int64_
 
 namespace {
 int64_t tn_mpad(int64_t M) { return cdiv(M, 64) * 64; }
+// slabs | dY planes (hi, mid) | per-row-tile column sums.  One layout for the bf16x3 and the f16x3s weight gradient, so that
+// one exported size serves a buffer used by either: f16x3s transposes in LDS, so it takes the two plane pieces and ignores them.
+struct BwdWeightWs { float *slab; uint16_t *ph, *pm; float *dbpart; };
+BwdWeightWs bwd_weight_layout(WsCursor &c, int64_t M, int64_t N, int64_t K, int splits) {
+  const int64_t dbparts = std::max<int64_t>(cdiv(M, 64), splits);  // row tiles (pre-pass) or splits (tr kernel)
+  return {c.take<float>((int64_t)splits * N * K), c.take<uint16_t>(N * tn_mpad(M)), c.take<uint16_t>(N * tn_mpad(M)), c.take<float>(dbparts * N)};
+}
 }  // namespace
 
 extern "C" int64_t svr_linear_bwd_weight_bf16x3_workspace(int64_t M, int64_t N, int64_t K) {
   int64_t rps;
-  int splits = tn_splits_x3(M, N, K, &rps);
-  // slabs | dY planes (hi, mid) | per-row-tile column sums
-  const int64_t dbparts = cdiv(M, 64) > splits ? cdiv(M, 64) : splits;  // row tiles (pre-pass) or splits (tr kernel)
-  return align256((int64_t)splits * N * K * 4) + 2 * align256(N * tn_mpad(M) * 2) + align256(dbparts * N * 4) + 256;
+  return ws_measure(bwd_weight_layout, M, N, K, tn_splits_x3(M, N, K, &rps));
 }
 
 extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const float *X, int64_t ldx, float *dW,
@@ -807,14 +812,8 @@ extern "C" int svr_linear_bwd_weight_bf16x3(const float *dY, int64_t lddy, const
   const int64_t rps = plan.rows_per_split;
   const int splits = plan.splits;
   const int64_t Mpad = tn_mpad(M), parts = cdiv(M, 64);
-  char *w = align256(workspace);
-  float *slab = (float *)w;
-  w += align256((int64_t)splits * N * K * 4);
-  uint16_t *ph = (uint16_t *)w;
-  w += align256(N * Mpad * 2);
-  uint16_t *pm = (uint16_t *)w;
-  w += align256(N * Mpad * 2);
-  float *dbpart = (float *)w;
+  WsCursor c(workspace);
+  const auto [slab, ph, pm, dbpart] = bwd_weight_layout(c, M, N, K, splits);
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
   if (plan.kernel == SVR_LIN_K_TN_TR) {
     // both operands row-major, transposing LDS reads: no pre-pass over dY; db from the K-tile-0 workgroups
@@ -845,11 +844,9 @@ extern "C" int svr_linear_bwd_weight_f16x3(const float *dY, int64_t lddy, const 
   hipStream_t s = (hipStream_t)stream;
   const int64_t rps = plan.rows_per_split;
   const int splits = plan.splits;
-  const int64_t Mpad = tn_mpad(M);
-  char *w = align256(workspace);
-  float *slab = (float *)w;
-  w += align256((int64_t)splits * N * K * 4) + 2 * align256(N * Mpad * 2);
-  float *dbpart = (float *)w;
+  WsCursor c(workspace);
+  const BwdWeightWs w = bwd_weight_layout(c, M, N, K, splits);
+  float *slab = w.slab, *dbpart = w.dbpart;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
   hipLaunchKernelGGL((linear_tn_x3_tr_kernel<true>), grid, dim3(256), 0, s, dY, lddy, X, ldx, slab, db ? dbpart : nullptr, M, N, K,
                      rps, splits, amax_dy, CwGeom{});
@@ -878,6 +875,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float *__r
   __syncthreads();
   if (g == 0 && idx < total) dW[idx] = ((red[threadIdx.x] + red[threadIdx.x + 64]) + red[threadIdx.x + 128]) + red[threadIdx.x + 192];
 }
+struct ConvWgradWs { float *slab, *dbpart; };
+ConvWgradWs conv_wgrad_layout(WsCursor &c, int64_t N, int64_t K, int splits) {
+  return {c.take<float>((int64_t)splits * N * K), c.take<float>((int64_t)splits * N)};
+}
 int conv_wgrad_splits(int64_t M, int64_t N, int64_t K, int64_t *rows_per_split) {
   const int64_t tiles = cdiv(N, TN_TM) * cdiv(K, TN_TN);
   const int64_t want = std::max<int64_t>(1, 384 / tiles);         // the slabs are written and read once each: few, long splits
@@ -894,8 +895,7 @@ extern "C" int64_t svr_conv2d_bwd_weight_workspace(const svr_conv2d_desc *d, int
   const int Ho = (d->H + 2 - d->k) / d->stride + 1, Wo = (d->W + 2 - d->k) / d->stride + 1;
   int64_t rps;
   const int64_t K = (int64_t)d->k * d->k * Cpad;
-  const int splits = conv_wgrad_splits((int64_t)d->B * Ho * Wo, Cout, K, &rps);
-  return align256((int64_t)splits * Cout * K * 4) + align256((int64_t)splits * Cout * 4) + 256;
+  return ws_measure(conv_wgrad_layout, (int64_t)Cout, K, conv_wgrad_splits((int64_t)d->B * Ho * Wo, Cout, K, &rps));
 }
 
 extern "C" int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, const uint32_t *amax_dy, int32_t Cout, float *dW,
@@ -911,9 +911,8 @@ extern "C" int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, 
   hipStream_t s = (hipStream_t)stream;
   int64_t rps;
   const int splits = conv_wgrad_splits(M, N, K, &rps);
-  char *w = align256(workspace);
-  float *slab = (float *)w;
-  float *dbpart = (float *)(w + align256((int64_t)splits * N * K * 4));
+  WsCursor c(workspace);
+  const auto [slab, dbpart] = conv_wgrad_layout(c, N, K, splits);
   CwGeom G{CvSrc{d->src0, d->src1, d->C0, d->C1, d->H, d->W, d->act}, Wo, Ho * Wo, 1.0f / (float)Wo, 1.0f / (float)(Ho * Wo), d->k, d->stride, 1, Cpad};
   const bool vec4 = d->C0 % 4 == 0 && d->C1 % 4 == 0 && (((uintptr_t)d->src0 | (uintptr_t)d->src1 | (uintptr_t)dY) & 15) == 0;
   dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, 3) void linear_nt_x6_kernel(const float *__res
 
 }  // namespace
 
-extern "C" int64_t svr_linear_fwd_bf16x6_workspace(int64_t N, int64_t K) { return 3 * N * K * (int64_t)sizeof(uint16_t) + 256; }
+extern "C" int64_t svr_linear_fwd_bf16x6_workspace(int64_t N, int64_t K) { return ws_measure(planes_layout, N * K, 3); }
 
 extern "C" int svr_linear_fwd_bf16x6(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias, float *Y,
                                      int64_t ldy, int64_t M, int64_t N, int64_t K, int epilogue, void *workspace,
@@ -175,8 +175,8 @@ extern "C" int svr_linear_fwd_bf16x6(const float *X, int64_t ldx, const float *W
   if (int rc = lin_plan(LinQuery{SVR_LIN_FWD_BF16X6, M, N, K, ldx, ldw, ldy, 0, lo4(X), lo4(W), lo4(Y), 0, epilogue, 0, 1}, plan)) return rc;
   SVR_CHECK(epilogue == SVR_EPI_NONE || bias, SVR_E_BADARG, "linear_fwd_bf16x6: epilogue %d needs bias", epilogue);
   hipStream_t s = (hipStream_t)stream;
-  uint16_t *p0 = (uint16_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-  uint16_t *p1 = p0 + N * K, *p2 = p1 + N * K;
+  WsCursor c(workspace, 16);
+  uint16_t *p0 = planes_layout(c, N * K, 3), *p1 = p0 + N * K, *p2 = p1 + N * K;
   hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)cdiv(N * (K / 2), 256)), dim3(256), 0, s, W, ldw, p0, p1, p2, N, K);
   dim3 grid((unsigned)cdiv(N, TN), (unsigned)cdiv(M, TM));
   hipLaunchKernelGGL(linear_nt_x6_kernel, grid, dim3(256), 0, s, X, ldx, p0, p1, p2,

@@ -334,7 +334,7 @@ void w_amax_launch(const float *W, int64_t ldw, int64_t N, int64_t K, uint32_t *
 }
 }  // namespace svr
 
-extern "C" int64_t svr_linear_fwd_f16x3_workspace(int64_t N, int64_t K) { return 2 * N * K * (int64_t)sizeof(uint16_t) + 512; }
+extern "C" int64_t svr_linear_fwd_f16x3_workspace(int64_t N, int64_t K) { return ws_measure(scaled_planes_layout, N * K); }
 
 extern "C" int svr_linear_fwd_f16x3(const float *X, int64_t ldx, const float *W, int64_t ldw, const float *bias, float *Y,
                                     int64_t ldy, int64_t M, int64_t N, int64_t K, int epilogue, void *workspace,
@@ -345,8 +345,8 @@ extern "C" int svr_linear_fwd_f16x3(const float *X, int64_t ldx, const float *W,
   LinPlan plan;   // shape checks first (PREPARE), the operand checks of a RUN below
   if (int rc = lin_plan(LinQuery{SVR_LIN_FWD_F16X3, M, N, K, ldx, ldw, ldy, 0, 0, 0, 0, 0, SVR_EPI_NONE, 0, 0}, plan)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  uint32_t *amax = align256<uint32_t>(workspace);
-  uint16_t *p0 = (uint16_t *)(amax + 64);
+  WsCursor c(workspace);
+  const auto [amax, p0] = scaled_planes_layout(c, N * K);
   if (W) {
     w_amax_launch(W, ldw, N, K, amax, s);
     hipLaunchKernelGGL(split_w_kernel, dim3((unsigned)cdiv(N * (K / 2), 256)), dim3(256), 0, s, W, ldw, amax, p0, N, K, 0);
@@ -380,7 +380,7 @@ extern "C" int svr_amax_f32(const float *X, int64_t ld, int64_t M, int64_t N, ui
   return launch_status("amax_f32");
 }
 
-extern "C" int64_t svr_linear_bwd_data_f16x3_workspace(int64_t N, int64_t K) { return 2 * N * K * (int64_t)sizeof(uint16_t) + 512; }
+extern "C" int64_t svr_linear_bwd_data_f16x3_workspace(int64_t N, int64_t K) { return ws_measure(scaled_planes_layout, N * K); }
 
 extern "C" int svr_linear_bwd_data_f16x3(const float *dY, int64_t lddy, const float *W, int64_t ldw, float *dX, int64_t lddx,
                                          int64_t M, int64_t N, int64_t K, int epilogue, const float *mask, int64_t ldmask,
@@ -397,8 +397,8 @@ extern "C" int svr_linear_bwd_data_f16x3(const float *dY, int64_t lddy, const fl
   hipStream_t s = (hipStream_t)stream;
   if (plan.kernel == SVR_LIN_K_NN_X3)
     return svr::linear_bwd_data_f16_nn(dY, lddy, W, ldw, dX, lddx, M, N, K, epilogue, mask, ldmask, amax_dy, amax_dx, workspace, s);
-  uint32_t *amax = align256<uint32_t>(workspace);
-  uint16_t *p0 = (uint16_t *)(amax + 64);
+  WsCursor c(workspace);
+  const auto [amax, p0] = scaled_planes_layout(c, N * K);
   if (W) {   // planes of W^T: K rows (dX columns) x N reduction elements
     w_amax_launch(W, ldw, N, K, amax, s);
     hipLaunchKernelGGL(split_w_kernel, dim3((unsigned)cdiv(K * (N / 2), 256)), dim3(256), 0, s, W, ldw, amax, p0, K, N, 1);

@@ -332,42 +332,22 @@ __global__ __launch_bounds__(kBlock) void mcc_emit_kernel(const uint32_t *__rest
 }
 
 bool sizes_ok(int64_t V, int64_t F) { return V >= 0 && V < (1LL << 31) && F >= 0 && F < (1LL << 31); }
-int64_t words(int64_t n) { return align256(n * 4); }
-int64_t scan_bytes(int64_t n) { return n > 0 ? align256((int64_t)scan_sum_excl_i32_temp_bytes(n)) : 0; }
+size_t scan_temp(int64_t n) { return n > 0 ? scan_sum_excl_i32_temp_bytes(n) : 0; }
 
-// the labelling's pieces of the workspace
-struct LabelWs {
-  int32_t *parent, *root_of, *is_root, *rank;
-  void *tmp;
-};
-LabelWs carve_label(void *ws, int64_t V) {
-  char *w = align256<char>(ws);
-  LabelWs r;
-  r.parent = (int32_t *)w;
-  r.root_of = (int32_t *)(w + words(V));
-  r.is_root = (int32_t *)(w + 2 * words(V));
-  r.rank = (int32_t *)(w + 3 * words(V));
-  r.tmp = w + 4 * words(V);
-  return r;
+// One buffer serves the three stages in turn, each with a layout of its own; the exported size is the largest of the three.
+struct LabelWs { int32_t *parent, *root_of, *is_root, *rank; char *tmp; size_t tmp_bytes; };
+LabelWs label_layout(WsCursor &c, int64_t V) {
+  const size_t tmp_bytes = scan_temp(V);
+  return {c.take<int32_t>(V), c.take<int32_t>(V), c.take<int32_t>(V), c.take<int32_t>(V), c.take<char>((int64_t)tmp_bytes), tmp_bytes};
 }
-int64_t label_bytes(int64_t V) { return 4 * words(V) + scan_bytes(V); }
-
-// the filter's: count leaves them for emit
-struct FilterWs {
-  int32_t *vertex_keep, *vertex_off, *face_keep, *face_off;
-  void *tmp;
-};
-FilterWs carve_filter(void *ws, int64_t V, int64_t F) {
-  char *w = align256<char>(ws);
-  FilterWs r;
-  r.vertex_keep = (int32_t *)w;
-  r.vertex_off = (int32_t *)(w + words(V));
-  r.face_keep = (int32_t *)(w + 2 * words(V));
-  r.face_off = (int32_t *)(w + 2 * words(V) + words(F));
-  r.tmp = w + 2 * words(V) + 2 * words(F);
-  return r;
+// the statistics rows: C <= V of them
+uint32_t *rows_layout(WsCursor &c, int64_t V) { return c.take<uint32_t>(V * kRow); }
+// the filter's pieces: count leaves them for emit; one temp piece serves the vertex scan and the face scan
+struct FilterWs { int32_t *vertex_keep, *vertex_off, *face_keep, *face_off; char *tmp; size_t vertex_tmp_bytes, face_tmp_bytes; };
+FilterWs filter_layout(WsCursor &c, int64_t V, int64_t F) {
+  const size_t tv = scan_temp(V), tf = scan_temp(F);
+  return {c.take<int32_t>(V), c.take<int32_t>(V), c.take<int32_t>(F), c.take<int32_t>(F), c.take<char>((int64_t)std::max(tv, tf)), tv, tf};
 }
-int64_t filter_bytes(int64_t V, int64_t F) { return 2 * words(V) + 2 * words(F) + std::max(scan_bytes(V), scan_bytes(F)); }
 
 unsigned blocks(int64_t n) { return (unsigned)cdiv(n, kBlock); }
 
@@ -375,8 +355,7 @@ unsigned blocks(int64_t n) { return (unsigned)cdiv(n, kBlock); }
 
 extern "C" int64_t svr_mesh_components_workspace_bytes(int64_t V, int64_t F) {
   SVR_CHECK(sizes_ok(V, F), SVR_E_BADSHAPE, "mesh_components_workspace_bytes: V=%ld F=%ld (need 0 <= V, F < 2^31)", (long)V, (long)F);
-  // one buffer serves the three stages in turn: the largest of them (C <= V statistics rows), and the slack of align256
-  return std::max(std::max(label_bytes(V), align256(V * kRow * 4)), filter_bytes(V, F)) + 256;
+  return std::max(std::max(ws_measure(label_layout, V), ws_measure(rows_layout, V)), ws_measure(filter_layout, V, F));
 }
 
 extern "C" int svr_mesh_components_label(const int32_t *faces, int64_t F, int64_t V, void *ws, int64_t ws_bytes, int32_t *vertex_label,
@@ -393,14 +372,14 @@ extern "C" int svr_mesh_components_label(const int32_t *faces, int64_t F, int64_
     SVR_CHECK(e == hipSuccess, (int)e, "mesh_components_label: memset failed: %s", hipGetErrorString(e));
     return SVR_OK;
   }
-  SVR_CHECK(ws_bytes >= svr_mesh_components_workspace_bytes(V, F), SVR_E_BADARG, "mesh_components_label: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_mesh_components_workspace_bytes(V, F));
-  const LabelWs w = carve_label(ws, V);
+  WsCursor c(ws);
+  const LabelWs w = label_layout(c, V);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "mesh_components_label: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   hipLaunchKernelGGL(mcc_init_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, w.parent, V);
   if (F > 0) hipLaunchKernelGGL(mcc_hook_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, faces, F, V, w.parent);
   hipLaunchKernelGGL(mcc_flatten_kernel, dim3(blocks(V)), dim3(kBlock), 0, s, w.parent, V, w.root_of, w.is_root);
   if (int rc = launch_status("mesh_components_label")) return rc;
-  e = scan_sum_excl_i32(w.tmp, scan_sum_excl_i32_temp_bytes(V), w.is_root, w.rank, V, s);
+  e = scan_sum_excl_i32(w.tmp, w.tmp_bytes, w.is_root, w.rank, V, s);
   SVR_CHECK(e == hipSuccess, (int)e, "mesh_components_label: scan failed: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(mcc_relabel_kernel, dim3(blocks(std::max(V, F))), dim3(kBlock), 0, s, w.root_of, w.is_root, w.rank, V, faces, F,
                      vertex_label, face_label, (long long *)count);
@@ -417,10 +396,10 @@ extern "C" int svr_mesh_components_stats(const float *verts, int64_t V, const in
   SVR_CHECK(verts && vertex_label && (F == 0 || face_label) && ws && root && vertex_count && face_count && marked_count && bbox_min &&
                 bbox_max,
             SVR_E_BADARG, "mesh_components_stats: null pointer");
-  SVR_CHECK(ws_bytes >= svr_mesh_components_workspace_bytes(V, F), SVR_E_BADARG, "mesh_components_stats: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_mesh_components_workspace_bytes(V, F));
+  WsCursor c(ws);
+  uint32_t *rows = rows_layout(c, V);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "mesh_components_stats: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   const hipStream_t s = (hipStream_t)stream;
-  uint32_t *rows = align256<uint32_t>(ws);
   hipLaunchKernelGGL(mcc_rows_init_kernel, dim3(blocks(C * kRow)), dim3(kBlock), 0, s, rows, C);
   const int uniform = uniform_path != 0;
   hipLaunchKernelGGL(mcc_vertex_stats_kernel, dim3(blocks(cdiv(V, kPerThread))), dim3(kBlock), 0, s, verts, vertex_label, mark, V, C, rows, uniform);
@@ -441,15 +420,15 @@ extern "C" int svr_mesh_filter_count(const int32_t *faces, int64_t F, int64_t V,
   SVR_CHECK(e == hipSuccess, (int)e, "mesh_filter_count: memset failed: %s", hipGetErrorString(e));
   if (V == 0 || F == 0) return SVR_OK;  // no valid face: nothing is kept
   SVR_CHECK(faces && vertex_label && keep && ws, SVR_E_BADARG, "mesh_filter_count: null pointer");
-  SVR_CHECK(ws_bytes >= svr_mesh_components_workspace_bytes(V, F), SVR_E_BADARG, "mesh_filter_count: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_mesh_components_workspace_bytes(V, F));
-  const FilterWs w = carve_filter(ws, V, F);
+  WsCursor c(ws);
+  const FilterWs w = filter_layout(c, V, F);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "mesh_filter_count: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   e = hipMemsetAsync(w.vertex_keep, 0, (size_t)V * 4, s);
   SVR_CHECK(e == hipSuccess, (int)e, "mesh_filter_count: memset failed: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(mcc_keep_kernel, dim3(blocks(F)), dim3(kBlock), 0, s, faces, F, V, vertex_label, keep, C, w.vertex_keep, w.face_keep);
   if (int rc = launch_status("mesh_filter_keep")) return rc;
-  e = scan_sum_excl_i32(w.tmp, scan_sum_excl_i32_temp_bytes(V), w.vertex_keep, w.vertex_off, V, s);
-  if (e == hipSuccess) e = scan_sum_excl_i32(w.tmp, scan_sum_excl_i32_temp_bytes(F), w.face_keep, w.face_off, F, s);
+  e = scan_sum_excl_i32(w.tmp, w.vertex_tmp_bytes, w.vertex_keep, w.vertex_off, V, s);
+  if (e == hipSuccess) e = scan_sum_excl_i32(w.tmp, w.face_tmp_bytes, w.face_keep, w.face_off, F, s);
   SVR_CHECK(e == hipSuccess, (int)e, "mesh_filter_count: scan failed: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(mcc_totals_kernel, dim3(1), dim3(1), 0, s, w.vertex_keep, w.vertex_off, V, w.face_keep, w.face_off, F,
                      (long long *)totals);
@@ -461,9 +440,9 @@ extern "C" int svr_mesh_filter_emit(const float *verts, int64_t V, const int32_t
   SVR_CHECK(sizes_ok(V, F), SVR_E_BADSHAPE, "mesh_filter_emit: V=%ld F=%ld (need 0 <= V, F < 2^31)", (long)V, (long)F);
   if (V == 0 || F == 0) return SVR_OK;
   SVR_CHECK(verts && faces && ws && out_verts && out_faces && vertex_index, SVR_E_BADARG, "mesh_filter_emit: null pointer");
-  SVR_CHECK(ws_bytes >= svr_mesh_components_workspace_bytes(V, F), SVR_E_BADARG, "mesh_filter_emit: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_mesh_components_workspace_bytes(V, F));
-  const FilterWs w = carve_filter(ws, V, F);
+  WsCursor c(ws);
+  const FilterWs w = filter_layout(c, V, F);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "mesh_filter_emit: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   hipLaunchKernelGGL(mcc_emit_kernel, dim3(blocks(std::max(V, F))), dim3(kBlock), 0, (hipStream_t)stream, (const uint32_t *)verts, V, faces,
                      F, w.vertex_keep, w.vertex_off, w.face_keep, w.face_off, (uint32_t *)out_verts, out_faces, vertex_index);
   return launch_status("mesh_filter_emit");

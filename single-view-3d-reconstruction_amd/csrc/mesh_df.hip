@@ -285,16 +285,9 @@ struct Ws {
   size_t tmp_bytes;
 };
 
-Ws carve(void *ws, int64_t nb) {
-  Ws w;
-  char *p = (char *)ws;
-  w.counts = (unsigned long long *)p;
-  p += align256((nb + 1) * 8);
-  w.thr2 = (double *)p;
-  p += align256(nb * 8);
-  w.tmp = p;
-  w.tmp_bytes = scan_sum_excl_u64_temp_bytes(nb + 1);
-  return w;
+Ws ws_layout(WsCursor &c, int64_t nb) {   // the launchers have always used the caller's pointer as it is: base alignment 1
+  const size_t tmp_bytes = scan_sum_excl_u64_temp_bytes(nb + 1);
+  return {c.take<unsigned long long>(nb + 1), c.take<double>(nb), c.take<char>((int64_t)tmp_bytes), tmp_bytes};
 }
 
 }  // namespace
@@ -311,7 +304,7 @@ extern "C" int64_t svr_mesh_df_bricks(int32_t X, int32_t Y, int32_t Z, int32_t s
 
 extern "C" int64_t svr_mesh_df_workspace_bytes(int32_t X, int32_t Y, int32_t Z, int32_t s) {
   DF_BRICKS("mesh_df_workspace_bytes");
-  return align256((B.n + 1) * 8) + align256(B.n * 8) + align256((int64_t)scan_sum_excl_u64_temp_bytes(B.n + 1)) + 256;
+  return ws_measure(ws_layout, B.n);
 }
 
 extern "C" int svr_mesh_df_valid_faces(const double *tri, int64_t F, void *ws, int64_t *n_valid, void *stream) {
@@ -338,9 +331,9 @@ extern "C" int svr_mesh_df_count(const double *tri, int64_t F, int32_t X, int32_
   SVR_CHECK(F > 0 && F < (1LL << 31), SVR_E_BADSHAPE, "mesh_df_count: F=%ld (need 1 <= F < 2^31)", (long)F);
   SVR_CHECK(tri && ws && offsets, SVR_E_BADARG, "mesh_df_count: null pointer");
   SVR_CHECK(slack >= 0.0, SVR_E_BADARG, "mesh_df_count: slack=%g", slack);  // false for NaN too
-  SVR_CHECK(ws_bytes >= svr_mesh_df_workspace_bytes(X, Y, Z, s), SVR_E_BADARG, "mesh_df_count: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_mesh_df_workspace_bytes(X, Y, Z, s));
-  const Ws w = carve(ws, B.n);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, B.n);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "mesh_df_count: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   hipStream_t st = (hipStream_t)stream;
   // the cap on dmin: (float)T is what the exact kernel compares with; a hair above it, so that rounding T never drops a face
   const double cap = truncate > 0.0 ? (double)(float)truncate * (1.0 + 0x1p-22) : 0.0;
@@ -360,7 +353,8 @@ extern "C" int svr_mesh_df_emit(const double *tri, int64_t F, int32_t X, int32_t
   SVR_CHECK(capacity >= 0, SVR_E_BADARG, "mesh_df_emit: capacity=%ld", (long)capacity);
   if (b0 == b1 || capacity == 0) return SVR_OK;
   SVR_CHECK(tri && ws && offsets && list, SVR_E_BADARG, "mesh_df_emit: null pointer");
-  const Ws w = carve(const_cast<void *>(ws), B.n);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, B.n);
   hipLaunchKernelGGL(df_emit_kernel, dim3((unsigned)(b1 - b0)), dim3(kCullThreads), 0, (hipStream_t)stream, tri, (int32_t)F, B, w.thr2,
                      offsets, b0, list, capacity);
   return launch_status("mesh_df_emit");

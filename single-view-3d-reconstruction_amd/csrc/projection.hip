@@ -403,12 +403,38 @@ extern "C" int svr_voxelize_splat_fwd(const float *pts, float *acc, int32_t *bas
   return launch_status("splat_fwd");
 }
 
+namespace {
+struct SplatWs {
+  int32_t *ends, *cs;
+  char *scan_tmp;
+  size_t scan_bytes;
+  uint32_t *keys_in = nullptr, *keys = nullptr;   // the item pieces exist only for T > 0
+  int32_t *vals_in = nullptr, *items = nullptr;
+  SplatRec *recs = nullptr;
+  char *sort_tmp = nullptr;
+};
+SplatWs splat_ordered_layout(WsCursor &c, int64_t cells, int64_t T) {
+  SplatWs w;
+  w.ends = c.take<int32_t>(cells + 1);
+  w.cs = c.take<int32_t>(cells + 1);
+  w.scan_bytes = svr::scan_max_i32_temp_bytes(cells + 1);
+  w.scan_tmp = c.take<char>((int64_t)w.scan_bytes);
+  if (T > 0) {
+    w.keys_in = c.take<uint32_t>(T);
+    w.vals_in = c.take<int32_t>(T);
+    w.keys = c.take<uint32_t>(T);
+    w.items = c.take<int32_t>(T);
+    w.recs = c.take<SplatRec>(T);
+    w.sort_tmp = c.take<char>((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32));   // for the widest key; sorted with fewer bits
+  }
+  c.take<char>(256);   // pad: unused, the size has always carried it
+  return w;
+}
+}  // namespace
+
 extern "C" int64_t svr_voxelize_splat_ordered_workspace(int32_t B, int32_t N, int32_t D0, int32_t D1, int32_t D2) {
   if (!splat_ordered_fits(B, N, D0, D1, D2)) return SVR_E_UNSUPPORTED;
-  const int64_t cells = splat_cells(B, D0, D1, D2), T = (int64_t)B * N;
-  int64_t bytes = 2 * align256((cells + 1) * 4) + align256((int64_t)svr::scan_max_i32_temp_bytes(cells + 1)) + 512;
-  if (T > 0) bytes += 4 * align256(T * 4) + align256(T * 16) + align256((int64_t)svr::sort_pairs_u32_temp_bytes(T, 32));
-  return bytes;
+  return ws_measure(splat_ordered_layout, splat_cells(B, D0, D1, D2), (int64_t)B * N);
 }
 
 extern "C" int svr_voxelize_splat_fwd_ordered(const float *pts, float *acc, float *vox, int32_t *base, uint8_t *valid,
@@ -423,43 +449,25 @@ extern "C" int svr_voxelize_splat_fwd_ordered(const float *pts, float *acc, floa
   SVR_CHECK(acc && workspace, SVR_E_BADARG, "splat_fwd_ordered: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const int64_t cells = splat_cells(B, D0, D1, D2), T = (int64_t)B * N;
-  char *w = align256(workspace);
-  int32_t *ends = (int32_t *)w;
-  w += align256((cells + 1) * 4);
-  int32_t *cs = (int32_t *)w;
-  w += align256((cells + 1) * 4);
-  void *scan_tmp = (void *)w;
-  const size_t scan_bytes = svr::scan_max_i32_temp_bytes(cells + 1);
-  w += align256((int64_t)scan_bytes);
-  hipError_t e = hipMemsetAsync(ends, 0, (size_t)(cells + 1) * sizeof(int32_t), s);
+  WsCursor c(workspace);
+  const SplatWs w = splat_ordered_layout(c, cells, T);
+  hipError_t e = hipMemsetAsync(w.ends, 0, (size_t)(cells + 1) * sizeof(int32_t), s);
   SVR_CHECK(e == hipSuccess, (int)e, "splat_fwd_ordered: memset failed: %s", hipGetErrorString(e));
-  const SplatRec *recs = nullptr;
   if (T > 0) {
     SVR_CHECK(pts, SVR_E_BADARG, "splat_fwd_ordered: null points");
-    uint32_t *keys_in = (uint32_t *)w;
-    w += align256(T * 4);
-    int32_t *vals_in = (int32_t *)w;
-    w += align256(T * 4);
-    uint32_t *keys = (uint32_t *)w;
-    w += align256(T * 4);
-    int32_t *items = (int32_t *)w;
-    w += align256(T * 4);
-    SplatRec *rw = (SplatRec *)w;
-    w += align256(T * 16);
     const uint32_t sentinel = (uint32_t)cells;
     const int bits = splat_key_bits(cells);
-    hipLaunchKernelGGL(splat_key_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, s, pts, keys_in, vals_in, base, valid, T, N,
+    hipLaunchKernelGGL(splat_key_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, s, pts, w.keys_in, w.vals_in, base, valid, T, N,
                        D0, D1, D2, sentinel);
-    e = svr::sort_pairs_u32((void *)w, svr::sort_pairs_u32_temp_bytes(T, bits), keys_in, keys, vals_in, items, T, bits, s);
+    e = svr::sort_pairs_u32(w.sort_tmp, svr::sort_pairs_u32_temp_bytes(T, bits), w.keys_in, w.keys, w.vals_in, w.items, T, bits, s);
     SVR_CHECK(e == hipSuccess, (int)e, "splat_fwd_ordered: radix sort failed: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(splat_record_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, s, pts, (const uint32_t *)keys,
-                       (const int32_t *)items, rw, ends, T, D0, D1, D2, sentinel);
-    recs = rw;
+    hipLaunchKernelGGL(splat_record_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, s, pts, (const uint32_t *)w.keys,
+                       (const int32_t *)w.items, w.recs, w.ends, T, D0, D1, D2, sentinel);
   }
-  e = svr::scan_max_i32(scan_tmp, scan_bytes, ends, cs, cells + 1, s);
+  e = svr::scan_max_i32(w.scan_tmp, w.scan_bytes, w.ends, w.cs, cells + 1, s);
   SVR_CHECK(e == hipSuccess, (int)e, "splat_fwd_ordered: scan failed: %s", hipGetErrorString(e));
   const int64_t strips = (int64_t)B * D0 * D1 * cdiv(D2, SPLAT_XS);  // < cells < 2^31
-  hipLaunchKernelGGL(splat_pull_kernel, dim3((unsigned)cdiv(strips, 256)), dim3(256), 0, s, acc, vox, recs, (const int32_t *)cs,
+  hipLaunchKernelGGL(splat_pull_kernel, dim3((unsigned)cdiv(strips, 256)), dim3(256), 0, s, acc, vox, (const SplatRec *)w.recs, (const int32_t *)w.cs,
                      (int)T, strips, D0, D1, D2);
   return launch_status("splat_fwd_ordered");
 }

@@ -247,6 +247,11 @@ __global__ __launch_bounds__(T * T) void rc_eval_kernel(const double *__restrict
   }
 }
 
+struct Ws { unsigned long long *counts; char *tmp; size_t tmp_bytes; };   // counts: tiles + 1
+Ws ws_layout(WsCursor &c, int64_t n) {
+  const size_t tmp_bytes = scan_sum_excl_u64_temp_bytes(n + 1);
+  return {c.take<unsigned long long>(n + 1), c.take<char>((int64_t)tmp_bytes), tmp_bytes};
+}
 }  // namespace
 
 #define RC_TILES(name)                                                                                                  \
@@ -260,7 +265,7 @@ extern "C" int64_t svr_raycast_tiles(int32_t H, int32_t W, int32_t T) {
 
 extern "C" int64_t svr_raycast_workspace_bytes(int32_t H, int32_t W, int32_t T) {
   RC_TILES("raycast_workspace_bytes");
-  return align256((S.n + 1) * 8) + align256((int64_t)scan_sum_excl_u64_temp_bytes(S.n + 1)) + 256;
+  return ws_measure(ws_layout, S.n);
 }
 
 extern "C" int svr_raycast_face_bounds(const double *tri, int64_t F, const float *consts, int32_t *rects, void *stream) {
@@ -275,15 +280,13 @@ extern "C" int svr_raycast_count(const int32_t *rects, int64_t F, int32_t H, int
   RC_TILES("raycast_count");
   SVR_CHECK(F > 0 && F < (1LL << 31), SVR_E_BADSHAPE, "raycast_count: F=%ld (need 1 <= F < 2^31)", (long)F);
   SVR_CHECK(rects && ws && offsets, SVR_E_BADARG, "raycast_count: null pointer");
-  SVR_CHECK(ws_bytes >= svr_raycast_workspace_bytes(H, W, T), SVR_E_BADARG, "raycast_count: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_raycast_workspace_bytes(H, W, T));
-  unsigned long long *counts = align256<unsigned long long>(ws);
-  void *tmp = (char *)counts + align256((S.n + 1) * 8);
-  const size_t tmp_bytes = scan_sum_excl_u64_temp_bytes(S.n + 1);
+  WsCursor c(ws);
+  const Ws w = ws_layout(c, S.n);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "raycast_count: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(rc_count_kernel, dim3((unsigned)S.n), dim3(kCullThreads), 0, st, rects, (int32_t)F, S, counts);
+  hipLaunchKernelGGL(rc_count_kernel, dim3((unsigned)S.n), dim3(kCullThreads), 0, st, rects, (int32_t)F, S, w.counts);
   if (int rc = launch_status("raycast_count")) return rc;
-  hipError_t e = scan_sum_excl_u64(tmp, tmp_bytes, (const uint64_t *)counts, (uint64_t *)offsets, S.n + 1, st);
+  hipError_t e = scan_sum_excl_u64(w.tmp, w.tmp_bytes, (const uint64_t *)w.counts, (uint64_t *)offsets, S.n + 1, st);
   SVR_CHECK(e == hipSuccess, (int)e, "raycast_count: scan failed: %s", hipGetErrorString(e));
   return launch_status("raycast_scan");
 }

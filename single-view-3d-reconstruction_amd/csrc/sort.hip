@@ -98,6 +98,13 @@ size_t rocprim_temp_bytes(int64_t total, int bits) {
   return tmp;
 }
 
+// Morton order and voxel order share this layout: the temp piece is sized for the wider key (Morton, 30 code bits; a voxel
+// order's row-major cell index has at most 30), while rocprim is handed the size for the bits actually sorted
+struct SortWs { uint64_t *keys_in, *keys_out; int32_t *vals_in; char *tmp; };
+SortWs sort_layout(WsCursor &c, int B, int64_t total) {
+  return {c.take<uint64_t>(total), c.take<uint64_t>(total), c.take<int32_t>(total),
+          c.take<char>((int64_t)rocprim_temp_bytes(total, key_bits(B, 30)))};
+}
 
 int sort_points(const float *points, int32_t *order, float *sorted_points, int B, int N, int mode, int D, int H, int W,
                 int ac, void *workspace, hipStream_t s, const char *what) {
@@ -106,19 +113,14 @@ int sort_points(const float *points, int32_t *order, float *sorted_points, int B
   SVR_CHECK(points && order && workspace, SVR_E_BADARG, "%s: null pointer", what);
   SVR_CHECK(mode == 0 || (D > 0 && H > 0 && W > 0 && D < 1023 && H < 1023 && W < 1023), SVR_E_UNSUPPORTED,
             "%s: volume dims must be in [1, 1022]", what);
-  char *w = (char *)workspace;
-  uint64_t *keys_in = (uint64_t *)w;
-  w += align256(total * 8);
-  uint64_t *keys_out = (uint64_t *)w;
-  w += align256(total * 8);
-  int32_t *vals_in = (int32_t *)w;
-  w += align256(total * 4);
+  WsCursor c(workspace, 1);
+  const SortWs w = sort_layout(c, B, total);
   const int cbits = code_bits(mode, D, H, W);
   int bits = key_bits(B, cbits);
   size_t tmp = rocprim_temp_bytes(total, bits);
-  hipLaunchKernelGGL(sort_key_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, points, keys_in, vals_in, total, N,
+  hipLaunchKernelGGL(sort_key_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, points, w.keys_in, w.vals_in, total, N,
                      mode, D, H, W, ac, cbits);
-  hipError_t e = rocprim::radix_sort_pairs((void *)w, tmp, keys_in, keys_out, vals_in, order, (size_t)total, 0, bits, s);
+  hipError_t e = rocprim::radix_sort_pairs((void *)w.tmp, tmp, w.keys_in, w.keys_out, w.vals_in, order, (size_t)total, 0, bits, s);
   SVR_CHECK(e == hipSuccess, (int)e, "%s: radix sort failed: %s", what, hipGetErrorString(e));
   if (sorted_points)
     hipLaunchKernelGGL(permute_points_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, points, order,
@@ -175,7 +177,7 @@ hipError_t scan_sum_excl_u64(void *tmp, size_t tmp_bytes, const uint64_t *in, ui
 extern "C" int64_t svr_points_morton_order_workspace(int32_t B, int32_t N) {
   int64_t total = (int64_t)B * N;
   if (total <= 0) return 256;
-  return 2 * align256(total * 8) + align256(total * 4) + align256((int64_t)rocprim_temp_bytes(total, key_bits(B, 30))) + 256;
+  return ws_measure(sort_layout, B, total);
 }
 
 extern "C" int svr_points_morton_order(const float *points, int32_t *order, float *sorted_points, int32_t B, int32_t N,

@@ -249,22 +249,10 @@ struct Ws {
   size_t tmp_bytes;
 };
 
-Ws carve(void *ws, const Grid &G) {
-  char *w = (char *)ws;
-  Ws r;
-  r.counts = (uint64_t *)w;
-  w += align256(G.nblk * 8);
-  r.offs = (uint64_t *)w;
-  w += align256(G.nblk * 8);
-  r.list = (int32_t *)w;
-  w += align256(G.nblk * 4);
-  r.start = (int32_t *)w;
-  w += align256(G.nblk * 4);
-  r.sel = (uint8_t *)w;
-  w += align256(G.nblk);
-  r.tmp = w;
-  r.tmp_bytes = scan_sum_excl_u64_temp_bytes(G.nblk);
-  return r;
+Ws ws_layout(WsCursor &c, int64_t nblk) {   // the launchers have always used the caller's pointer as it is: base alignment 1
+  const size_t tmp_bytes = scan_sum_excl_u64_temp_bytes(nblk);
+  return {c.take<uint64_t>(nblk), c.take<uint64_t>(nblk), c.take<int32_t>(nblk), c.take<int32_t>(nblk), c.take<uint8_t>(nblk),
+          c.take<char>((int64_t)tmp_bytes), tmp_bytes};
 }
 
 #define SL_GRID(name)                                                                                                      \
@@ -280,8 +268,7 @@ extern "C" int64_t svr_sl_workspace_bytes(int32_t X, int32_t Y, int32_t Z, int32
     set_error("sl_workspace_bytes: bad lattice %d x %d x %d, block %d", X, Y, Z, s);
     return SVR_E_BADSHAPE;
   }
-  return 2 * align256(G.nblk * 8) + 2 * align256(G.nblk * 4) + align256(G.nblk) +
-         align256((int64_t)scan_sum_excl_u64_temp_bytes(G.nblk)) + 256;
+  return ws_measure(ws_layout, G.nblk);
 }
 
 extern "C" int svr_sl_coarse_points(const float *tx, const float *ty, const float *tz, int32_t X, int32_t Y, int32_t Z,
@@ -297,9 +284,9 @@ extern "C" int svr_sl_fill_seed(const float *coarse, int32_t X, int32_t Y, int32
                                 uint8_t *state, void *ws, int64_t ws_bytes, void *stream) {
   SL_GRID("sl_fill_seed");
   SVR_CHECK(coarse && field && state && ws, SVR_E_BADARG, "sl_fill_seed: null pointer");
-  SVR_CHECK(ws_bytes >= svr_sl_workspace_bytes(X, Y, Z, s), SVR_E_BADARG, "sl_fill_seed: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_sl_workspace_bytes(X, Y, Z, s));
-  const Ws w = carve(ws, G);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, G.nblk);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "sl_fill_seed: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sl_fill_kernel, dim3((unsigned)std::min<int64_t>(cdiv(G.np, kBlock), kFillBlocks)), dim3(kBlock), 0, st,
                      coarse, G, field);
@@ -313,7 +300,8 @@ extern "C" int svr_sl_select(int32_t X, int32_t Y, int32_t Z, int32_t s, int32_t
                              int64_t *totals, void *stream) {
   SL_GRID("sl_select");
   SVR_CHECK(state && ws && totals, SVR_E_BADARG, "sl_select: null pointer");
-  const Ws w = carve(ws, G);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, G.nblk);
   const hipStream_t st = (hipStream_t)stream;
   const dim3 blocks((unsigned)cdiv(G.nblk, kBlock));
   hipLaunchKernelGGL(sl_count_kernel, blocks, dim3(kBlock), 0, st, G, (int)(all != 0), state, w.sel, w.counts);
@@ -333,7 +321,8 @@ extern "C" int svr_sl_block_points(const float *tx, const float *ty, const float
             (long)G.nblk);
   if (n_blocks == 0) return SVR_OK;
   SVR_CHECK(tx && ty && tz && ws && pts, SVR_E_BADARG, "sl_block_points: null pointer");
-  const Ws w = carve(const_cast<void *>(ws), G);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, G.nblk);
   hipLaunchKernelGGL(sl_block_points_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)stream, tx, ty, tz, G,
                      w.list, w.start, pts);
   return launch_status("sl_block_points");
@@ -347,7 +336,8 @@ extern "C" int svr_sl_scatter(const float *vals, int32_t X, int32_t Y, int32_t Z
   SVR_CHECK(round >= 1 && round <= 255, SVR_E_BADARG, "sl_scatter: round %d outside [1, 255]", round);
   if (n_blocks == 0) return SVR_OK;
   SVR_CHECK(vals && ws && field && state, SVR_E_BADARG, "sl_scatter: null pointer");
-  const Ws w = carve(const_cast<void *>(ws), G);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, G.nblk);
   hipLaunchKernelGGL(sl_scatter_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, (hipStream_t)stream, vals, G, w.list,
                      w.start, (int)round, field, state);
   return launch_status("sl_scatter");
@@ -364,7 +354,8 @@ extern "C" int svr_sl_leak_check(const float *field, int32_t X, int32_t Y, int32
   SVR_CHECK(e == hipSuccess, (int)e, "sl_leak_check: memset failed: %s", hipGetErrorString(e));
   if (n_blocks == 0) return SVR_OK;
   SVR_CHECK(field && state && ws, SVR_E_BADARG, "sl_leak_check: null pointer");
-  const Ws w = carve(ws, G);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, G.nblk);
   hipLaunchKernelGGL(sl_leak_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, field, G, level, w.list, state, w.sel,
                      (unsigned long long *)(totals + 2));
   return launch_status("sl_leak");

@@ -151,13 +151,14 @@ __global__ __launch_bounds__(kBlock) void vc_finalise_kernel(int64_t V, uint32_t
   block_add_totals_u64<kBlock>(mine, 0, part, changed);  // every thread of the block arrives here
 }
 
-int64_t acc_bytes(int64_t V) { return align256(V * 16); }
+struct Ws { uint32_t *acc; unsigned long long *changed; };   // V rows of four words; two words: block_add_totals_u64's pair
+Ws ws_layout(WsCursor &c, int64_t V) { return {c.take<uint32_t>(4 * V), c.take<unsigned long long>(2)}; }
 
 }  // namespace
 
 extern "C" int64_t svr_vertex_color_workspace_bytes(int64_t V) {
   SVR_CHECK(V >= 0 && V < (1LL << 31), SVR_E_BADSHAPE, "vertex_color_workspace_bytes: V=%ld (need 0 <= V < 2^31)", (long)V);
-  return acc_bytes(V) + 256 + 256;  // the rows, the counter, the slack of align256
+  return ws_measure(ws_layout, V);
 }
 
 extern "C" int svr_vertex_color_sample(const float *verts, int64_t V, const float *consts, const float *depth, int32_t H, int32_t W,
@@ -185,12 +186,12 @@ extern "C" int svr_vertex_color_spread(const int32_t *faces, int64_t F, int64_t 
   if (passes) *passes = 0;
   if (V == 0 || F == 0 || max_passes == 0) return SVR_OK;
   SVR_CHECK(faces && colors && state && ws, SVR_E_BADARG, "vertex_color_spread: null pointer");
-  SVR_CHECK(ws_bytes >= svr_vertex_color_workspace_bytes(V), SVR_E_BADARG, "vertex_color_spread: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_vertex_color_workspace_bytes(V));
+  WsCursor c(ws);
+  const Ws w = ws_layout(c, V);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "vertex_color_spread: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   hipStream_t st = (hipStream_t)stream;
-  uint32_t *acc = align256<uint32_t>(ws);
-  unsigned long long *changed = (unsigned long long *)((char *)acc + acc_bytes(V));  // two words: block_add_totals_u64's pair
-  hipError_t e = hipMemsetAsync(acc, 0, (size_t)acc_bytes(V) + 256, st);             // once per call; the passes keep it zero
+  // both pieces, once per call; the passes keep them zero
+  hipError_t e = hipMemsetAsync(w.acc, 0, (size_t)(c.bytes() - WsCursor::kSlack), st);
   SVR_CHECK(e == hipSuccess, (int)e, "vertex_color_spread: memset failed: %s", hipGetErrorString(e));
   // a pass that changes anything colours a vertex, so the fixed point comes within V passes; one more shows it
   const int64_t limit = max_passes < 0 || max_passes > V + 1 ? V + 1 : max_passes;
@@ -199,14 +200,14 @@ extern "C" int svr_vertex_color_spread(const int32_t *faces, int64_t F, int64_t 
   while (done < limit) {
     const int64_t n = limit - done < check_every ? limit - done : check_every;
     for (int64_t p = 0; p < n; ++p) {
-      hipLaunchKernelGGL(vc_accumulate_kernel, dim3((unsigned)cdiv(F, kBlock)), dim3(kBlock), 0, st, faces, F, V, colors, state, acc);
-      hipLaunchKernelGGL(vc_finalise_kernel, dim3((unsigned)cdiv(V, kBlock)), dim3(kBlock), 0, st, V, acc, colors, state, changed);
+      hipLaunchKernelGGL(vc_accumulate_kernel, dim3((unsigned)cdiv(F, kBlock)), dim3(kBlock), 0, st, faces, F, V, colors, state, w.acc);
+      hipLaunchKernelGGL(vc_finalise_kernel, dim3((unsigned)cdiv(V, kBlock)), dim3(kBlock), 0, st, V, w.acc, colors, state, w.changed);
     }
     if (int rc = launch_status("vertex_color_spread")) return rc;
     done += n;
     if (done >= limit) break;  // nothing left to decide
     unsigned long long now = 0;
-    e = hipMemcpyAsync(&now, changed, sizeof(now), hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(&now, w.changed, sizeof(now), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     SVR_CHECK(e == hipSuccess, (int)e, "vertex_color_spread: reading the counter failed: %s", hipGetErrorString(e));
     if (now == seen) break;  // none of the last n passes changed a vertex: neither will any later one

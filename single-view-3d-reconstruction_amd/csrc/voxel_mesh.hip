@@ -152,18 +152,9 @@ struct Ws {
   size_t tmp_bytes;
 };
 
-Ws carve(void *ws, int64_t n) {
-  char *w = (char *)ws;
-  Ws r;
-  r.counts = (uint64_t *)w;
-  w += align256(n * 8);
-  r.offs = (uint64_t *)w;
-  w += align256(n * 8);
-  r.flags = (uint8_t *)w;
-  w += align256(n);
-  r.tmp = w;
-  r.tmp_bytes = scan_sum_excl_u64_temp_bytes(n);
-  return r;
+Ws ws_layout(WsCursor &c, int64_t n) {   // the launchers have always used the caller's pointer as it is: base alignment 1
+  const size_t tmp_bytes = scan_sum_excl_u64_temp_bytes(n);
+  return {c.take<uint64_t>(n), c.take<uint64_t>(n), c.take<uint8_t>(n), c.take<char>((int64_t)tmp_bytes), tmp_bytes};
 }
 
 // ---- depth-map planes ---------------------------------------------------------------------------------------------
@@ -224,7 +215,7 @@ extern "C" int64_t svr_voxel_mesh_workspace_bytes(int32_t X, int32_t Y, int32_t 
     return SVR_E_BADSHAPE;
   }
   if (empty(L)) return 256;
-  return 2 * align256(L.n * 8) + align256(L.n) + align256((int64_t)scan_sum_excl_u64_temp_bytes(L.n)) + 256;
+  return ws_measure(ws_layout, L.n);
 }
 
 extern "C" int svr_voxel_mesh_count(const float *field, int32_t X, int32_t Y, int32_t Z, double threshold, void *ws, int64_t ws_bytes,
@@ -238,9 +229,9 @@ extern "C" int svr_voxel_mesh_count(const float *field, int32_t X, int32_t Y, in
   SVR_CHECK(e == hipSuccess, (int)e, "voxel_mesh_count: memset failed: %s", hipGetErrorString(e));
   if (empty(L)) return SVR_OK;
   SVR_CHECK(field && ws, SVR_E_BADARG, "voxel_mesh_count: null pointer");
-  SVR_CHECK(ws_bytes >= svr_voxel_mesh_workspace_bytes(X, Y, Z), SVR_E_BADARG, "voxel_mesh_count: workspace of %ld bytes, need %ld",
-            (long)ws_bytes, (long)svr_voxel_mesh_workspace_bytes(X, Y, Z));
-  const Ws w = carve(ws, L.n);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, L.n);
+  SVR_CHECK(ws_bytes >= c.bytes(), SVR_E_BADARG, "voxel_mesh_count: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)c.bytes());
   const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(L.n, kBlock), kClassifyBlocks);
   hipLaunchKernelGGL(vm_classify_kernel, dim3(blocks), dim3(kBlock), 0, s, field, L, threshold, w.counts, w.flags,
                      (unsigned long long *)totals);
@@ -260,7 +251,8 @@ extern "C" int svr_voxel_mesh_emit(const float *field, int32_t X, int32_t Y, int
             X, Y, Z);
   if (empty(L)) return SVR_OK;
   SVR_CHECK(ws && verts && faces, SVR_E_BADARG, "voxel_mesh_emit: null pointer");
-  const Ws w = carve(ws, L.n);
+  WsCursor c(ws, 1);
+  const Ws w = ws_layout(c, L.n);
   hipLaunchKernelGGL(vm_emit_kernel, dim3((unsigned)cdiv(L.n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, L, w.offs, w.flags, verts,
                      faces);
   return launch_status("vm_emit");
