@@ -33,6 +33,7 @@ extern "C" {
 #define SVR_E_UNSUPPORTED (-4)
 #define SVR_E_IO (-5)
 #define SVR_E_NOTFOUND (-6)
+#define SVR_E_INTERNAL (-7) /* a bound that the design rules out was reached; nothing was written out of bounds */
 
 #define SVR_MAX_LEVELS 6
 
@@ -1058,6 +1059,55 @@ int svr_mesh_filter_count(const int32_t *faces, int64_t F, int64_t V, const int3
                           void *ws, int64_t ws_bytes, int64_t *totals, void *stream);
 int svr_mesh_filter_emit(const float *verts, int64_t V, const int32_t *faces, int64_t F, void *ws, int64_t ws_bytes, float *out_verts,
                          int32_t *out_faces, int32_t *vertex_index, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Mesh simplification by vertex clustering, Rossignac-Borrel (no reference op: the reference writes raw marching-cubes output,
+ * every triangle smaller than a lattice cell; util/mesh_simplify.py drives this, tests/mesh_simplify_oracle.py restates it in
+ * numpy).  Errors, ownership and streams as for svr_mc_*.  Wherever threads meet the values are integers
+ * (cells, vertex indices, int64 fixed-point sums), so every output is the same bits on every run, whichever way the atomics
+ * arrive.  The unit is built with -ffp-contract=off.
+ *   verts: (V, 3) float32, faces: (F, 3) int32, on the device, 0 <= V, F < 2^31 (else SVR_E_BADSHAPE).
+ *   cell: the cluster edge, a float32, finite with 2^-10 <= cell <= 2^16 (else SVR_E_BADARG, and nothing is launched).
+ *   The rule:
+ *     1. a vertex is CLUSTERABLE iff its three coordinates are finite and each |v_a| < 2^16.  The others belong to no cluster
+ *        and are counted (`bad`).
+ *     2. its CELL is q_a = floor((double)v_a / (double)cell), computed in float64; |q_a| < 2^27 by the limits, an int32.  Two
+ *        clusterable vertices are in one CLUSTER iff their (q_x, q_y, q_z) are equal.
+ *     3. a cluster's ROOT is its smallest member vertex index; clusters are numbered in ascending order of root.
+ *     4. POSITION: s_a(i) = (int64) rint((double)v_a * 65536), ties to even (the product is exact); S_a = the int64 sum over
+ *        the members and n = their number (|S_a| < 2^63 by the limits); the cluster's vertex is
+ *        (float)(((double)S_a / (double)n) / 65536.0).  A cluster with n == 1 keeps the three words of its one vertex, copied:
+ *        a cell no larger than the vertex spacing is the identity on positions, bit for bit.
+ *     5. a face is VALID iff its three indices lie in [0, V) and name clusterable vertices (the indices are compared before
+ *        any of them addresses memory); its MAPPED triple is the three cluster numbers; it is DEGENERATE iff two of them are
+ *        equal.
+ *     6. the CANONICAL triple is the mapped triple rotated so that its smallest number comes first (a rotation keeps the
+ *        orientation).  Two non-degenerate faces are DUPLICATES iff their canonical triples are equal; of a set of duplicates
+ *        only the face with the smallest index is kept.  (A, B, C) and (A, C, B) are no duplicates: both stay, a two-sided sheet.
+ *     7. OUTPUT: a face is kept iff it is valid, not degenerate and the first of its duplicates; a cluster is kept iff a kept
+ *        face names it.  Kept clusters keep their relative order and are renumbered 0 .. V'-1; kept faces keep their relative
+ *        order and their own rotation, with the new numbers.  vertex_cluster[i] (V, int32) = the output vertex of i's cluster,
+ *        -1 if i is not clusterable or its cluster was dropped; cluster_size[j] (V', int32) = n.  Any per-vertex attribute can
+ *        be pooled by the caller over vertex_cluster.
+ *   Consequences: every member moves by less than `cell` per axis (its cluster's vertex lies in the closed hull of the cell's
+ *   members), plus the fixed-point step (2^-17 per member, so at most that for the mean) and half a float32 ulp of the result.
+ *   A closed input can lose manifoldness where a feature is thinner than a cell (two sheets collapse into a two-sided sheet or
+ *   an edge shared by four faces): simplification trades topology for size, and nothing here repairs it.
+ *   ws: svr_mesh_simplify_workspace_bytes(V, F) device bytes (negative = SVR_E_BADSHAPE); needs no zeroing, and must be the
+ *   same buffer, untouched, between svr_mesh_simplify_count and svr_mesh_simplify_emit.
+ *   svr_mesh_simplify_count: totals (DEVICE int64 x 3) = V', F', bad.  V == 0 or F == 0: (0, 0, bad), ws may be null.
+ *     uniform_path: nonzero lets a wave whose vertices share one cluster fold its sums before it issues atomics; 0 issues them
+ *     per lane.  The outputs are the same bits either way.  Reading the totals is the caller's one host synchronisation.  The
+ *     call is asynchronous, so the one failure it can only meet on the device -- a hash set without an empty slot, which a
+ *     half-empty table rules out -- arrives in the totals: all three hold SVR_E_INTERNAL, and no kernel has left its buffers.
+ *   svr_mesh_simplify_emit: out_verts (V', 3), out_faces (F', 3), cluster_size (V') as the totals size them (not touched, and
+ *     may be null, when the totals are 0), vertex_cluster (V).  V == 0 or F == 0: only vertex_cluster is filled, with -1.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_mesh_simplify_workspace_bytes(int64_t V, int64_t F);
+int svr_mesh_simplify_count(const float *verts, int64_t V, const int32_t *faces, int64_t F, float cell, void *ws, int64_t ws_bytes,
+                            int32_t uniform_path, int64_t *totals, void *stream);
+int svr_mesh_simplify_emit(const float *verts, int64_t V, const int32_t *faces, int64_t F, void *ws, int64_t ws_bytes, float *out_verts,
+                           int32_t *out_faces, int32_t *vertex_cluster, int32_t *cluster_size, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,

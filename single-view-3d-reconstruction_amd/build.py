@@ -37,6 +37,7 @@ SOURCES = {
     "raycast.hip": ["-ffp-contract=off"],
     "vertex_color.hip": ["-ffp-contract=off"],
     "mesh_components.hip": ["-ffp-contract=off"],
+    "mesh_simplify.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "io_npz.cpp": [],
     "io_df.cpp": [],

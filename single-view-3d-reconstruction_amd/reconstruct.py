@@ -32,15 +32,20 @@ uint8 and `color_state` (V,) uint8 (util/mesh_color.py).  
 
 ``python -m svr_amd.reconstruct --checkpoint C (--rgb a.png [b.png ...] | --distance d.exr) --out DIR [--inf_res n]
 [--block s] [--space grid|normalized|camera] [--flip] [--color [--color_bias metres]] [--keep_largest]
-[--min_component_faces N] [--min_component_extent CELLS] [--drop_unseen]`` prints one line per view: the written
-paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour state.
+[--min_component_faces N] [--min_component_extent CELLS] [--drop_unseen] [--simplify CELLS]`` prints one line per view:
+the written paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour state.
 
 ``clean(keep_largest=False, min_faces=0, min_extent=0.0, drop_unseen=False)`` drops connected components of the predicted
 mesh, the floaters an occupancy network leaves beside the surface (util/mesh_clean.py), and keeps
 `components` and `kept`.  Nothing calls it by default.  On the command line the size criteria (``--keep_largest``,
 ``--min_component_faces``, ``--min_component_extent``) run first; ``--drop_unseen`` (needs ``--color``) then colours the mesh
 and drops the components the camera sees no vertex of; ``--color`` finally colours the mesh that is written.  With any of
-the four the line ends in ``components=C kept=K``: the components of the raw mesh and how many of them were written."""
+the four the line ends in ``components=C kept=K``: the components of the raw mesh and how many of them were written.
+
+``simplify(cell=1.0)`` merges the vertices inside each cube of `cell` grid cells per edge into their mean and drops the faces
+that collapse or repeat (util/mesh_simplify.py); it keeps `vertex_cluster` and forgets the colours.
+Nothing calls it by default.  ``--simplify CELLS`` runs it after the component filters and before ``--color`` colours the
+mesh that is written, so ``--drop_unseen`` still decides on the unsimplified mesh; the counts printed are the written mesh's."""
 import argparse
 import os
 from pathlib import Path
@@ -72,6 +77,7 @@ class Reconstruction:
         self.pixel_map = IDENTITY_MAP if pixel_map is None else tuple(pixel_map)      # depth-map pixel -> image position
         self.colors = self.color_state = None           # colorize()'s results
         self.components = self.kept = None              # clean()'s: the statistics before the filter, the flag per component
+        self.vertex_cluster = None                      # simplify()'s: where each vertex of the mesh before it went
 
     def _camera_consts(self):
         K = self._intrinsic if self._intrinsic is not None else get_intrinsic()
@@ -157,6 +163,22 @@ class Reconstruction:
         self.vertices, self.faces = vertices, faces
         if self.colors is not None:
             self.colors, self.color_state = self.colors[index.long()], self.color_state[index.long()]
+        return self
+
+    def simplify(self, cell=1.0):
+        """Simplify the predicted mesh by vertex clustering (util.mesh_simplify): the vertices inside
+        one cube of `cell` grid cells per edge (multiplied by inf_res here: the vertices are lattice indices) become one vertex
+        at their mean, and the faces that collapse or repeat are dropped.  Replaces `vertices` and `faces`, stores
+        `vertex_cluster` (per vertex of the mesh BEFORE the call, its new vertex or -1) and returns self.  `colors` and
+        `color_state` are reset to None: a cluster's vertex is a new position, so ``save(color=True)`` (or ``colorize()``)
+        colours the simplified mesh from the image there instead of pooling the old colours.  `components` and `kept` stay:
+        they describe the raw mesh.  A mesh without faces is returned unchanged."""
+        from .util.mesh_simplify import simplify_mesh
+        if self.faces is None or int(self.faces.shape[0]) == 0:
+            return self
+        out = simplify_mesh(self.vertices, self.faces, float(cell) * self._inf_res)
+        self.vertices, self.faces, self.vertex_cluster = out.vertices, out.faces, out.vertex_cluster
+        self.colors = self.color_state = None
         return self
 
     def save(self, prefix, space="grid", color=False):
@@ -306,11 +328,15 @@ def main(argv=None):
     parser.add_argument("--min_component_extent", type=float, default=None, metavar="CELLS",
                         help="drop components whose bounding-box diagonal is shorter than CELLS grid cells")
     parser.add_argument("--drop_unseen", action="store_true", help="drop components the camera sees no vertex of (needs --color)")
+    parser.add_argument("--simplify", type=float, default=None, metavar="CELLS",
+                        help="merge the vertices inside each cube of CELLS grid cells per edge (vertex clustering; default: off)")
     args = parser.parse_args(argv)
     if args.color and args.distance:
         parser.error("--color needs --rgb: a distance map carries no colours")
     if args.drop_unseen and not args.color:
         parser.error("--drop_unseen needs --color: what the camera sees is decided while colouring")
+    if args.simplify is not None and not args.simplify > 0:
+        parser.error("--simplify needs a positive number of grid cells")
     by_size = args.keep_largest or args.min_component_faces is not None or args.min_component_extent is not None
     cleaning = by_size or args.drop_unseen
     rec =Reconstructor.from_checkpoint(args.checkpoint, inf_res=args.inf_res, skip_unet=True if args.distance else None,
@@ -332,6 +358,8 @@ def main(argv=None):
                 view.clean(drop_unseen=True)
                 total = view.components.count if total is None else total
             parts = f" components={total} kept={int(view.kept.sum())}"
+        if args.simplify is not None:                     # after the filters, which saw the raw mesh and its colour states
+            view.simplify(args.simplify)
         if args.color:                                    # on the mesh that is written
             _, state = view.colorize(bias=args.color_bias)
             n = torch.bincount(state.long(), minlength=3).tolist()
