@@ -1110,6 +1110,51 @@ int svr_mesh_simplify_emit(const float *verts, int64_t V, const int32_t *faces, 
                            int32_t *out_faces, int32_t *vertex_cluster, int32_t *cluster_size, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Mesh smoothing, Taubin's lambda|mu iteration by an all-integer rule (no reference op: the reference writes raw marching-cubes
+ * output, terraced where the network's field is near-binary; util/mesh_smooth.py drives this, tests/mesh_smooth_oracle.py
+ * restates it in numpy).  Errors, ownership and streams as for svr_mc_*.  The iteration is all integers,
+ * so every output bit is independent of the order of atomics and of FP contraction; the only floating-point operations are
+ * the two conversions at either end.  The unit is built with -ffp-contract=off.
+ *   verts: (V, 3) float32, faces: (F, 3) int32, on the device, 0 <= V < 2^31, 0 <= F <= 2^28 (else SVR_E_BADSHAPE).
+ *   iterations: 0 <= n <= 1024.  lam, mu: float32 with 0 < lam <= 1 and -1 <= mu <= 0 after the rounding of point 1; mu = 0
+ *   is plain Laplacian smoothing, one pass per iteration.  fix_boundary: nonzero keeps the vertices of point 5 in place.
+ *   Anything else is SVR_E_BADARG, and so are out_verts overlapping verts (a pass reads every old position) and a workspace
+ *   that is too small; every refusal happens before anything is enqueued.
+ *   The rule:
+ *     1. the step weights are fixed point: L_lam = rint((double)lam * 65536) and L_mu = rint((double)mu * 65536), integers,
+ *        with 1 <= L_lam <= 65536 and -65536 <= L_mu <= 0.
+ *     2. a vertex is USABLE iff its three coordinates are finite and each |v_a| < 2^16 (svr_mesh_simplify's "clusterable").
+ *     3. a face is VALID iff its three indices lie in [0, V), are pairwise distinct, and name usable vertices (the indices are
+ *        compared before any of them addresses memory).  Repeated valid faces each count.
+ *     4. every valid face (a, b, c) gives a the ENTRY (next b, prev c), b the entry (c, a) and c the entry (a, b); m_i is the
+ *        number of entries of vertex i.
+ *     5. i is INTERIOR iff for every j the number of its entries with next = j equals the number with prev = j (equality of
+ *        multisets, exact): every edge that leaves i on one face comes back on another.
+ *     6. STATE (uint8), the first that applies: 3 = not usable; 1 = m_i is 0; 2 = fix_boundary is set and i is not interior;
+ *        0 = movable.
+ *     7. every usable vertex gets q_a = (int64) rint((double)v_a * 65536) per axis, ties to even (the product is exact).
+ *     8. n times: one Jacobi pass with L = L_lam, then one with L = L_mu (omitted when L_mu = 0).  A pass reads the old q of
+ *        every vertex and gives each movable vertex i, per axis,
+ *          S = the sum over i's entries of (q[next] + q[prev]),  c = 2 m_i,
+ *          mean = floor((S + m_i) / c)            -- floor division; S + m_i can be negative,
+ *          step = (L * (mean - q) + 32768) >> 16  -- an arithmetic shift (floor),
+ *          q' = clamp(q + step, -2^33, 2^33).
+ *        The other vertices keep q.  |S + m_i| <= 2^29 * 2^33 + 2^28 < 2^63 and |L * (mean - q)| < 2^52.
+ *     9. OUTPUT: a movable vertex, when n > 0, becomes (float)((double)q_a / 65536.0); every other vertex keeps its three
+ *        input words, NaN payloads included; n = 0 is the identity, bit for bit.  Faces are not touched.  state (V, uint8) as
+ *        in 6; counts (DEVICE int64 x 4) = the number of vertices in states 0, 1, 2, 3.
+ *   Consequences: a negative mu extrapolates, so a coordinate can leave +-2^16 although every input lies inside; the clamp
+ *   keeps the sums inside int64, so an output can be as large as +-131072.0 (= 2^33 / 2^16), and never larger.  On a closed
+ *   manifold every vertex is interior; where the lattice border cuts a surface open, the rim is what fix_boundary holds.
+ *   ws: svr_mesh_smooth_workspace_bytes(V, F) device bytes (negative = SVR_E_BADSHAPE); needs no zeroing.
+ *   svr_mesh_smooth is asynchronous and synchronises nothing with the host: the output sizes are known.  V == 0: only
+ *   counts is written.  F == 0: out_verts is a copy, every state is 1 or 3, ws may be null.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_mesh_smooth_workspace_bytes(int64_t V, int64_t F);
+int svr_mesh_smooth(const float *verts, int64_t V, const int32_t *faces, int64_t F, int32_t iterations, float lam, float mu,
+                    int32_t fix_boundary, void *ws, int64_t ws_bytes, float *out_verts, uint8_t *state, int64_t *counts, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * The files are read on the host (svr_df_* / svr_npz_*: File formats, below).

@@ -189,6 +189,8 @@ SIGNATURES = {
     "svr_mesh_simplify_workspace_bytes": (I64, [I64, I64]),
     "svr_mesh_simplify_count": (C.c_int, [P, I64, P, I64, F32, P, I64, I32, P, P]),
     "svr_mesh_simplify_emit": (C.c_int, [P, I64, P, I64, P, I64, P, P, P, P, P]),
+    "svr_mesh_smooth_workspace_bytes": (I64, [I64, I64]),
+    "svr_mesh_smooth": (C.c_int, [P, I64, P, I64, I32, F32, F32, I32, P, I64, P, P, P, P]),
     "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),

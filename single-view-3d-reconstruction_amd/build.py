@@ -38,6 +38,7 @@ SOURCES = {
     "vertex_color.hip": ["-ffp-contract=off"],
     "mesh_components.hip": ["-ffp-contract=off"],
     "mesh_simplify.hip": ["-ffp-contract=off"],
+    "mesh_smooth.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "io_npz.cpp": [],
     "io_df.cpp": [],

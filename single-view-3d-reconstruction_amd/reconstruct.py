@@ -32,7 +32,8 @@ uint8 and `color_state` (V,) uint8 (util/mesh_color.py).  
 
 ``python -m svr_amd.reconstruct --checkpoint C (--rgb a.png [b.png ...] | --distance d.exr) --out DIR [--inf_res n]
 [--block s] [--space grid|normalized|camera] [--flip] [--color [--color_bias metres]] [--keep_largest]
-[--min_component_faces N] [--min_component_extent CELLS] [--drop_unseen] [--simplify CELLS]`` prints one line per view:
+[--min_component_faces N] [--min_component_extent CELLS] [--drop_unseen] [--smooth ITERATIONS [--smooth_lambda L]
+[--smooth_mu M]] [--simplify CELLS]`` prints one line per view:
 the written paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour state.
 
 ``clean(keep_largest=False, min_faces=0, min_extent=0.0, drop_unseen=False)`` drops connected components of the predicted
@@ -45,7 +46,12 @@ the four the line ends in ``components=C kept=K``: the components of the raw mes
 ``simplify(cell=1.0)`` merges the vertices inside each cube of `cell` grid cells per edge into their mean and drops the faces
 that collapse or repeat (util/mesh_simplify.py); it keeps `vertex_cluster` and forgets the colours.
 Nothing calls it by default.  ``--simplify CELLS`` runs it after the component filters and before ``--color`` colours the
-mesh that is written, so ``--drop_unseen`` still decides on the unsimplified mesh; the counts printed are the written mesh's."""
+mesh that is written, so ``--drop_unseen`` still decides on the unsimplified mesh; the counts printed are the written mesh's.
+
+``smooth(iterations=10, lam=0.5, mu=-0.53, fix_boundary=True)`` moves the vertices by Taubin's lambda|mu iteration
+(util/mesh_smooth.py) and keeps `smooth_state`; faces, components, clusters and colours stay.  Nothing
+calls it by default.  ``--smooth ITERATIONS [--smooth_lambda L] [--smooth_mu M]`` runs it after the component flags and before
+``--simplify``, so the clusters average smoothed positions."""
 import argparse
 import os
 from pathlib import Path
@@ -78,6 +84,7 @@ class Reconstruction:
         self.colors = self.color_state = None           # colorize()'s results
         self.components = self.kept = None              # clean()'s: the statistics before the filter, the flag per component
         self.vertex_cluster = None                      # simplify()'s: where each vertex of the mesh before it went
+        self.smooth_state = None                        # smooth()'s: which vertices it moved
 
     def _camera_consts(self):
         K = self._intrinsic if self._intrinsic is not None else get_intrinsic()
@@ -179,6 +186,22 @@ class Reconstruction:
         out = simplify_mesh(self.vertices, self.faces, float(cell) * self._inf_res)
         self.vertices, self.faces, self.vertex_cluster = out.vertices, out.faces, out.vertex_cluster
         self.colors = self.color_state = None
+        return self
+
+    def smooth(self, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True):
+        """Smooth the predicted mesh with Taubin's lambda|mu iteration (util.mesh_smooth): takes the
+        terraces out of the marching-cubes surface of a near-binary field without shrinking it.  With `fix_boundary` the rims
+        the lattice border cut open stay on the border.  Replaces `vertices`, stores `smooth_state` (per vertex: 0 moved, 1 in
+        no face, 2 held on a boundary, 3 not usable) and returns self.  `faces`, `components`, `kept`, `vertex_cluster`,
+        `colors` and `color_state` stay: the indices are unchanged and a position moves by less than a cell or so, so the
+        colours are still those of the image at (nearly) that place; a second ``colorize()`` resamples them at the smoothed
+        positions.  `smooth_state`, like `vertex_cluster`, describes the mesh the call saw: a later ``clean()`` or ``simplify()``
+        renumbers the vertices and leaves it as it is.  A mesh without faces is returned unchanged."""
+        from .util.mesh_smooth import smooth_mesh
+        if self.faces is None or int(self.faces.shape[0]) == 0:
+            return self
+        out = smooth_mesh(self.vertices, self.faces, iterations=iterations, lam=lam, mu=mu, fix_boundary=fix_boundary)
+        self.vertices, self.smooth_state = out.vertices, out.state
         return self
 
     def save(self, prefix, space="grid", color=False):
@@ -330,7 +353,13 @@ def main(argv=None):
     parser.add_argument("--drop_unseen", action="store_true", help="drop components the camera sees no vertex of (needs --color)")
     parser.add_argument("--simplify", type=float, default=None, metavar="CELLS",
                         help="merge the vertices inside each cube of CELLS grid cells per edge (vertex clustering; default: off)")
+    parser.add_argument("--smooth", type=int, default=None, metavar="ITERATIONS",
+                        help="Taubin lambda|mu smoothing of the mesh, ITERATIONS times, rims on the lattice border held (default: off)")
+    parser.add_argument("--smooth_lambda", type=float, default=0.5, help="the shrinking step of --smooth, 0 < L <= 1")
+    parser.add_argument("--smooth_mu", type=float, default=-0.53, help="the inflating step of --smooth, -1 <= M <= 0 (0: plain Laplacian)")
     args = parser.parse_args(argv)
+    if args.smooth is not None and not 0 < args.smooth <= 1024:
+        parser.error("--smooth needs a positive number of iterations, 1024 at the most")
     if args.color and args.distance:
         parser.error("--color needs --rgb: a distance map carries no colours")
     if args.drop_unseen and not args.color:
@@ -358,6 +387,8 @@ def main(argv=None):
                 view.clean(drop_unseen=True)
                 total = view.components.count if total is None else total
             parts = f" components={total} kept={int(view.kept.sum())}"
+        if args.smooth is not None:                       # after the filters: floaters are dropped, not smoothed
+            view.smooth(args.smooth, lam=args.smooth_lambda, mu=args.smooth_mu)
         if args.simplify is not None:                     # after the filters, which saw the raw mesh and its colour states
             view.simplify(args.simplify)
         if args.color:                                    # on the mesh that is written

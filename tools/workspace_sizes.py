@@ -99,6 +99,7 @@ def table(L, ops):
     add("svr_vertex_color_workspace_bytes", [(0,), (1,), (257,), (100000,), (2 ** 31 - 1,), (-1,), (2 ** 31,)])
     add("svr_mesh_components_workspace_bytes", MESHES)
     add("svr_mesh_simplify_workspace_bytes", MESHES)
+    add("svr_mesh_smooth_workspace_bytes", MESHES + [(100000, 2 ** 28), (0, 2 ** 28 + 1)])
     add("svr_depth_head_workspace", [(8, 256, 256), (8, 240, 320), (1, 1, 1)])
     return rows
 
@@ -107,7 +108,7 @@ def sizes(lib_path):
     from svr_amd import _lib as L, ops   # the binding's struct mirrors and signatures (the header is the same for both)
     lib = C.CDLL(lib_path or L.LIB_PATH)
     names = sorted(n for n, (res, _) in L.SIGNATURES.items() if "workspace" in n and res is L.I64)
-    assert len(names) == 38, names
+    assert len(names) == 39, names
     names.append("svr_conv2d_planes_bytes")         # the UNet's weight planes: the one multi-piece buffer not called a workspace
     for n in names:
         getattr(lib, n).restype, getattr(lib, n).argtypes = L.SIGNATURES[n]
