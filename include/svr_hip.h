@@ -482,6 +482,27 @@ int svr_conv3d_k3_bwd_weight_f16x3(const float *in, const float *dout, float *dW
 #define SVR_CONV_FWD_BF16X6 3
 int svr_conv3d_k3_variant(int32_t op, int32_t B, int32_t D, int32_t H, int32_t Wd, int32_t Ci, int32_t Co, int32_t *ck,
                           int32_t *tn, int32_t *vt, int32_t *persistent, int64_t *workgroup_rows);
+/* Which kernel a 3x3x3 weight-gradient entry point runs for a shape (each launcher asks the same function).  Host only: no
+ * device memory is touched, callable without a GPU.  op = SVR_CONV_BWD_WEIGHT_*: F32 = svr_conv3d_k3_bwd_weight, F16X3S =
+ * svr_conv3d_k3_bwd_weight_f16x3, BF16X3 = svr_conv3d_k3_bwd_weight_bf16x3 and its _param form.  Outputs (each may be NULL):
+ *   kernel: SVR_WGRAD_*.  The f32 entry: C1_CO16_LDS (Ci == 1, Co == 16, W <= 128: input rows in LDS), C1_CO16 (wider rows),
+ *     C1 (Ci == 1, other Co <= 32), BRICK (Ci, Co % 4 == 0).  The split entries: WS_PAIR / WS = the wave-specialised kernel
+ *     (paired-row tiles for Ci <= 16) where every workgroup gets 8 bricks or more, X3 = the 8-wave kernel otherwise;
+ *   parts: workgroups (per 32 x 32 channel-tile pair for BRICK / WS_PAIR / WS / X3) among which the volume is dealt;
+ *   max_bricks_per_part: 4x4x8-voxel bricks the busiest of them walks (1 for the Ci == 1 kernels: one chunk of rows each).
+ * Returns what the entry point returns for the shape (SVR_E_BADSHAPE / SVR_E_UNSUPPORTED), SVR_E_BADARG for an unknown op.  */
+#define SVR_CONV_BWD_WEIGHT_F32 0
+#define SVR_CONV_BWD_WEIGHT_F16X3S 1
+#define SVR_CONV_BWD_WEIGHT_BF16X3 2
+#define SVR_WGRAD_C1_CO16_LDS 0
+#define SVR_WGRAD_C1_CO16 1
+#define SVR_WGRAD_C1 2
+#define SVR_WGRAD_BRICK 3
+#define SVR_WGRAD_WS_PAIR 4
+#define SVR_WGRAD_WS 5
+#define SVR_WGRAD_X3 6
+int svr_conv3d_k3_bwd_weight_variant(int32_t op, int32_t B, int32_t D, int32_t H, int32_t W, int32_t Ci, int32_t Co,
+                                     int32_t *kernel, int32_t *parts, int64_t *max_bricks_per_part);
 
 /* ---------------------------------------------------------------------------------------
  * BatchNorm3d (training or eval) + MaxPool3d(2), channels-last

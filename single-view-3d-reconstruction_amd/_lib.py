@@ -125,6 +125,7 @@ SIGNATURES = {
     "svr_conv3d_k3_bwd_data_f16x3": (C.c_int, [P, P, P, I32, I32, I32, I32, I32, I32, C.c_int, P, P, P, P, P]),
     "svr_conv3d_k3_bwd_weight_f16x3": (C.c_int, [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P, P, P]),
     "svr_conv3d_k3_variant": (C.c_int, [I32, I32, I32, I32, I32, I32, I32, P, P, P, P, P]),
+    "svr_conv3d_k3_bwd_weight_variant": (C.c_int, [I32, I32, I32, I32, I32, I32, I32, P, P, P]),
     "svr_bn_stats_workspace": (I64, [I64, I32]),
     "svr_bn_stats": (C.c_int, [P, P, I64, I32, P, P]),
     "svr_bn_stats_finalize": (C.c_int, [P, P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, P]),

@@ -54,6 +54,12 @@ void conv3d_bwd_weight_reduce_launch(const float *slab, float *dWp, int Ci, int 
                                      hipStream_t s, int param_layout, const float *dbpart, float *db, int dbparts);
 void conv3d_c1_wgrad_reduce_launch(const float *slab, float *dWp, int Co, int parts, int param_layout, const float *dbpart,
                                    float *db, hipStream_t s);
+// conv3d.hip / conv3d_bwdw_bf16.hip: which kernel (SVR_WGRAD_*) a 3x3x3 weight-gradient entry point runs for a shape, with how
+// many workgroups per channel-tile pair (parts) and how many bricks the busiest of them walks (per_part).  Host arithmetic only;
+// each launcher asks its own function, svr_conv3d_k3_bwd_weight_variant exports both.  Returns SVR_OK or the entry point's refusal.
+struct WgradVariant { int kernel, parts; int64_t per_part; };
+int conv3d_bwd_weight_f32_variant(int B, int D, int H, int W, int Ci, int Co, WgradVariant *v);
+int conv3d_bwd_weight_x3_variant(int B, int D, int H, int W, int Ci, int Co, WgradVariant *v);
 // sort.hip: stable 32-bit key / value radix sort (rocPRIM)
 size_t sort_pairs_u32_temp_bytes(int64_t n, int bits);
 hipError_t sort_pairs_u32(void *tmp, size_t tmp_bytes, const uint32_t *kin, uint32_t *kout, const int32_t *vin, int32_t *vout,

@@ -788,6 +788,31 @@ int check_shape(int B, int D, int H, int W, int Ci, int Co) {
 }  // namespace
 
 namespace svr {
+// The kernel choice of svr_conv3d_k3_bwd_weight, from the shape alone (svr_conv3d_k3_bwd_weight_variant exports it; the
+// launcher below asks this function, so the two cannot drift).  parts = workgroups = partial slabs
+// (per channel-tile pair for the brick kernel); per_part = bricks the busiest workgroup walks (the Ci == 1 kernels take
+// one chunk of rows each: 1).
+int conv3d_bwd_weight_f32_variant(int B, int D, int H, int W, int Ci, int Co, WgradVariant *v) {
+  if (int rc = check_shape(B, D, H, W, Ci, Co)) return rc;
+  v->per_part = 1;
+  if (Ci == 1) {
+    SVR_CHECK(Co <= 32, SVR_E_UNSUPPORTED, "conv3d_bwd_weight: Ci=1 needs Co<=32 (got %d)", Co);
+    const int64_t nrows = (int64_t)B * D * H;
+    if (Co == 16 && W <= 128) {   // the A operand from LDS: one workgroup per 16-row y block of one z plane
+      v->kernel = SVR_WGRAD_C1_CO16_LDS;
+      v->parts = B * D * (int)cdiv(H, C1L_ROWS);
+    } else {
+      v->kernel = Co == 16 ? SVR_WGRAD_C1_CO16 : SVR_WGRAD_C1;
+      v->parts = (int)cdiv(nrows, BW_ROWS);
+    }
+    return SVR_OK;
+  }
+  SVR_CHECK(Ci % 4 == 0 && Co % 4 == 0, SVR_E_UNSUPPORTED, "conv3d_bwd_weight: need Ci, Co %% 4 == 0 (Ci=%d Co=%d)", Ci, Co);
+  v->kernel = SVR_WGRAD_BRICK;
+  v->parts = bw_brick_parts(B, D, H, W, Ci, Co);
+  v->per_part = cdiv((int64_t)B * cdiv(D, BRZ) * cdiv(H, BRY) * cdiv(W, BRX), v->parts);
+  return SVR_OK;
+}
 // shared with conv3d_bwdw_bf16.hip: dWp = ordered f64 sum of `parts` slabs [part][tap][tile][32][32]
 void conv3d_bwd_weight_reduce_launch(const float *slab, float *dWp, int Ci, int Co, int cit, int cot, int parts,
                                      hipStream_t s, int param_layout, const float *dbpart, float *db, int dbparts) {
@@ -887,41 +912,38 @@ extern "C" int svr_conv3d_k3_bwd_weight(const float *in, const float *dout, floa
                                         int32_t H, int32_t W, int32_t Ci, int32_t Co, void *workspace, void *stream) {
   if (int rc = check_shape(B, D, H, W, Ci, Co)) return rc;
   SVR_CHECK(in && dout && dWp && workspace, SVR_E_BADARG, "conv3d_bwd_weight: null pointer");
+  WgradVariant v;
+  if (int rc = conv3d_bwd_weight_f32_variant(B, D, H, W, Ci, Co, &v)) return rc;
   hipStream_t s = (hipStream_t)stream;
   ConvShape sh{B, D, H, W, Ci, Co};
   const int64_t nrows = (int64_t)B * D * H;
-  const int chunks = (int)cdiv(nrows, BW_ROWS);
+  const int parts = v.parts;
   float *slab = (float *)workspace;
   int64_t slab_floats;
-  if (Ci == 1) {
-    SVR_CHECK(Co <= 32, SVR_E_UNSUPPORTED, "conv3d_bwd_weight: Ci=1 needs Co<=32 (got %d)", Co);
-    int parts = chunks;
-    if (Co == 16 && W <= 128) {
+  if (v.kernel != SVR_WGRAD_BRICK) {
+    if (v.kernel == SVR_WGRAD_C1_CO16_LDS) {
       const int nyb = (int)cdiv(H, C1L_ROWS);
-      parts = B * D * nyb;
       float *dbpart = db ? slab + (int64_t)parts * 1024 : nullptr;
       hipLaunchKernelGGL(conv3d_c1_bwd_weight_co16_lds_kernel, dim3(parts), dim3(256), 0, s, in, dout, slab, sh, nyb, dbpart);
       if (db) {
         col_parts_sum_launch(dbpart, db, 16, parts, s);  // db[co] = ordered f64 sum of the partials [parts][16]
         db = nullptr;  // done
       }
-    } else if (Co == 16) {
-      float *dbpart = db ? slab + (int64_t)chunks * 1024 : nullptr;  // the colsum scratch is at least chunks * 16 floats
-      hipLaunchKernelGGL(conv3d_c1_bwd_weight_co16_kernel, dim3(chunks), dim3(256), 0, s, in, dout, slab, sh, dbpart);
+    } else if (v.kernel == SVR_WGRAD_C1_CO16) {
+      float *dbpart = db ? slab + (int64_t)parts * 1024 : nullptr;  // the colsum scratch is at least parts * 16 floats
+      hipLaunchKernelGGL(conv3d_c1_bwd_weight_co16_kernel, dim3(parts), dim3(256), 0, s, in, dout, slab, sh, dbpart);
       if (db) {
-        col_parts_sum_launch(dbpart, db, 16, chunks, s);  // db[co] = ordered f64 sum of the partials [parts][16]
+        col_parts_sum_launch(dbpart, db, 16, parts, s);  // db[co] = ordered f64 sum of the partials [parts][16]
         db = nullptr;  // done
       }
     } else
-      hipLaunchKernelGGL(conv3d_c1_bwd_weight_kernel, dim3(chunks), dim3(256), 0, s, in, dout, slab, sh);
+      hipLaunchKernelGGL(conv3d_c1_bwd_weight_kernel, dim3(parts), dim3(256), 0, s, in, dout, slab, sh);
     hipLaunchKernelGGL(conv3d_c1_bwd_weight_reduce_kernel, dim3(27 * Co), dim3(256), 0, s, slab, dWp, Co, parts, 0,
                        (const float *)nullptr, (float *)nullptr);
     slab_floats = (int64_t)parts * 1024;
   } else {
-    SVR_CHECK(Ci % 4 == 0 && Co % 4 == 0, SVR_E_UNSUPPORTED, "conv3d_bwd_weight: need Ci, Co %% 4 == 0 (Ci=%d Co=%d)", Ci, Co);
     int cit = (int)cdiv(Ci, 32), cot = (int)cdiv(Co, 32);
     int nbz = (int)cdiv(D, BRZ), nby = (int)cdiv(H, BRY), nbx = (int)cdiv(W, BRX);
-    int parts = bw_brick_parts(B, D, H, W, Ci, Co);
     dim3 grid((unsigned)parts, (unsigned)(cit * cot));
     hipLaunchKernelGGL(conv3d_bwd_weight_brick_kernel, grid, dim3(256), 0, s, in, dout, slab, sh, nbz, nby, nbx, cot);
     int per = 27 * cit * cot * 1024;

@@ -586,6 +586,40 @@ int bwd_weight_x3(const float *in, const float *dout, float *dWp, float *db, int
                   int32_t Co, void *workspace, void *stream, int param_layout, bool f16 = false, const uint32_t *amax_dout = nullptr);
 }
 
+// The kernel choice of the split-precision entry points below, from the shape alone (svr_conv3d_k3_bwd_weight_variant exports
+// it; bwd_weight_x3 asks this function, so the two cannot drift).  The wave-specialised kernel when every workgroup gets at
+// least WS_MIN_BRICKS bricks (its pipeline fills and drains once per launch, and one consumer wave per SIMD has no partner to
+// hide its own latencies), on paired-row tiles for Ci <= 16; the 8-wave kernel for the short launches (the 8^3 layer: 2 bricks
+// per workgroup).
+int svr::conv3d_bwd_weight_x3_variant(int B, int D, int H, int W, int Ci, int Co, WgradVariant *v) {
+  SVR_CHECK(B > 0 && D > 0 && H > 0 && W > 0, SVR_E_BADSHAPE, "conv3d_bwd_weight_bf16x3: empty volume %dx%dx%dx%d", B, D, H, W);
+  SVR_CHECK(Ci >= 4 && Ci % 4 == 0 && Co % 4 == 0 && Co >= 4, SVR_E_UNSUPPORTED,
+            "conv3d_bwd_weight_bf16x3: need Ci, Co %% 4 == 0 (Ci=%d Co=%d)", Ci, Co);
+  // the kernels' 24-bit row multiplies and 32-bit byte offsets inside one sample, 32-bit brick ids
+  const int64_t nbricks = (int64_t)B * cdiv(D, BRZ) * cdiv(H, BRY) * cdiv(W, BRX);
+  SVR_CHECK((int64_t)D * H * W <= (1LL << 24) && (int64_t)D * H * W * (Ci > Co ? Ci : Co) < (1LL << 30) && nbricks < (1LL << 31),
+            SVR_E_UNSUPPORTED, "conv3d_bwd_weight_bf16x3: volume %dx%dx%dx%d too large for 32-bit offsets", B, D, H, W);
+  constexpr int WS_MIN_BRICKS = 8;
+  v->parts = x3_parts(B, D, H, W, Ci, Co);
+  v->per_part = cdiv(nbricks, v->parts);
+  v->kernel = nbricks < (int64_t)v->parts * WS_MIN_BRICKS ? SVR_WGRAD_X3 : (Ci <= 16 ? SVR_WGRAD_WS_PAIR : SVR_WGRAD_WS);
+  return SVR_OK;
+}
+
+// Which kernel a 3x3x3 weight-gradient entry point runs for a shape (host only, no device memory: callable without a GPU).
+extern "C" int svr_conv3d_k3_bwd_weight_variant(int32_t op, int32_t B, int32_t D, int32_t H, int32_t W, int32_t Ci, int32_t Co,
+                                                int32_t *kernel, int32_t *parts, int64_t *max_bricks_per_part) {
+  SVR_CHECK(op >= SVR_CONV_BWD_WEIGHT_F32 && op <= SVR_CONV_BWD_WEIGHT_BF16X3, SVR_E_BADARG, "conv3d_k3_bwd_weight_variant: op %d", op);
+  WgradVariant v;
+  if (int rc = op == SVR_CONV_BWD_WEIGHT_F32 ? conv3d_bwd_weight_f32_variant(B, D, H, W, Ci, Co, &v)
+                                             : conv3d_bwd_weight_x3_variant(B, D, H, W, Ci, Co, &v))
+    return rc;
+  if (kernel) *kernel = v.kernel;
+  if (parts) *parts = v.parts;
+  if (max_bricks_per_part) *max_bricks_per_part = v.per_part;
+  return SVR_OK;
+}
+
 // The weight gradient on the scaled f16 split ("f16x3s": f32 level, see svr_linear_bwd_weight_f16x3); amax_dout: svr_amax_f32 of
 // dout (or the amax output of the kernel that produced it).  param_layout != 0: dW(Co,Ci,3,3,3), else the packed [tap][ci][co].
 extern "C" int svr_conv3d_k3_bwd_weight_f16x3(const float *in, const float *dout, float *dW, float *db, int32_t B, int32_t D,
@@ -613,29 +647,20 @@ int bwd_weight_x3(const float *in, const float *dout, float *dWp, float *db, int
                   int32_t Co, void *workspace, void *stream, int param_layout, bool f16, const uint32_t *amax_dout) {
   SVR_CHECK(B > 0 && D > 0 && H > 0 && W > 0, SVR_E_BADSHAPE, "conv3d_bwd_weight_bf16x3: empty volume %dx%dx%dx%d", B, D, H, W);
   SVR_CHECK(in && dout && dWp && workspace, SVR_E_BADARG, "conv3d_bwd_weight_bf16x3: null pointer");
-  SVR_CHECK(Ci >= 4 && Ci % 4 == 0 && Co % 4 == 0 && Co >= 4, SVR_E_UNSUPPORTED,
-            "conv3d_bwd_weight_bf16x3: need Ci, Co %% 4 == 0 (Ci=%d Co=%d)", Ci, Co);
+  WgradVariant v;
+  if (int rc = conv3d_bwd_weight_x3_variant(B, D, H, W, Ci, Co, &v)) return rc;
   SVR_CHECK((((uintptr_t)in | (uintptr_t)dout) & 15) == 0, SVR_E_ALIGN, "conv3d_bwd_weight_bf16x3: 16-byte alignment");
-  // the kernel's 24-bit row multiplies and 32-bit byte offsets inside one sample, 32-bit brick ids
-  SVR_CHECK((int64_t)D * H * W <= (1LL << 24) && (int64_t)D * H * W * (Ci > Co ? Ci : Co) < (1LL << 30) &&
-                (int64_t)B * cdiv(D, BRZ) * cdiv(H, BRY) * cdiv(W, BRX) < (1LL << 31),
-            SVR_E_UNSUPPORTED, "conv3d_bwd_weight_bf16x3: volume %dx%dx%dx%d too large for 32-bit offsets", B, D, H, W);
   hipStream_t s = (hipStream_t)stream;
   ConvShape sh{B, D, H, W, Ci, Co};
   const int cit = (int)cdiv(Ci, 32), cot = (int)cdiv(Co, 32);
   const int nbz = (int)cdiv(D, BRZ), nby = (int)cdiv(H, BRY), nbx = (int)cdiv(W, BRX);
-  const int parts = x3_parts(B, D, H, W, Ci, Co);
+  const int parts = v.parts;
   float *slab = (float *)workspace;
   float *dbpart = db ? slab + (int64_t)parts * 2 * 27 * cit * cot * 1024 : nullptr;
-  // Dispatch: the wave-specialised kernel when every workgroup gets at least WS_MIN_BRICKS bricks (its pipeline fills and
-  // drains once per launch, and one consumer wave per SIMD has no partner to hide its own latencies); the 8-wave kernel for
-  // the short launches (the 8^3 layer: 2 bricks per workgroup).
-  constexpr int WS_MIN_BRICKS = 8;
-  const int64_t nbricks = (int64_t)B * nbz * nby * nbx;
-  if (nbricks >= (int64_t)parts * WS_MIN_BRICKS) {
+  if (v.kernel != SVR_WGRAD_X3) {
     const dim3 grid((unsigned)parts, (unsigned)(cit * cot));
     const uint32_t *am = f16 ? amax_dout : nullptr;
-    if (Ci <= 16) {
+    if (v.kernel == SVR_WGRAD_WS_PAIR) {
       if (f16) hipLaunchKernelGGL((conv3d_bwd_weight_ws_kernel<true, true>), grid, dim3(NT), 0, s, in, dout, slab, sh, nbz, nby, nbx, cot, dbpart, am);
       else hipLaunchKernelGGL((conv3d_bwd_weight_ws_kernel<false, true>), grid, dim3(NT), 0, s, in, dout, slab, sh, nbz, nby, nbx, cot, dbpart, am);
     } else {

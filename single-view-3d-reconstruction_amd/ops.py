@@ -1170,6 +1170,21 @@ def conv3d_k3_variant(op, B, dims, Ci, Co):
     return {"ck": ck.value, "tn": tn.value, "vt": vt.value, "persistent": bool(pers.value), "workgroup_rows": rows.value}
 
 
+WGRAD_VARIANT_OPS = {"bwd_weight_f32": 0, "bwd_weight_f16x3s": 1, "bwd_weight_bf16x3": 2}      # SVR_CONV_BWD_WEIGHT_* of svr_hip.h
+WGRAD_KERNELS = ("C1_CO16_LDS", "C1_CO16", "C1", "BRICK", "WS_PAIR", "WS", "X3")                # SVR_WGRAD_*
+
+
+def conv3d_k3_bwd_weight_variant(op, B, dims, Ci, Co):
+    """The kernel the 3x3x3 weight-gradient entry point `op` (a key of WGRAD_VARIANT_OPS) runs for (B, *dims, Ci -> Co):
+    {"kernel" (a name of WGRAD_KERNELS), "parts", "max_bricks_per_part"} (svr_conv3d_k3_bwd_weight_variant; host only, no GPU
+    needed).  A shape the entry point refuses raises with its error code, as the entry point would."""
+    D, H, W = dims
+    kernel, parts, per = C.c_int32(), C.c_int32(), C.c_int64()
+    check(_lib.lib().svr_conv3d_k3_bwd_weight_variant(WGRAD_VARIANT_OPS[op], B, D, H, W, Ci, Co, C.byref(kernel), C.byref(parts),
+                                                      C.byref(per)), "conv3d_k3_bwd_weight_variant")
+    return {"kernel": WGRAD_KERNELS[kernel.value], "parts": parts.value, "max_bricks_per_part": per.value}
+
+
 # Arithmetic of the encoder's weight gradients: "bf16x3" (conv3d_bwdw_bf16.hip), "f16x3s" (its scaled f16 form: f32 level)
 # or "f32" (exact-f32 MFMA)
 BACKWARD_CONV_WEIGHT = BACKWARD_GEMM

@@ -240,6 +240,51 @@ def test_conv3d_variant_refuses_what_the_entry_points_refuse():
     assert q(4, 2, 8, 8, 8, 16, 16) == -1 and q(-1, 2, 8, 8, 8, 16, 16) == -1 and q(0, 2, 0, 8, 8, 16, 16) == -2
 
 
+def test_wgrad_variant_table_and_every_kernel_is_reached():
+    """Which kernel a 3x3x3 weight-gradient entry point runs, asked of the library (svr_conv3d_k3_bwd_weight_variant: the
+    function the launchers of csrc/conv3d.hip and csrc/conv3d_bwdw_bf16.hip themselves call), for every row of
+    tests/_wgrad_cases.py; the rows, together, reach EVERY kernel the launchers can select, the 8-wave split kernel and the f32
+    brick kernel each with one brick per workgroup and with several.  A change to x3_parts, bw_brick_parts, WS_MIN_BRICKS or the
+    W <= 128 rule that moves a row onto another kernel fails here, without a GPU."""
+    import __graft_entry__ as ge
+    ge.build()
+    from svr_amd import _lib, ops
+    from tests import _wgrad_cases as WC
+    assert len({c[0] for c in WC.CASES}) == len(WC.CASES)
+    l = _lib.lib()
+    z = ctypes.c_void_p(0)
+    reached, per_seen = set(), set()
+    for name, op, B, dims, Ci, Co, tag, per in WC.expected():
+        if tag is None:      # refused by the entry point: the query returns its error code
+            assert l.svr_conv3d_k3_bwd_weight_variant(ops.WGRAD_VARIANT_OPS[op], B, *dims, Ci, Co, z, z, z) == WC.UNSUPPORTED, (name, op)
+            continue
+        v = ops.conv3d_k3_bwd_weight_variant(op, B, dims, Ci, Co)
+        assert v["kernel"] == tag, (name, op, v)
+        reached.add((op, tag))
+        nb, pairs = WC.bricks(B, dims), -(-Ci // 32) * -(-Co // 32)
+        if tag in ("X3", "BRICK"):
+            assert per in ("1", ">1") and (v["max_bricks_per_part"] == 1) == (per == "1"), (name, op, v)
+            per_seen.add((tag, per))
+        if tag == "BRICK":   # one brick per workgroup exactly when the volume has fewer bricks than the rule's 512 / pairs parts
+            assert (v["max_bricks_per_part"] == 1) == (nb <= -(-512 // pairs)), (name, v, nb)
+            assert v["parts"] == min(-(-512 // pairs), nb), (name, v)
+        if tag in ("WS_PAIR", "WS", "X3"):
+            assert v["parts"] == min(-(-256 // pairs), nb) and v["max_bricks_per_part"] == -(-nb // v["parts"]), (name, v)
+            assert (tag == "X3") == (nb < 8 * v["parts"]) and (tag == "WS_PAIR") == (tag != "X3" and Ci <= 16), (name, v)
+        if tag.startswith("C1"):
+            assert v["max_bricks_per_part"] == 1 and v["parts"] >= 1, (name, v)
+    assert reached == WC.ALL_VARIANTS, sorted(reached ^ WC.ALL_VARIANTS)
+    assert per_seen == {(t, p) for t in ("X3", "BRICK") for p in ("1", ">1")}, per_seen
+    assert len(WC.ALL_VARIANTS) == 4 + 2 * 3
+    # what the entry points refuse, the query refuses with the same code; every output may be NULL
+    q = lambda op, *a: l.svr_conv3d_k3_bwd_weight_variant(op, *a, z, z, z)     # noqa: E731
+    assert q(0, 1, 8, 8, 8, 16, 32) == 0 and q(1, 1, 8, 8, 8, 16, 32) == 0 and q(2, 1, 8, 8, 8, 4, 4) == 0
+    assert q(3, 1, 8, 8, 8, 16, 32) == -1 and q(-1, 1, 8, 8, 8, 16, 32) == -1
+    assert q(0, 1, 0, 8, 8, 16, 32) == -2 and q(2, 1, 8, 8, 0, 16, 32) == -2
+    assert q(0, 1, 8, 8, 8, 1, 48) == -4 and q(0, 1, 8, 8, 8, 6, 32) == -4 and q(1, 1, 8, 8, 8, 1, 16) == -4 and q(2, 1, 8, 8, 8, 16, 6) == -4
+    assert q(1, 1, 256, 256, 257, 16, 16) == -4 and q(0, 1, 256, 256, 257, 16, 16) == 0      # over 2^24 voxels: the f32 kernel only
+
+
 def test_linear_variant_table_and_every_launcher_branch_is_reached():
     """Which kernel, epilogue form and bias form a linear op runs, asked of the library (svr_linear_variant: the function the
     launchers of csrc/gemm*.hip themselves call) through ops.linear_variant, for every case of tests/test_gpu_gemm_paths.py;

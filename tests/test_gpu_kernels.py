@@ -472,6 +472,31 @@ def test_conv3d_fwd_bwd(B, dims, Ci, Co):
             assert G.rel_err(_ncdhw(d3).numpy(), (gx * (x > 0)).detach().numpy()) < tol, mode
 
 
+@pytest.mark.parametrize("Ci", [16, 32])
+@pytest.mark.parametrize("B,dims", [(2, (9, 7, 11)), (1, (8, 8, 8))])
+def test_conv3d_to1_unaligned_input(B, dims, Ci):
+    """The Co == 1 forward (backward-data of conv_in) on an input that does not start on a 16-byte boundary: svr_conv3d_k3 then
+    takes conv3d_to1_kernel<16|32> instead of the column kernel conv3d_to1_col_kernel.  A contiguous view one float into a larger
+    buffer is such an input; the same values in a buffer of their own take the column kernel.  Both against f64, and against
+    each other."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(Ci * 100 + dims[0])
+    x = torch.randn(B, Ci, *dims, generator=g)
+    w = torch.randn(1, Ci, 3, 3, 3, generator=g) / (27 * Ci) ** 0.5
+    y_ref = F.conv3d(x.double(), w.double(), padding=1).numpy()
+    wf, _ = ops.conv3d_pack_weight(w.cuda(), want_bwd=False)
+    xa = _cl(x)
+    buf = torch.empty(xa.numel() + 1, device="cuda")
+    xu = buf[1:].view(xa.shape)
+    xu.copy_(xa)
+    assert xa.data_ptr() % 16 == 0 and xu.data_ptr() % 16 == 4 and xu.is_contiguous()
+    y_col, y_to1 = ops.conv3d_k3(xa, wf), ops.conv3d_k3(xu, wf)
+    assert y_to1.shape == (B, *dims, 1)
+    assert G.rel_err(_ncdhw(y_col).numpy(), y_ref) < 3e-6
+    assert G.rel_err(_ncdhw(y_to1).numpy(), y_ref) < 3e-6
+    assert G.rel_err(y_to1.cpu().numpy(), y_col.cpu().numpy()) < 3e-6
+
+
 @pytest.mark.parametrize("B,dims,Ci,Co,gscale", [(2, (10, 6, 12), 16, 32, 1e-5), (1, (8, 8, 8), 32, 32, 1.0), (2, (7, 5, 6), 32, 64, 3e-8),
                                                   (1, (6, 6, 6), 64, 64, 1e-3), (1, (4, 5, 6), 64, 128, 1e-6), (2, (4, 4, 4), 128, 128, 20.0),
                                                   (2, (17, 16, 24), 16, 32, 1e-4)])
