@@ -375,6 +375,19 @@ int svr_fc_out_bwd(const float *H, int64_t ldh, const float *w, const float *dlo
                    const int32_t *row_map, float *dH, int64_t lddh, float *dw, float *db, int64_t M,
                    int64_t K, uint32_t *amax_dh, void *workspace, void *stream);
 
+/* The tail of the point MLP in one kernel (mlp_tail.hip): h1 = relu(h0 W1^T + b1), h2 = relu(h1 W2^T + b2),
+ * logits[r(m)] = h2[m,:].w_out + b_out -- bit for bit what svr_linear_fwd_f16x3 (twice, BIAS_RELU) and svr_fc_out_fwd
+ * return, without reading h1 and h2 back (both are still written: the backward needs them).  W1, W2 (hidden, hidden)
+ * contiguous; h0, h1, h2 (M, hidden) with leading dimensions ldh*.  hidden == 256 only; h0 / h1 / h2 rows 16-byte aligned,
+ * leading dimensions multiples of 4, w_out 16-byte aligned: SVR_E_UNSUPPORTED otherwise (run the three ops instead).
+ * PREPARE / RUN as svr_linear_fwd_f16x3: h0 == NULL prepares the workspace from W1 and W2 only, W1 == NULL (then W2 == NULL
+ * too) runs on a prepared workspace.  workspace: svr_mlp_tail_fwd_workspace(hidden) bytes (SVR_E_UNSUPPORTED for a width
+ * the kernel is not built for).                                                                                       */
+int64_t svr_mlp_tail_fwd_workspace(int64_t hidden);
+int svr_mlp_tail_fwd(const float *h0, int64_t ldh0, const float *W1, const float *b1, const float *W2, const float *b2,
+                     const float *w_out, const float *b_out, float *h1, int64_t ldh1, float *h2, int64_t ldh2,
+                     float *logits, const int32_t *row_map, int64_t M, int64_t hidden, void *workspace, void *stream);
+
 /* BCE-with-logits, reduction 'none' -> sum over points -> mean over batch
  * (trainer/trainer_ifnet.py:46).  loss: 1 float; dlogits (B,N) = gscale*(sigmoid(z)-y)/B
  * (dlogits may be NULL).  workspace: B doubles.                                           */

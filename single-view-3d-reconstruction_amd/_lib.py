@@ -98,6 +98,8 @@ SIGNATURES = {
     "svr_linear_bwd_weight_f16x3": (C.c_int, [P, I64, P, I64, P, I64, P, I64, I64, I64, P, P, P]),
     "svr_linear_variant": (C.c_int, [I32, I64, I64, I64, I64, I64, I64, I64, I32, I32, I32, I32, I32, I32, P, P, P, P, P, P]),
     "svr_fc_out_fwd": (C.c_int, [P, I64, P, P, P, P, I64, I64, P]),
+    "svr_mlp_tail_fwd_workspace": (I64, [I64]),
+    "svr_mlp_tail_fwd": (C.c_int, [P, I64, P, P, P, P, P, P, P, I64, P, I64, P, P, I64, I64, P, P]),
     "svr_fc_out_bwd_workspace": (I64, [I64, I64]),
     "svr_fc_out_bwd": (C.c_int, [P, I64, P, P, P, P, I64, P, P, I64, I64, P, P, P]),
     "svr_bce_logits_sum_mean": (C.c_int, [P, P, P, P, I64, I64, F32, P, P]),

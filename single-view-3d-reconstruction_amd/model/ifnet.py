@@ -655,9 +655,7 @@ class _PointMLPFn(torch.autograd.Function):
         _EncoderGatherFn's fused backward."""
         ctx.headless = w0p is None
         h0 = feat if ctx.headless else ops.linear_fwd(feat, w0p, b0, relu=True)
-        h1 = ops.linear_fwd(h0, w1, b1, relu=True)
-        h2 = ops.linear_fwd(h1, w2, b2, relu=True)
-        logits = ops.fc_out_fwd(h2, wo, bo, row_map)
+        h1, h2, logits = ops.mlp_tail_fwd(h0, w1, b1, w2, b2, wo, bo, row_map)      # one kernel where it applies, else the three ops
         ctx.save_for_backward(*(() if ctx.headless else (feat, w0p)), w1, w2, wo, h0, h1, h2)
         ctx.row_map = row_map
         ctx.link = link
@@ -897,8 +895,11 @@ class IFNet(nn.Module):
                     for conv in convs:
                         if conv.weight.shape[1] > 1:
                             prep.add_conv(conv.weight.detach(), which)
-                prep.add_linear(self.fc_1.weight.detach().squeeze(2), which)
-                prep.add_linear(self.fc_2.weight.detach().squeeze(2), which)
+                # fc_1 / fc_2 forward: the planes of the fused tail (ops.mlp_tail_fwd) where it runs, else one set per layer
+                w1, w2 = self.fc_1.weight.detach().squeeze(2), self.fc_2.weight.detach().squeeze(2)
+                if which == "bwd" or not prep.add_mlp_tail(w1, w2):
+                    prep.add_linear(w1, which)
+                    prep.add_linear(w2, which)
                 if which == "fwd":
                     prep.mark(side)
             prep.finish(side)
@@ -978,9 +979,9 @@ class IFNet(nn.Module):
         else:
             rows = ext.feature_rows_from_levels(levels, points)
             h = ops.linear_fwd(rows, self._fc0_internal(), self.fc_0.bias, relu=True)
-        h = ops.linear_fwd(h, self.fc_1.weight.squeeze(2), self.fc_1.bias, relu=True)
-        h = ops.linear_fwd(h, self.fc_2.weight.squeeze(2), self.fc_2.bias, relu=True)
-        return ops.fc_out_fwd(h, self.fc_out.weight.reshape(-1).contiguous(), self.fc_out.bias, row_map).view(B, N)
+        _, _, logits = ops.mlp_tail_fwd(h, self.fc_1.weight.squeeze(2), self.fc_1.bias, self.fc_2.weight.squeeze(2), self.fc_2.bias,
+                                        self.fc_out.weight.reshape(-1).contiguous(), self.fc_out.bias, row_map)
+        return logits.view(B, N)
 
     def forward(self, x, points, spatial_sort=True):
         """logits (B,N).  With spatial_sort the points of every sample are visited in Morton order: the whole

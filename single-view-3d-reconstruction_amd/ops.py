@@ -639,6 +639,23 @@ class PreparedWeights:
                                               _p(ws), _stream()), "linear_bwd_data_f16x3 prepare")
             self._valid[("lbh", w.data_ptr())] = (w._version, len(self._events))
 
+    def add_mlp_tail(self, w1, w2):
+        """w1, w2 (256,256): the planes of the fused fc_1 -> fc_2 -> fc_out kernel (mlp_tail_fwd), one workspace for both; False
+        (nothing added) where mlp_tail_fwd would run the three ops."""
+        _f32(w1, w2)
+        hidden = w1.shape[1]
+        if _mlp_tail_op(None, hidden, w1, w2, None, None) != "mlp_tail_f16x3":
+            return False
+        l = _lib.lib()
+        z = C.c_void_p(0)
+        ws = self._buf(("mt", w1.data_ptr()), l.svr_mlp_tail_fwd_workspace(hidden), w1.device)
+        check(l.svr_mlp_tail_fwd(z, 0, C.c_void_p(w1.data_ptr()), z, C.c_void_p(w2.data_ptr()), z, z, z, z, 0, z, 0, z, z, 0, hidden,
+                                 _p(ws), _stream()), "mlp_tail_fwd prepare")
+        self._ws[("mt2", w2.data_ptr())] = ws      # found by either matrix; mlp_tail_fwd wants both to name this buffer
+        self._valid[("mt", w1.data_ptr())] = (w1._version, len(self._events))
+        self._valid[("mt2", w2.data_ptr())] = (w2._version, len(self._events))
+        return True
+
     def mark(self, stream):
         """An event behind the planes added so far: a lookup waits for the event of ITS planes only (the forward pass does not
         wait for the backward planes -- 54 launch-bound kernels per step, 0.5 ms of side-stream time)."""
@@ -654,8 +671,9 @@ class PreparedWeights:
         self._valid.clear()
 
     def lookup(self, kind, w):
-        """The prepared workspace of `w` for `kind` ("cf" / "cb" / "lf" / "lb"), or None.  The first hit of a step makes
-        the calling stream wait for the preparation (the step's later work on other streams is ordered behind it)."""
+        """The prepared workspace of `w` for `kind` ("cf" / "cb" / "lf" / "lb"; "mt" / "mt2": the fused tail's, found by fc_1's /
+        fc_2's matrix), or None.  The first hit of a step makes the calling stream wait for the preparation (the step's later work
+        on other streams is ordered behind it)."""
         key = (kind, w.data_ptr())
         ver, idx = self._valid.get(key, (-1, 0))
         if ver != w._version or idx >= len(self._events):      # not prepared, or modified in place since (an optimizer step)
@@ -703,6 +721,21 @@ def _al16(lay):
 def _linear_fwd_op(mode, K):
     mode = mode or FORWARD_GEMM
     return "fwd_" + mode if mode in ("f16x3", "bf16x6") and K % 16 == 0 else "fwd_f32"
+
+
+MLP_TAIL_HIDDEN = 256      # the width mlp_tail.hip is built for
+
+
+def _mlp_tail_op(mode, hidden, w1, w2, wo, h0):
+    """fc_1 -> fc_2 -> fc_out: "mlp_tail_f16x3" (svr_mlp_tail_fwd, one kernel) for the default arithmetic at the width the
+    kernel is built for and operands it can move as float4; "three_ops" (linear_fwd twice, fc_out_fwd) for everything else.
+    w1, w2, wo: the tensors (wo None: not known yet); h0: operand_layout() of the input (None: contiguous and aligned)."""
+    mode = mode or FORWARD_GEMM
+    if (mode == "f16x3" and hidden == MLP_TAIL_HIDDEN and tuple(w1.shape) == (hidden, hidden) and tuple(w2.shape) == (hidden, hidden)
+            and w1.is_contiguous() and w2.is_contiguous() and (wo is None or (wo.is_contiguous() and wo.data_ptr() % 16 == 0))
+            and _al16(h0)):
+        return "mlp_tail_f16x3"
+    return "three_ops"
 
 
 def _linear_bwd_data_op(mode, N, dy, out, mask):
@@ -780,6 +813,32 @@ def linear_fwd(x, w, bias, relu=True, out=None, mode=None):
                                     _p(bias), _rp(out), out.stride(0), M, N, K, epi, C.c_void_p(0), 0, _stream()),
           "linear_fwd")
     return out
+
+
+def mlp_tail_fwd(h0, w1, b1, w2, b2, wo, bo, row_map=None):
+    """(h1, h2, logits) = relu(h0 @ w1.T + b1), relu(h1 @ w2.T + b2), fc_out(h2) scattered by row_map: the fused kernel of
+    mlp_tail.hip where _mlp_tail_op says so, else the three calls -- the same bits either way."""
+    _f32(h0, w1, b1, w2, b2, wo, bo)
+    M, K = h0.shape
+    assert w1.shape == (w1.shape[0], K) and w2.shape == (w2.shape[0], w1.shape[0]) and h0.stride(1) == 1
+    if _mlp_tail_op(None, K, w1, w2, wo, operand_layout(h0)) != "mlp_tail_f16x3":
+        h1 = linear_fwd(h0, w1, b1, relu=True)
+        h2 = linear_fwd(h1, w2, b2, relu=True)
+        return h1, h2, fc_out_fwd(h2, wo, bo, row_map)
+    l = _lib.lib()
+    h1 = torch.empty(M, K, device=h0.device, dtype=torch.float32)
+    h2 = torch.empty(M, K, device=h0.device, dtype=torch.float32)
+    logits = torch.empty(M, device=h0.device, dtype=torch.float32)
+    ws = _lookup("mt", w1, None, "f16x3")
+    if ws is not None and _lookup("mt2", w2, None, "f16x3") is not ws:      # (the planes of this w1 were made with another w2)
+        ws = None
+    z = C.c_void_p(0)
+    wp1, wp2 = (z, z) if ws is not None else (C.c_void_p(w1.data_ptr()), C.c_void_p(w2.data_ptr()))      # W NULL: prepared
+    if ws is None:
+        ws = torch.empty(l.svr_mlp_tail_fwd_workspace(K), device=h0.device, dtype=torch.uint8)
+    check(l.svr_mlp_tail_fwd(C.c_void_p(h0.data_ptr()), h0.stride(0), wp1, _p(b1), wp2, _p(b2), _p(wo), _p(bo), _p(h1), K, _p(h2), K,
+                             _p(logits), _p(row_map), M, K, _p(ws), _stream()), "mlp_tail_fwd")
+    return h1, h2, logits
 
 
 # Arithmetic of the two backward GEMMs of the point MLP: "f16x3s" (DEFAULT since round 4: the SCALED 3-product f16 split --
