@@ -730,6 +730,42 @@ int svr_conv2d_finish_bwd(const svr_conv2d_desc *d, const float *dvirt, float *d
 int64_t svr_conv2d_bwd_weight_workspace(const svr_conv2d_desc *d, int32_t Cout);
 int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, const uint32_t *amax_dy, int32_t Cout, float *dW, float *db,
                           void *workspace, void *stream);
+/* What the conv2d entry points above do with a layer (the launchers and the workspace-size functions ask the same functions).
+ * Host only: no device memory is touched, callable without a GPU.  op = SVR_CV2_*; the shape as the descriptor holds it
+ * (act = 0, upsample = 0); lo_src0 / lo_src1 / lo_dy / lo_out: the low four address bits of the two sources, of dY and of the
+ * output (Y / dIn).  The layer runs on the plain-FMA kernels where svr_conv2d_small_supported says so (as svr_amd.ops routes it),
+ * else on the GEMMs.  plan (may be NULL) receives:
+ *   family: SVR_CV2_SMALL / IGEMM64 / IGEMM128 (conv2d_igemm_kernel<64 / 128>) / WGRAD_TR (linear_tn_x3_tr_kernel<true, true, *>);
+ *   vec4: the gathered operand (the input; dY for backward-data) goes through the 16-byte loader;  Ho, Wo: output size;
+ *   forward / backward-data GEMMs: classes (4: the parity classes of a stride-2 backward), mtiles (row tiles of the largest
+ *     class), tiles (workgroups per reduction split), ksteps, splits, ksplit (k-steps per split), epilogue (SVR_CV2_EPI_*: COAL /
+ *     LANE = the kernel's own epilogue, float4 rows through LDS or one dword per lane; REDUCE_V4 / REDUCE_SCALAR = partial tiles
+ *     summed by ig_reduce_kernel), reduce_grid (its workgroups; it strides where split_stride > 1024 * reduce_grid),
+ *     split_stride (floats of the output), workspace_bytes (the partial outputs; 0 unsplit);
+ *   weight gradient: dy_vec4 (dY through the float4 loader), tiles, splits (row slabs), rows_per_split, last_rows;
+ *   small kernels: co, kk (kernel size), grid (grid.x), capped (forward / backward-data: the grid is at its cap and workgroups
+ *     stride), rows_per_block, parts, ipg, groups, grid_y (weight gradient), workspace_bytes (its partials).
+ * Returns SVR_OK or the entry point's own refusal (SVR_E_BADARG for an unknown op), its text in svr_last_error().               */
+#define SVR_CV2_FWD 0
+#define SVR_CV2_BWD_DATA 1
+#define SVR_CV2_BWD_WEIGHT 2
+#define SVR_CV2_SMALL 0
+#define SVR_CV2_IGEMM64 1
+#define SVR_CV2_IGEMM128 2
+#define SVR_CV2_WGRAD_TR 3
+#define SVR_CV2_EPI_COAL 0
+#define SVR_CV2_EPI_LANE 1
+#define SVR_CV2_EPI_REDUCE_V4 2
+#define SVR_CV2_EPI_REDUCE_SCALAR 3
+typedef struct svr_conv2d_plan {
+  int32_t family, vec4, Ho, Wo;
+  int32_t classes, ksteps, splits, ksplit, epilogue, reduce_grid;
+  int32_t dy_vec4;
+  int32_t co, kk, grid, capped, rows_per_block, parts, ipg, groups, grid_y;
+  int64_t mtiles, tiles, split_stride, rows_per_split, last_rows, workspace_bytes;
+} svr_conv2d_plan;
+int svr_conv2d_variant(int32_t op, int32_t B, int32_t H, int32_t W, int32_t C0, int32_t C1, int32_t Cout, int32_t k, int32_t stride,
+                       int32_t lo_src0, int32_t lo_src1, int32_t lo_dy, int32_t lo_out, svr_conv2d_plan *plan);
 
 /* ---------------------------------------------------------------------------------------
  * Occupancy labelling against a triangle mesh (replaces check_mesh_contains,

@@ -28,6 +28,12 @@ class Conv2dDesc(C.Structure):
                 ("stride", I32), ("act", I32), ("upsample", I32)]
 
 
+class Conv2dPlan(C.Structure):      # svr_conv2d_plan (tests/test_capi_cpu.py compares the layout with the header's)
+    _fields_ = [(n, I32) for n in ("family", "vec4", "Ho", "Wo", "classes", "ksteps", "splits", "ksplit", "epilogue", "reduce_grid",
+                                   "dy_vec4", "co", "kk", "grid", "capped", "rows_per_block", "parts", "ipg", "groups", "grid_y")] + \
+               [(n, I64) for n in ("mtiles", "tiles", "split_stride", "rows_per_split", "last_rows", "workspace_bytes")]
+
+
 class PullPlan(C.Structure):
     _fields_ = [("keys", P), ("recs", P), ("heads", P), ("n_items", I64)]
 
@@ -157,6 +163,7 @@ SIGNATURES = {
     "svr_conv2d_finish_bwd": (C.c_int, [C.POINTER(Conv2dDesc), P, P, P, P]),
     "svr_conv2d_bwd_weight_workspace": (I64, [C.POINTER(Conv2dDesc), I32]),
     "svr_conv2d_bwd_weight": (C.c_int, [C.POINTER(Conv2dDesc), P, P, I32, P, P, P, P]),
+    "svr_conv2d_variant": (C.c_int, [I32] * 13 + [C.POINTER(Conv2dPlan)]),
     "svr_mesh_hash_entries": (I64, [P, I64, P, I64, I32, P]),
     "svr_mesh_hash_build": (C.c_int, [P, I64, P, I64, I32, P, P, P, I64]),
     "svr_mesh_contains": (C.c_int, [P, I32, I64, P, P, P, I32, P, P, P, P]),

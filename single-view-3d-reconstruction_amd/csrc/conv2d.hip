@@ -13,6 +13,7 @@
 // Bilinear upsample = at::upsample_bilinear2d, align_corners = False, scale 2: src = max(0, 0.5 * (dst + 0.5) - 0.5),
 // i0 = (int)src, i1 = i0 + (i0 < n - 1), l1 = src - i0, l0 = 1 - l1; value = l0y*(l0x*v00 + l1x*v01) + l1y*(l0x*v10 + l1x*v11).
 #include "common.h"
+#include "conv2d_plan.h"
 #include "conv2d_virt.h"
 #include <algorithm>
 
@@ -174,6 +175,9 @@ int check_block(const svr_conv2d_desc *d, const char *what) {
   SVR_CHECK((d->k == 4 && d->stride == 2) || (d->k == 3 && d->stride == 1), SVR_E_UNSUPPORTED, "%s: k=%d stride=%d (k4 s2 / k3 s1)", what,
             d->k, d->stride);
   SVR_CHECK(d->act >= 0 && d->act <= 2, SVR_E_BADARG, "%s: act %d", what, d->act);
+  const int up = d->upsample ? 2 : 1;      // (C division truncates toward zero: a 1-pixel side at k4 s2 would count one output row)
+  SVR_CHECK(up * d->H + 2 >= d->k && up * d->W + 2 >= d->k, SVR_E_BADSHAPE, "%s: input %d x %d (padding 1) is smaller than the %d x %d window: no output",
+            what, up * d->H, up * d->W, d->k, d->k);
   return SVR_OK;
 }
 
@@ -275,7 +279,7 @@ extern "C" int svr_conv2d_finish_bwd(const svr_conv2d_desc *d, const float *dvir
 // A GEMM tile would be 1/64 .. 1/32 full, so these run on the vector ALUs in plain f32 FMAs (no split, no amax): 16 lanes per
 // pixel, one channel quad each.  Weights are staged in LDS as [tap][c][co]; limit CO * C * k * k <= 8192 floats.
 namespace {
-constexpr int SM_MAXW = 8192;
+constexpr int SM_MAXW = CV2_SM_MAXW;
 
 template <int CO>
 __device__ __forceinline__ void sm_stage_w(const float *__restrict__ W, float *wl, int C, int kk) {
@@ -481,23 +485,17 @@ __global__ __launch_bounds__(256) void conv2d_small_wgrad_reduce_kernel(const fl
   }
 }
 
-int sm_check(const svr_conv2d_desc *d, int Cout, const char *what) {
-  SVR_CHECK(d && d->src0 && d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0, SVR_E_BADARG, "%s: bad descriptor", what);
+// the launch plan of a small-kernel entry point (conv2d_plan.h: the function svr_conv2d_variant answers from); pointers are
+// checked by the caller
+int sm_plan(int op, const svr_conv2d_desc *d, int Cout, const char *what, svr_conv2d_plan &P) {
+  SVR_CHECK(d && d->src0, SVR_E_BADARG, "%s: bad descriptor", what);
   SVR_CHECK(d->C1 == 0 || d->src1, SVR_E_BADARG, "%s: C1 = %d without a second source", what, d->C1);
-  SVR_CHECK((d->k == 4 && d->stride == 2) || (d->k == 3 && d->stride == 1), SVR_E_UNSUPPORTED, "%s: k=%d stride=%d", what, d->k, d->stride);
-  SVR_CHECK(!d->upsample, SVR_E_UNSUPPORTED, "%s: the x2 upsample is materialised first (svr_conv2d_virtual)", what);
-  SVR_CHECK((int64_t)d->B * d->H * d->W < (1 << 24), SVR_E_UNSUPPORTED, "%s: %ld pixels (row decode limit 2^24)", what, (long)d->B * d->H * d->W);
-  SVR_CHECK(Cout >= 1 && Cout <= 4 && (int64_t)Cout * (d->C0 + d->C1) * d->k * d->k <= SM_MAXW, SVR_E_UNSUPPORTED,
-            "%s: Cout=%d C=%d (1..4 output channels, Cout*C*k*k <= %d)", what, Cout, d->C0 + d->C1, SM_MAXW);
-  return SVR_OK;
+  return cv2_small_plan(Cv2Query{op, d->B, d->H, d->W, d->C0, d->C1, Cout, d->k, d->stride, d->act, d->upsample, cv2_lo4(d->src0),
+                                 cv2_lo4(d->src1), 0, 0}, P);
 }
-bool sm_vec4(const svr_conv2d_desc *d) {
-  return d->C0 % 4 == 0 && d->C1 % 4 == 0 && (((uintptr_t)d->src0 | (uintptr_t)d->src1) & 15) == 0;
-}
-int sm_rows_per_block(int64_t M) { return (int)std::max<int64_t>(64, cdiv(cdiv(M, 1024), 4) * 4); }
 }  // namespace
 
-extern "C" int svr_conv2d_small_supported(int32_t Cout, int32_t C, int32_t k) { return Cout >= 1 && Cout <= 4 && (int64_t)Cout * C * k * k <= SM_MAXW; }
+extern "C" int svr_conv2d_small_supported(int32_t Cout, int32_t C, int32_t k) { return cv2_small_supported(Cout, C, k); }
 
 #define SM_CO(CALL)              \
   switch (Cout) {                \
@@ -508,15 +506,14 @@ extern "C" int svr_conv2d_small_supported(int32_t Cout, int32_t C, int32_t k) { 
   }
 
 extern "C" int svr_conv2d_small_fwd(const svr_conv2d_desc *d, const float *W, const float *bias, float *Y, int32_t Cout, void *stream) {
-  if (int rc = sm_check(d, Cout, "conv2d_small_fwd")) return rc;
+  svr_conv2d_plan P;
+  if (int rc = sm_plan(SVR_CV2_FWD, d, Cout, "conv2d_small_fwd", P)) return rc;
   SVR_CHECK(W && Y, SVR_E_BADARG, "conv2d_small_fwd: null pointer");
-  int Hv, Wv, Ho, Wo;
-  out_dims(d, Hv, Wv, Ho, Wo);
+  const int Ho = P.Ho, Wo = P.Wo;
   const CvSrc S{d->src0, d->src1, d->C0, d->C1, d->H, d->W, d->act};
-  const int64_t M = (int64_t)d->B * Ho * Wo;
-  const dim3 grid((unsigned)std::min<int64_t>(cdiv(M, 16), 2048));
+  const dim3 grid((unsigned)P.grid);
   hipStream_t s = (hipStream_t)stream;
-  const bool v4 = sm_vec4(d);
+  const bool v4 = P.vec4;
 #define CALL(N)                                                                                                          \
   if (d->k == 3) {                                                                                                       \
     if (v4) hipLaunchKernelGGL((conv2d_small_fwd_kernel<N, 3, true>), grid, dim3(256), 0, s, S, W, bias, Y, d->B, Ho, Wo);   \
@@ -531,14 +528,12 @@ extern "C" int svr_conv2d_small_fwd(const svr_conv2d_desc *d, const float *W, co
 }
 
 extern "C" int svr_conv2d_small_bwd_data(const svr_conv2d_desc *d, const float *W, const float *dY, int32_t Cout, float *dIn, void *stream) {
-  if (int rc = sm_check(d, Cout, "conv2d_small_bwd_data")) return rc;
+  svr_conv2d_plan P;
+  if (int rc = sm_plan(SVR_CV2_BWD_DATA, d, Cout, "conv2d_small_bwd_data", P)) return rc;
   SVR_CHECK(W && dY && dIn, SVR_E_BADARG, "conv2d_small_bwd_data: null pointer");
-  int Hv, Wv, Ho, Wo;
-  out_dims(d, Hv, Wv, Ho, Wo);
-  const int C = d->C0 + d->C1;
-  const int64_t total = (int64_t)d->B * d->H * d->W * ((C + 3) / 4);
+  const int C = d->C0 + d->C1, Ho = P.Ho, Wo = P.Wo;
   SVR_CHECK((((uintptr_t)dIn) & 15) == 0, SVR_E_ALIGN, "conv2d_small_bwd_data: dIn must be 16-byte aligned");
-  const unsigned gridx = (unsigned)std::min<int64_t>(cdiv(total, 256), 4096);
+  const unsigned gridx = (unsigned)P.grid;
   hipStream_t s = (hipStream_t)stream;
 #define CALL(N)                                                                                                                              \
   if (d->k == 3) hipLaunchKernelGGL((conv2d_small_bwd_data_kernel<N, 3>), dim3(gridx), dim3(256), 0, s, dY, W, dIn, d->B, d->H, d->W, C, Ho, Wo); \
@@ -550,30 +545,24 @@ extern "C" int svr_conv2d_small_bwd_data(const svr_conv2d_desc *d, const float *
 
 extern "C" int64_t svr_conv2d_small_bwd_weight_workspace(const svr_conv2d_desc *d, int32_t Cout) {
   if (!d) return 0;
-  int Hv, Wv, Ho, Wo;
-  out_dims(d, Hv, Wv, Ho, Wo);
-  const int64_t M = (int64_t)d->B * Ho * Wo;
-  const int64_t parts = cdiv(M, sm_rows_per_block(M));
-  return parts * ((int64_t)d->k * d->k * (d->C0 + d->C1) * Cout + Cout) * 4 + 256;
+  svr_conv2d_plan P;
+  if (cv2_small_plan(Cv2Query{SVR_CV2_BWD_WEIGHT, d->B, d->H, d->W, d->C0, d->C1, Cout, d->k, d->stride, d->act, d->upsample, 0, 0, 0, 0}, P) != SVR_OK)
+    return 256;
+  return P.workspace_bytes + 256;
 }
 
 extern "C" int svr_conv2d_small_bwd_weight(const svr_conv2d_desc *d, const float *dY, int32_t Cout, float *dW, float *db, void *workspace,
                                            void *stream) {
-  if (int rc = sm_check(d, Cout, "conv2d_small_bwd_weight")) return rc;
+  svr_conv2d_plan P;
+  if (int rc = sm_plan(SVR_CV2_BWD_WEIGHT, d, Cout, "conv2d_small_bwd_weight", P)) return rc;
   SVR_CHECK(dY && dW && workspace, SVR_E_BADARG, "conv2d_small_bwd_weight: null pointer");
-  int Hv, Wv, Ho, Wo;
-  out_dims(d, Hv, Wv, Ho, Wo);
-  const int C = d->C0 + d->C1, kk = d->k * d->k;
+  const int C = d->C0 + d->C1, kk = d->k * d->k, Ho = P.Ho, Wo = P.Wo;
   const CvSrc S{d->src0, d->src1, d->C0, d->C1, d->H, d->W, d->act};
-  const int64_t M = (int64_t)d->B * Ho * Wo;
-  const int rpb = sm_rows_per_block(M);
-  const int parts = (int)cdiv(M, rpb);
+  const int rpb = P.rows_per_block, parts = P.parts, ipg = P.ipg, G = P.groups;
   float *part = align256<float>(workspace);
-  const int items = kk * ((C + 3) / 4);
-  const int ipg = std::min(1024, (items + 63) / 64 * 64), G = std::max(1, 1024 / ipg);   // items per group, groups per workgroup
-  const dim3 grid((unsigned)parts, (unsigned)cdiv(items, ipg));
+  const dim3 grid((unsigned)parts, (unsigned)P.grid_y);
   hipStream_t s = (hipStream_t)stream;
-  const bool v4 = sm_vec4(d);
+  const bool v4 = P.vec4;
   const float rWo = 1.0f / (float)Wo, rHW = 1.0f / (float)(Ho * Wo);
 #define CALL(N)                                                                                                                                  \
   if (d->k == 3) {                                                                                                                               \

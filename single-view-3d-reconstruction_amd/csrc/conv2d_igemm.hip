@@ -22,6 +22,7 @@
 // operand, 9 times per virtual pixel): svr_conv2d_virtual writes the activated, upsampled, concatenated input once (1x the
 // activation, where the patch matrix was 9x) and the convolution reads that.
 #include "common.h"
+#include "conv2d_plan.h"
 #include "conv2d_virt.h"
 #include "f16x3.h"
 #include <algorithm>
@@ -34,6 +35,7 @@ constexpr int GK = 16;           // reduction elements per step (one MFMA depth)
 constexpr int GLW = 8;           // dwords per LDS row of a plane: 16 halves
 constexpr int GTM = 128;         // tile rows
 constexpr int GAPLANE = GTM * GLW;
+static_assert(GK == CV2_GK && GTM == CV2_TM, "cv2_ig_plan (conv2d_plan.h) counts 128-row tiles and k-steps of 16");
 
 // LDS planes: slot_dw / frag_f16 of f16x3.h (conflict-free ds_read_b128 on unpadded rows), as gemm_f16x3.hip
 
@@ -398,45 +400,25 @@ __global__ __launch_bounds__(256) void ig_split_many_kernel(const IgPrepTable T,
   }
 }
 
-int pad16(int c) { return (c + 15) / 16 * 16; }
+int pad16(int c) { return cv2_pad16(c); }
 
-int ig_check(const svr_conv2d_desc *d, int Cout, const char *what) {
-  SVR_CHECK(d && d->src0 && d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0 && Cout > 0, SVR_E_BADARG, "%s: bad descriptor", what);
-  SVR_CHECK(d->C1 == 0 || d->src1, SVR_E_BADARG, "%s: C1 = %d without a second source", what, d->C1);
-  SVR_CHECK((d->k == 4 && d->stride == 2) || (d->k == 3 && d->stride == 1) || (d->k == 1 && d->stride == 1), SVR_E_UNSUPPORTED,
-            "%s: k=%d stride=%d (k4 s2 p1 / k3 s1 p1 / k1 s1 p0)", what, d->k, d->stride);
-  SVR_CHECK(d->act >= 0 && d->act <= 2, SVR_E_BADARG, "%s: act %d", what, d->act);
-  SVR_CHECK(!d->upsample, SVR_E_UNSUPPORTED, "%s: the x2 upsample is materialised first (svr_conv2d_virtual)", what);
-  SVR_CHECK((int64_t)d->B * d->H * d->W < (1 << 24), SVR_E_UNSUPPORTED, "%s: %ld pixels (row decode limit 2^24)", what,
-            (long)d->B * d->H * d->W);
-  return SVR_OK;
-}
-
-// reduction splits: enough workgroups to fill the chip (512 four-wave or 1 024 two-wave ones: two waves per SIMD -- a k-step is a
-// dependent chain load -> split -> LDS -> MFMA, and with one wave per SIMD the 512-tile layers ran at 2.8 us per k-step;
-// profiles/r04_unet_split_target.txt), at least 8 k-steps each
-int ig_splits(int64_t tiles, int ksteps, int n_out, int *ksplit) {
-  const int target = n_out <= 64 ? 1024 : 512;
-  int splits = (int)std::min<int64_t>(std::max<int64_t>(1, target / std::max<int64_t>(tiles, 1)), std::max(1, ksteps / 8));
-  splits = std::min(splits, 64);
-  *ksplit = (int)cdiv(ksteps, splits);
-  return (int)cdiv(ksteps, *ksplit);
+Cv2Query ig_query(int op, const svr_conv2d_desc *d, int Cout, const void *dY, const void *out) {
+  return Cv2Query{op, d->B, d->H, d->W, d->C0, d->C1, Cout, d->k, d->stride, d->act, d->upsample, cv2_lo4(d->src0), cv2_lo4(d->src1),
+                  cv2_lo4(dY), cv2_lo4(out)};
 }
 
 template <bool VEC4>
-void ig_launch(const IgGeom &G, int ncls, int64_t mtiles, int splits, const uint16_t *planes, const uint32_t *amax_w,
+void ig_launch(const IgGeom &G, const svr_conv2d_plan &P, const uint16_t *planes, const uint32_t *amax_w,
                const uint32_t *amax_x, const float *bias, float *Y, float *partial, uint32_t *amax_y, hipStream_t s) {
-  if (G.N <= 64) {
+  const int ncls = P.classes, splits = P.splits;
+  const int64_t mtiles = P.mtiles;
+  if (P.family == SVR_CV2_IGEMM64) {
     dim3 grid(xcd_grid(cdiv(G.N, 64) * mtiles), ncls, splits);
     hipLaunchKernelGGL((conv2d_igemm_kernel<64, VEC4>), grid, dim3(128), 0, s, G, planes, amax_w, amax_x, bias, Y, partial, amax_y);
   } else {
     dim3 grid(xcd_grid(cdiv(G.N, 128) * mtiles), ncls, splits);
     hipLaunchKernelGGL((conv2d_igemm_kernel<128, VEC4>), grid, dim3(256), 0, s, G, planes, amax_w, amax_x, bias, Y, partial, amax_y);
   }
-}
-
-bool vec4_ok(const CvSrc &S) {
-  return S.C0 % 4 == 0 && S.C1 % 4 == 0 && (((uintptr_t)S.p0 | (uintptr_t)S.p1) & 15) == 0;
 }
 
 // a layer's weight planes (hi, lo): the forward's, then the backward-data's
@@ -504,49 +486,50 @@ extern "C" int svr_conv2d_prepare_many(int32_t n, const float *const *W, const i
 }
 
 extern "C" int64_t svr_conv2d_workspace_bytes(const svr_conv2d_desc *d, int32_t Cout) {
-  // partial outputs of the reduction splits, forward (B Ho Wo Cout) or backward-data (B H W C): at most 64 splits, and only
-  // where there are fewer than 512 tiles -- bound by 64 * 512 tiles * 128 * 128 floats; sized exactly instead:
+  // partial outputs of the reduction splits, forward (B Ho Wo Cout) or backward-data (B H W C), sized exactly by the plans the
+  // two launchers run on (a refused plan needs nothing; k = 1 is forward only)
   if (!d) return 0;
-  const int C = d->C0 + d->C1;
-  const int pad = d->k == 1 ? 0 : 1, Ho = (d->H + 2 * pad - d->k) / d->stride + 1, Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-  int ks;
-  const int64_t mf = cdiv((int64_t)d->B * Ho * Wo, GTM) * cdiv(Cout, Cout <= 64 ? 64 : 128);
-  const int sf = ig_splits(mf, d->k * d->k * pad16(C) / GK, Cout, &ks);
-  const int64_t fwd = sf > 1 ? (int64_t)sf * d->B * Ho * Wo * Cout * 4 : 0;
-  const int ncls = d->stride == 2 ? 4 : 1;
-  const int64_t mb = cdiv((int64_t)d->B * cdiv(d->H, d->stride) * cdiv(d->W, d->stride), GTM) * cdiv(C, C <= 64 ? 64 : 128);
-  const int sb = ig_splits(mb * ncls, (d->stride == 2 ? 4 : 9) * pad16(Cout) / GK, C, &ks);
-  const int64_t bwd = (sb > 1 && d->k != 1) ? (int64_t)sb * d->B * d->H * d->W * C * 4 : 0;   // (k = 1: forward only)
+  svr_conv2d_plan pf, pb;
+  const int64_t fwd = cv2_ig_plan(ig_query(SVR_CV2_FWD, d, Cout, nullptr, nullptr), pf) == SVR_OK ? pf.workspace_bytes : 0;
+  const int64_t bwd = cv2_ig_plan(ig_query(SVR_CV2_BWD_DATA, d, Cout, nullptr, nullptr), pb) == SVR_OK ? pb.workspace_bytes : 0;
   return align256(std::max(fwd, bwd)) + 256;
+}
+
+extern "C" int svr_conv2d_variant(int32_t op, int32_t B, int32_t H, int32_t W, int32_t C0, int32_t C1, int32_t Cout, int32_t k, int32_t stride,
+                                  int32_t lo_src0, int32_t lo_src1, int32_t lo_dy, int32_t lo_out, svr_conv2d_plan *plan) {
+  SVR_CHECK(op == SVR_CV2_FWD || op == SVR_CV2_BWD_DATA || op == SVR_CV2_BWD_WEIGHT, SVR_E_BADARG, "conv2d_variant: unknown op %d", op);
+  svr_conv2d_plan p;
+  const int rc = cv2_plan(Cv2Query{op, B, H, W, C0, C1, Cout, k, stride, 0, 0, (unsigned)lo_src0 & 15, (unsigned)lo_src1 & 15,
+                                   (unsigned)lo_dy & 15, (unsigned)lo_out & 15}, p);
+  if (plan) *plan = p;
+  return rc;
 }
 
 extern "C" int svr_conv2d_fwd(const svr_conv2d_desc *d, const void *planes, const uint32_t *amax_w, const float *bias, float *Y,
                               int32_t Cout, const uint32_t *amax_x, uint32_t *amax_y, void *workspace, void *stream) {
-  if (int rc = ig_check(d, Cout, "conv2d_fwd")) return rc;
-  SVR_CHECK(planes && amax_w && Y, SVR_E_BADARG, "conv2d_fwd: null pointer");
-  const int pad = d->k == 1 ? 0 : 1;
-  const int C = d->C0 + d->C1, Ho = (d->H + 2 * pad - d->k) / d->stride + 1, Wo = (d->W + 2 * pad - d->k) / d->stride + 1;
-  SVR_CHECK(Ho > 0 && Wo > 0, SVR_E_BADSHAPE, "conv2d_fwd: empty output");
+  SVR_CHECK(d && d->src0 && planes && amax_w && Y, SVR_E_BADARG, "conv2d_fwd: null pointer");
+  SVR_CHECK(d->C1 == 0 || d->src1, SVR_E_BADARG, "conv2d_fwd: C1 = %d without a second source", d->C1);
+  svr_conv2d_plan P;
+  if (int rc = cv2_ig_plan(ig_query(SVR_CV2_FWD, d, Cout, nullptr, Y), P)) return rc;
+  const int C = d->C0 + d->C1;
   IgGeom G{};
   G.S = CvSrc{d->src0, d->src1, d->C0, d->C1, d->H, d->W, d->act};
-  G.B = d->B; G.mode = 0; G.k = d->k; G.stride = d->stride; G.pad = pad; G.Qh = Ho; G.Qw = Wo;
-  G.Cpad = pad16(C); G.N = Cout; G.ksteps = d->k * d->k * G.Cpad / GK; G.class_stride = 0;
-  const int64_t mtiles = cdiv((int64_t)d->B * Ho * Wo, GTM);
-  const int splits = ig_splits(mtiles * cdiv(Cout, Cout <= 64 ? 64 : 128), G.ksteps, Cout, &G.ksplit);
-  G.split_stride = (int64_t)d->B * Ho * Wo * Cout;
+  G.B = d->B; G.mode = 0; G.k = d->k; G.stride = d->stride; G.pad = d->k == 1 ? 0 : 1; G.Qh = P.Ho; G.Qw = P.Wo;
+  G.Cpad = pad16(C); G.N = Cout; G.ksteps = P.ksteps; G.ksplit = P.ksplit; G.class_stride = 0;
+  G.split_stride = P.split_stride;
   float *partial = nullptr;
-  if (splits > 1) {
-    SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_fwd: %d reduction splits need the workspace", splits);
+  if (P.splits > 1) {
+    SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_fwd: %d reduction splits need the workspace", P.splits);
     partial = align256<float>(workspace);
   }
   WsCursor c(planes);
   const uint16_t *pf = ig_planes_layout(c, Cout, C, d->k).pf;
   hipStream_t s = (hipStream_t)stream;
-  if (vec4_ok(G.S)) ig_launch<true>(G, 1, mtiles, splits, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
-  else ig_launch<false>(G, 1, mtiles, splits, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
-  if (splits > 1)
-    hipLaunchKernelGGL(ig_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(G.split_stride, 1024), 1024)), dim3(256), 0, s,
-                       (const float *)partial, G.split_stride, splits, bias, Y, G.split_stride, Cout, amax_y);
+  if (P.vec4) ig_launch<true>(G, P, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
+  else ig_launch<false>(G, P, pf, amax_w, amax_x, bias, Y, partial, amax_y, s);
+  if (P.splits > 1)
+    hipLaunchKernelGGL(ig_reduce_kernel, dim3((unsigned)P.reduce_grid), dim3(256), 0, s, (const float *)partial, G.split_stride, P.splits,
+                       bias, Y, G.split_stride, Cout, amax_y);
   return launch_status("conv2d_fwd");
 }
 
@@ -554,31 +537,30 @@ extern "C" int svr_conv2d_fwd(const svr_conv2d_desc *d, const void *planes, cons
 // activation's derivative (and the upsample adjoint) and splits it over the two sources.
 extern "C" int svr_conv2d_bwd_data(const svr_conv2d_desc *d, const void *planes, const uint32_t *amax_w, const float *dY,
                                    const uint32_t *amax_dy, int32_t Cout, float *dIn, void *workspace, void *stream) {
-  if (int rc = ig_check(d, Cout, "conv2d_bwd_data")) return rc;
-  SVR_CHECK(planes && amax_w && dY && dIn, SVR_E_BADARG, "conv2d_bwd_data: null pointer");
-  const int C = d->C0 + d->C1, Ho = (d->H + 2 - d->k) / d->stride + 1, Wo = (d->W + 2 - d->k) / d->stride + 1;
+  SVR_CHECK(d && d->src0 && planes && amax_w && dY && dIn, SVR_E_BADARG, "conv2d_bwd_data: null pointer");
+  SVR_CHECK(d->C1 == 0 || d->src1, SVR_E_BADARG, "conv2d_bwd_data: C1 = %d without a second source", d->C1);
+  svr_conv2d_plan P;
+  if (int rc = cv2_ig_plan(ig_query(SVR_CV2_BWD_DATA, d, Cout, dY, dIn), P)) return rc;
+  const int C = d->C0 + d->C1;
   IgGeom G{};
-  G.S = CvSrc{dY, nullptr, Cout, 0, Ho, Wo, 0};
-  G.B = d->B; G.mode = d->stride == 2 ? 2 : 1; G.k = d->k; G.stride = d->stride; G.pad = 1; G.Qh = d->H; G.Qw = d->W;
+  G.S = CvSrc{dY, nullptr, Cout, 0, P.Ho, P.Wo, 0};
+  G.B = d->B; G.mode = P.classes == 4 ? 2 : 1; G.k = d->k; G.stride = d->stride; G.pad = 1; G.Qh = d->H; G.Qw = d->W;
   G.Cpad = pad16(Cout); G.N = C;
-  const int taps = G.mode == 2 ? 4 : d->k * d->k, ncls = G.mode == 2 ? 4 : 1;
-  G.ksteps = taps * G.Cpad / GK;
-  G.class_stride = 2LL * taps * G.Cpad * C;
-  const int64_t mtiles = cdiv((int64_t)d->B * cdiv(d->H, G.mode == 2 ? 2 : 1) * cdiv(d->W, G.mode == 2 ? 2 : 1), GTM);
-  const int splits = ig_splits(mtiles * ncls * cdiv(C, C <= 64 ? 64 : 128), G.ksteps, C, &G.ksplit);
-  G.split_stride = (int64_t)d->B * d->H * d->W * C;
+  G.ksteps = P.ksteps; G.ksplit = P.ksplit;
+  G.class_stride = 2LL * P.ksteps * GK * C;      // (taps * Cpad = ksteps * 16 halves per row, two planes)
+  G.split_stride = P.split_stride;
   float *partial = nullptr;
-  if (splits > 1) {
-    SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_bwd_data: %d reduction splits need the workspace", splits);
+  if (P.splits > 1) {
+    SVR_CHECK(workspace, SVR_E_BADARG, "conv2d_bwd_data: %d reduction splits need the workspace", P.splits);
     partial = align256<float>(workspace);
   }
   WsCursor c(planes);
   const uint16_t *pb = ig_planes_layout(c, Cout, C, d->k).pb;
   hipStream_t s = (hipStream_t)stream;
-  if (vec4_ok(G.S)) ig_launch<true>(G, ncls, mtiles, splits, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);
-  else ig_launch<false>(G, ncls, mtiles, splits, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);
-  if (splits > 1)
-    hipLaunchKernelGGL(ig_reduce_kernel, dim3((unsigned)std::min<int64_t>(cdiv(G.split_stride, 1024), 1024)), dim3(256), 0, s,
-                       (const float *)partial, G.split_stride, splits, (const float *)nullptr, dIn, G.split_stride, C, (uint32_t *)nullptr);
+  if (P.vec4) ig_launch<true>(G, P, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);
+  else ig_launch<false>(G, P, pb, amax_w, amax_dy, nullptr, dIn, partial, nullptr, s);
+  if (P.splits > 1)
+    hipLaunchKernelGGL(ig_reduce_kernel, dim3((unsigned)P.reduce_grid), dim3(256), 0, s, (const float *)partial, G.split_stride, P.splits,
+                       (const float *)nullptr, dIn, G.split_stride, C, (uint32_t *)nullptr);
   return launch_status("conv2d_bwd_data");
 }

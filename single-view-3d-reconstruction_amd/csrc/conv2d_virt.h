@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cv_divmod.h"
 
 namespace {
 
@@ -14,7 +15,12 @@ struct CvSrc {
   int act;               // 0 none, 1 LeakyReLU(0.2), 2 ReLU
 };
 
-__device__ __forceinline__ float cv_act(float v, int act) { return act == 1 ? (v > 0.f ? v : 0.2f * v) : (act == 2 ? fmaxf(v, 0.f) : v); }
+// ReLU keeps a NaN, as torch.relu does (fmaxf returns its non-NaN operand: a NaN entering a decoder block would leave as 0);
+// identical for every other input.  The loaders below select AFTER loading from clamped coordinates, so a NaN reaches exactly
+// the outputs whose window holds it (tests/test_gpu_conv2d_paths.py)
+__device__ __forceinline__ float cv_act(float v, int act) {
+  return act == 1 ? (v > 0.f ? v : 0.2f * v) : (act == 2 ? (v != v ? v : fmaxf(v, 0.f)) : v);
+}
 __device__ __forceinline__ float4 cv_act4(float4 v, int act) {
   return make_float4(cv_act(v.x, act), cv_act(v.y, act), cv_act(v.z, act), cv_act(v.w, act));
 }
@@ -49,14 +55,6 @@ __device__ __forceinline__ float4 cv_load4(const CvSrc &S, int pix0, int iy, int
     v = make_float4(e[0], e[1], e[2], e[3]);
   }
   return v;
-}
-
-// n / d and n % d for 0 <= n < 2^24, 0 < d < 2^24 through one float multiply (rcp = 1.0f / d) and one correction step
-__device__ __forceinline__ void cv_divmod(int n, int d, float rcp, int &q, int &r) {
-  q = (int)((float)n * rcp);
-  r = n - q * d;
-  if (r < 0) { --q; r += d; }
-  else if (r >= d) { ++q; r -= d; }
 }
 
 }  // namespace

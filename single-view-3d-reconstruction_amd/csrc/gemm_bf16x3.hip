@@ -20,6 +20,7 @@
 #include "common.h"
 #define SVR_GEMM_PLAN_ONLY
 #include "gemm_core.h"
+#include "conv2d_plan.h"
 #include "conv2d_virt.h"
 #include "f16x3.h"
 
@@ -879,44 +880,36 @@ struct ConvWgradWs { float *slab, *dbpart; };
 ConvWgradWs conv_wgrad_layout(WsCursor &c, int64_t N, int64_t K, int splits) {
   return {c.take<float>((int64_t)splits * N * K), c.take<float>((int64_t)splits * N)};
 }
-int conv_wgrad_splits(int64_t M, int64_t N, int64_t K, int64_t *rows_per_split) {
-  const int64_t tiles = cdiv(N, TN_TM) * cdiv(K, TN_TN);
-  const int64_t want = std::max<int64_t>(1, 384 / tiles);         // the slabs are written and read once each: few, long splits
-  int64_t rps = cdiv(cdiv(M, want), XK) * XK;
-  rps = std::max<int64_t>(rps, 4 * XK);
-  *rows_per_split = rps;
-  return (int)cdiv(M, rps);
+static_assert(TN_TM == CV2_WG_TILE && TN_TN == CV2_WG_TILE && XK == CV2_WG_XK, "cv2_wgrad_plan (conv2d_plan.h) counts 128 x 128 tiles and k-steps of 32");
+Cv2Query conv_wgrad_query(const svr_conv2d_desc *d, int Cout, const void *dY) {
+  return Cv2Query{SVR_CV2_BWD_WEIGHT, d->B, d->H, d->W, d->C0, d->C1, Cout, d->k, d->stride, d->act, d->upsample, cv2_lo4(d->src0),
+                  cv2_lo4(d->src1), cv2_lo4(dY), 0};
 }
 }  // namespace
 
 extern "C" int64_t svr_conv2d_bwd_weight_workspace(const svr_conv2d_desc *d, int32_t Cout) {
   if (!d) return 0;
-  const int C = d->C0 + d->C1, Cpad = (C + 15) / 16 * 16;
-  const int Ho = (d->H + 2 - d->k) / d->stride + 1, Wo = (d->W + 2 - d->k) / d->stride + 1;
-  int64_t rps;
-  const int64_t K = (int64_t)d->k * d->k * Cpad;
-  return ws_measure(conv_wgrad_layout, (int64_t)Cout, K, conv_wgrad_splits((int64_t)d->B * Ho * Wo, Cout, K, &rps));
+  svr_conv2d_plan P;
+  if (cv2_wgrad_plan(conv_wgrad_query(d, Cout, nullptr), P) != SVR_OK) return 0;
+  return ws_measure(conv_wgrad_layout, (int64_t)Cout, (int64_t)d->k * d->k * cv2_pad16(d->C0 + d->C1), (int)P.splits);
 }
 
 extern "C" int svr_conv2d_bwd_weight(const svr_conv2d_desc *d, const float *dY, const uint32_t *amax_dy, int32_t Cout, float *dW,
                                      float *db, void *workspace, void *stream) {
   SVR_CHECK(d && d->src0 && dY && dW && workspace && Cout > 0, SVR_E_BADARG, "conv2d_bwd_weight: null pointer");
-  SVR_CHECK((d->k == 4 && d->stride == 2) || (d->k == 3 && d->stride == 1), SVR_E_UNSUPPORTED, "conv2d_bwd_weight: k=%d stride=%d", d->k, d->stride);
-  SVR_CHECK(!d->upsample, SVR_E_UNSUPPORTED, "conv2d_bwd_weight: the x2 upsample is materialised first (svr_conv2d_virtual)");
   SVR_CHECK(d->C1 == 0 || d->src1, SVR_E_BADARG, "conv2d_bwd_weight: C1 = %d without a second source", d->C1);
-  const int C = d->C0 + d->C1, Cpad = (C + 15) / 16 * 16;
-  const int Ho = (d->H + 2 - d->k) / d->stride + 1, Wo = (d->W + 2 - d->k) / d->stride + 1;
+  svr_conv2d_plan P;
+  if (int rc = cv2_wgrad_plan(conv_wgrad_query(d, Cout, dY), P)) return rc;
+  const int C = d->C0 + d->C1, Cpad = cv2_pad16(C), Ho = P.Ho, Wo = P.Wo;
   const int64_t M = (int64_t)d->B * Ho * Wo, K = (int64_t)d->k * d->k * Cpad, N = Cout;
-  SVR_CHECK(M > 0 && M < (1 << 24) && (int64_t)d->B * d->H * d->W < (1 << 24), SVR_E_UNSUPPORTED, "conv2d_bwd_weight: %ld output pixels (row decode limit 2^24)", (long)M);
   hipStream_t s = (hipStream_t)stream;
-  int64_t rps;
-  const int splits = conv_wgrad_splits(M, N, K, &rps);
+  const int64_t rps = P.rows_per_split;
+  const int splits = P.splits;
   WsCursor c(workspace);
   const auto [slab, dbpart] = conv_wgrad_layout(c, N, K, splits);
   CwGeom G{CvSrc{d->src0, d->src1, d->C0, d->C1, d->H, d->W, d->act}, Wo, Ho * Wo, 1.0f / (float)Wo, 1.0f / (float)(Ho * Wo), d->k, d->stride, 1, Cpad};
-  const bool vec4 = d->C0 % 4 == 0 && d->C1 % 4 == 0 && (((uintptr_t)d->src0 | (uintptr_t)d->src1 | (uintptr_t)dY) & 15) == 0;
-  dim3 grid(xcd_grid(cdiv(K, TN_TN) * cdiv(N, TN_TM) * splits));
-  if (vec4)
+  dim3 grid(xcd_grid(P.tiles * splits));
+  if (P.vec4)
     hipLaunchKernelGGL((linear_tn_x3_tr_kernel<true, true, true>), grid, dim3(256), 0, s, dY, (int64_t)Cout, (const float *)nullptr, (int64_t)0,
                        slab, db ? dbpart : nullptr, M, N, K, rps, splits, amax_dy, G);
   else

@@ -1541,6 +1541,9 @@ ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 def _conv2d_desc(src0, src1, k, stride, act, up):
     _f32(src0, src1)
     B, H, W, C0 = src0.shape
+    if (2 if up else 1) * min(H, W) + 2 * (0 if k == 1 else 1) < k:      # (the library refuses it too: SVR_E_BADSHAPE)
+        raise ValueError(f"conv2d: input {H} x {W}{' upsampled x2' if up else ''} with padding {0 if k == 1 else 1} is smaller than "
+                         f"the {k} x {k} window: no output")
     d = _lib.Conv2dDesc(_p(src0), _p(src1), B, H, W, C0, src1.shape[3] if src1 is not None else 0, k, stride, act, int(up))
     Hv, Wv = (2 * H, 2 * W) if up else (H, W)
     pad = 0 if k == 1 else 1
@@ -1635,7 +1638,8 @@ def _amax_any(t):
     """amax word of a gradient tensor of any element count (amax_of wants multiples of 4 and 16-byte alignment)."""
     if t.numel() % 4 == 0 and t.data_ptr() % 16 == 0:
         return amax_of(t)
-    return t.detach().abs().max().reshape(1).view(torch.int32)
+    a = t.detach().abs()      # (a NaN does not move the scale, as in the kernel's fmaxf: it must poison its own window only)
+    return torch.where(torch.isnan(a), torch.zeros_like(a), a).max().reshape(1).view(torch.int32)
 
 
 def _conv2d_ws(nbytes, device):
@@ -1734,6 +1738,27 @@ def conv2d_bwd_weight(src0, src1, k, stride, act, dy, Cout, want_bias=True):
     check(_lib.lib().svr_conv2d_bwd_weight(C.byref(d), _p(dy), _amax_any(dy).data_ptr(), Cout, _p(dw), _p(db), _p(ws), _stream()),
           "conv2d_bwd_weight")
     return dw, db
+
+
+CONV2D_VARIANT_OPS = {"fwd": 0, "bwd_data": 1, "bwd_weight": 2}      # SVR_CV2_* of svr_hip.h
+CONV2D_FAMILIES = ("small", "igemm64", "igemm128", "wgrad_tr")
+CONV2D_EPILOGUES = ("coal", "lane", "reduce_v4", "reduce_scalar")
+
+
+def conv2d_variant(op, B, H, W, C0, C1, Cout, k, stride, lo_src0=0, lo_src1=0, lo_dy=0, lo_out=0):
+    """What the conv2d op `op` (a key of CONV2D_VARIANT_OPS) does with a layer: the plan its launcher runs on, as a dict
+    (svr_conv2d_variant; host only, no GPU needed).  lo_*: the low four address bits of the sources, dY and the output.
+    "family" is a name of CONV2D_FAMILIES, "epilogue" (the GEMM forward / backward-data) one of CONV2D_EPILOGUES, else None.
+    A layer the entry point refuses raises with its error code and message, as the entry point would."""
+    p = _lib.Conv2dPlan()
+    check(_lib.lib().svr_conv2d_variant(CONV2D_VARIANT_OPS[op], B, H, W, C0, C1, Cout, k, stride, lo_src0, lo_src1, lo_dy, lo_out,
+                                        C.byref(p)), "conv2d_variant")
+    v = {n: int(getattr(p, n)) for n, _ in p._fields_}
+    v["op"], v["family"] = op, CONV2D_FAMILIES[p.family]
+    v["epilogue"] = CONV2D_EPILOGUES[p.epilogue] if v["family"] in ("igemm64", "igemm128") else None
+    for n in ("vec4", "dy_vec4", "capped"):
+        v[n] = bool(v[n])
+    return v
 
 
 # ------------------------------------------------------------------------------------------

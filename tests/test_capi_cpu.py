@@ -365,3 +365,149 @@ def test_linear_variant_refuses_what_the_entry_points_refuse():
     assert q(O["bwd_weight_f16x3s"], 8, 8, 6, (8, 6, 6, 0), (0,) * 4) == (0, -2)
     assert q(O["bwd_weight_bf16x3"], 8, 6, 8, (6, 8, 8, 0), (0,) * 4) == (0, -2)            # N % 4
     assert q(O["bwd_weight_bf16x3"], 8, 8, 6, (8, 6, 6, 0), (0,) * 4) == (0, 0)             # K % 4 != 0: the pre-pass path
+
+
+def test_conv2d_variant_table_and_every_branch_is_reached():
+    """What a UNet 2-D convolution op runs -- kernel family, loader form, parity classes, epilogue form, splits, the small
+    kernels' grids -- asked of the library (svr_conv2d_variant: the plan functions of csrc/conv2d_plan.h, which the launchers of
+    conv2d_igemm.hip, conv2d.hip and gemm_bf16x3.hip and their workspace-size functions themselves call), for every row of
+    tests/_conv2d_cases.py; the rows, together, reach EVERY (op, family, loader, classes, epilogue) the launchers can produce --
+    found by sweeping the query over shapes and address bits, so a launcher branch that gains a variant fails here until a case
+    names it -- and the regimes inside the branches (grid-stride reduce, > 4 slabs, grid.y > 1, capped grids).  The real layers
+    of Unet and UNetMini at num_filters = 32 (batch 1, 2 and 8) are pinned against tests/golden/conv2d_unet_layers.json.  No GPU."""
+    import itertools
+    import json
+    import __graft_entry__ as ge
+    ge.build()
+    from svr_amd import _lib, ops
+    from svr_amd.model import UNetMini, Unet
+    from tests import _conv2d_cases as K
+    assert len({c[0] for c in K.CASES}) == len(K.CASES)
+    reached, extras = set(), set()
+    for name, shape, mis, tags, ext in K.CASES:
+        assert set(tags) == ({"fwd"} if shape[6] == 1 else set(K.OPS)), name
+        got_ext = set()
+        for op, tag in tags.items():
+            v = K.query(ops, op, shape, mis)
+            assert K.tag(v) == tag, (name, op, K.tag(v), tag)
+            reached.add((op, tag))
+            got_ext |= K.extras(v)
+        assert got_ext == set(ext), (name, got_ext, ext)
+        extras |= got_ext
+    assert reached == K.ALL_VARIANTS, sorted(reached ^ K.ALL_VARIANTS)
+    assert extras >= K.ALL_EXTRAS, sorted(K.ALL_EXTRAS - extras)
+    assert len(K.ALL_VARIANTS) == 14 + 28 + 3 + 16 + 8 + 16
+    # everything the launchers can answer with, over a sweep of shapes and address bits
+    seen = set()
+    for (H, W), C0, C1, Cout, (k, s), mis in itertools.product(((6, 5), (40, 36)), (3, 4, 68, 132), (0, 4, 5), (1, 2, 3, 4, 6, 8, 24, 66, 72),
+                                                              ((3, 1), (4, 2)), ((), ("src0",), ("dy",))):
+        for op in K.OPS:
+            seen.add((op, K.tag(K.query(ops, op, (1, H, W, C0, C1, Cout, k, s), mis))))
+    for shape in [c[1] for c in K.CASES]:
+        for op in K.OPS if shape[6] != 1 else ("fwd",):
+            seen.add((op, K.tag(K.query(ops, op, shape))))
+    assert seen == K.ALL_VARIANTS, sorted(seen ^ K.ALL_VARIANTS)
+    # the real layers (DESIGN.md section 4)
+    table = json.load(open(os.path.join(REPO, "tests", "golden", "conv2d_unet_layers.json")))
+    for nm, cls, (H, W) in (("full", Unet, (256, 256)), ("mini", UNetMini, (240, 320))):
+        for B in (1, 2, 8):
+            rows = table[f"{nm}_{H}x{W}_b{B}"]
+            layers = K.unet_layers(cls, B, H, W)
+            assert [r[0] for r in rows] == [n for n, _ in layers]
+            for (name, shape), row in zip(layers, rows):
+                vs = [K.query(ops, op, shape) for op in K.OPS]
+                got = [name, list(shape)] + [K.tag(v) for v in vs] + \
+                      [vs[0]["splits"], vs[1]["splits"], vs[2]["splits"] if vs[2]["family"] != "small" else vs[2]["parts"]]
+                assert got == row, (nm, B, got, row)
+    full8 = {r[0]: r for r in table["full_256x256_b8"]}
+    assert full8["conv1"][2] == "igemm64/s/c1/lane" and full8["conv1"][5] == 1          # 1 024 tiles: the kernel's own epilogue
+    assert full8["conv4"][3] == "igemm128/v4/c4/reduce_v4" and full8["dconv8"][2].startswith("small/")
+    # the workspace-size functions answer from the same plans
+    l = _lib.lib()
+    for _, shape, _, tags, _ in K.CASES:
+        B, H, W, C0, C1, Cout, k, s = shape
+        d = _lib.Conv2dDesc(ctypes.c_void_p(16), ctypes.c_void_p(16) if C1 else None, B, H, W, C0, C1, k, s, 0, 0)
+        if tags["fwd"].startswith("small"):
+            v = K.query(ops, "bwd_weight", shape)
+            assert l.svr_conv2d_small_bwd_weight_workspace(ctypes.byref(d), Cout) == v["workspace_bytes"] + 256
+            continue
+        need = max(K.query(ops, op, shape)["workspace_bytes"] for op in tags if op != "bwd_weight")
+        assert l.svr_conv2d_workspace_bytes(ctypes.byref(d), Cout) == (need + 255) // 256 * 256 + 256, shape
+
+
+def test_conv2d_variant_refuses_what_the_entry_points_refuse():
+    """The query's refusals are the entry points' own (one plan function each): unknown op, bad counts, kernel sizes, the 2^24
+    row-decode limit of ig_check / sm_check / svr_conv2d_bwd_weight, and an input smaller than the window -- where C division
+    (truncating toward zero) used to count one output row for H = 1 at k4 s2 and the ops failed on a null pointer instead."""
+    import pytest
+    import svr_amd  # noqa: F401
+    from svr_amd import _lib, ops
+    l = _lib.lib()
+    q = lambda op, *a: l.svr_conv2d_variant(op, *a, 0, 0, 0, 0, None)     # noqa: E731  (the plan may be NULL)
+    ok = (2, 9, 7, 16, 0, 40, 3, 1)
+    assert [q(op, *ok) for op in (0, 1, 2)] == [0, 0, 0] and q(3, *ok) == -1 and q(-1, *ok) == -1
+    for op in (0, 1, 2):
+        assert q(op, 0, 9, 7, 16, 0, 40, 3, 1) == -1 and q(op, 2, 9, 7, 0, 0, 40, 3, 1) == -1 and q(op, 2, 9, 7, 16, -1, 40, 3, 1) == -1
+        assert q(op, 2, 9, 7, 16, 0, 0, 3, 1) == -1
+        assert q(op, 2, 9, 7, 16, 0, 40, 3, 2) == -4 and q(op, 2, 9, 7, 16, 0, 40, 5, 1) == -4
+        assert q(op, 2, 9, 7, 16, 0, 2, 5, 1) == -4                                   # the small kernels: k3 s1 / k4 s2 only
+        # 2^24 pixels: the float row decode (cv_divmod) and the 32-bit pixel indices end there
+        assert q(op, 1, 4096, 4096, 16, 0, 40, 3, 1) == -4 and q(op, 1, 4096, 4095, 16, 0, 40, 3, 1) == 0
+        assert q(op, 1, 4096, 4096, 16, 0, 2, 3, 1) == -4 and q(op, 1, 4096, 4095, 16, 0, 2, 3, 1) == 0
+        assert q(op, 4, 2048, 2048, 4, 0, 8, 4, 2) == -4 and q(op, 4, 2048, 2047, 4, 0, 8, 4, 2) == 0
+        # no output pixel: H + 2 < k
+        for shape in ((1, 1, 8, 16, 0, 40, 4, 2), (1, 8, 1, 16, 0, 40, 4, 2), (1, 1, 1, 16, 0, 2, 4, 2)):
+            assert q(op, *shape) == -2, (op, shape)
+            assert b"smaller than the 4 x 4 window" in l.svr_last_error() and b"1" in l.svr_last_error()
+        assert q(op, 1, 2, 2, 16, 0, 40, 4, 2) == 0 and q(op, 1, 1, 1, 16, 0, 40, 3, 1) == 0
+    assert q(0, 1, 1, 40, 16, 0, 16, 1, 1) == 0 and q(1, 1, 1, 40, 16, 0, 16, 1, 1) == -4 and q(2, 1, 1, 40, 16, 0, 16, 1, 1) == -4   # k = 1: forward only
+    with pytest.raises(RuntimeError, match="smaller than the 4 x 4 window"):
+        ops.conv2d_variant("fwd", 1, 1, 8, 16, 0, 40, 4, 2)
+    # the entry points themselves, before any launch (host checks; the pointers are never followed)
+    P = ctypes.c_void_p
+    for H, W in ((1, 8), (8, 1)):
+        d = _lib.Conv2dDesc(P(256), None, 1, H, W, 16, 0, 4, 2, 0, 0)
+        r = ctypes.byref(d)
+        assert l.svr_conv2d_fwd(r, P(256), P(256), None, P(256), 40, None, None, P(256), None) == -2
+        assert l.svr_conv2d_bwd_data(r, P(256), P(256), P(256), None, 40, P(256), P(256), None) == -2
+        assert l.svr_conv2d_bwd_weight(r, P(256), None, 40, P(256), None, P(256), None) == -2
+        assert l.svr_conv2d_small_fwd(r, P(256), None, P(256), 2, None) == -2
+        assert l.svr_conv2d_small_bwd_data(r, P(256), P(256), 2, P(256), None) == -2
+        assert l.svr_conv2d_small_bwd_weight(r, P(256), 2, P(256), None, P(256), None) == -2
+        assert l.svr_conv2d_im2col(r, P(256), None) == -2 and l.svr_conv2d_col2im(r, P(256), P(256), P(256), None, None) == -2
+        assert b"smaller than the 4 x 4 window" in l.svr_last_error()
+        # ... and the ops refuse on the host with the sizes, before they allocate
+        x = torch.zeros(1, H, W, 16)
+        for call in (lambda: ops.conv2d_im2col(x, None, 4, 2, 0, False), lambda: ops.conv2d_bwd_weight(x, None, 4, 2, 0, x, 40)):
+            with pytest.raises(ValueError, match=f"input {H} x {W} .* smaller than the 4 x 4 window"):
+                call()
+
+
+def test_conv2d_plan_struct_matches_the_header(tmp_path):
+    """svr_conv2d_plan of include/svr_hip.h, compiled as plain C, against its ctypes mirror: size and every field's offset."""
+    import subprocess
+    import svr_amd
+    Pl = svr_amd._lib.Conv2dPlan
+    names = [n for n, _ in Pl._fields_]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "svr_hip.h"', 'int main(void) {', '  printf("%zu\\n", sizeof(svr_conv2d_plan));']
+    lines += [f'  printf("%zu\\n", offsetof(svr_conv2d_plan, {n}));' for n in names] + ['  return 0;', '}']
+    (tmp_path / "plan.c").write_text("\n".join(lines))
+    exe = tmp_path / "plan"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(REPO, "include"), str(tmp_path / "plan.c"), "-o", str(exe)], check=True)
+    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert out == [ctypes.sizeof(Pl)] + [getattr(Pl, n).offset for n in names]
+
+
+def test_cv_divmod_one_correction_step_suffices(tmp_path):
+    """csrc/cv_divmod.h -- the row decode of the UNet's weight-gradient kernels -- built with g++ into tests/host/cv_divmod_driver.cpp:
+    q, r equal n / d, n % d exhaustively in n < 2^24 for the network's divisors and d = 1, 2, 3, 2^k +- 1, 2^24 - 1, and at the
+    multiples of d +- 1 for a sweep of d."""
+    import subprocess
+    exe = tmp_path / "cv_divmod_driver"
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-I",
+                    os.path.join(REPO, "single-view-3d-reconstruction_amd", "csrc"),
+                    os.path.join(REPO, "tests", "host", "cv_divmod_driver.cpp"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.returncode, r.stdout[-500:], r.stderr[-500:])
+    divisors, checks = (int(x) for x in r.stdout.split()[1:3])
+    assert divisors >= 60 and checks > 60 * (1 << 24)
