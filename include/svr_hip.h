@@ -1225,6 +1225,70 @@ int svr_mesh_smooth(const float *verts, int64_t V, const int32_t *faces, int64_t
                     int32_t fix_boundary, void *ws, int64_t ws_bytes, float *out_verts, uint8_t *state, int64_t *counts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Shaded previews of a mesh: area-weighted vertex normals, a shading pass over the ray caster's face map, and the box
+ * filter behind supersampling (no reference op: the reference shows pictures of its meshes but ships no code for them;
+ * util/mesh_render.py drives this, tests/mesh_render_oracle.py restates it in numpy).  Errors,
+ * ownership and streams as for svr_mc_*.  Both units are built with -ffp-contract=off: one rounding per float64 operation.
+ *
+ * svr_mesh_vertex_normals.  verts: (V, 3) float32, faces: (F, 3) int32, on the device, 0 <= V < 2^31, 0 <= F <= 2^28 (else
+ * SVR_E_BADSHAPE).  The rule is all-integer up to the final normalisation, so no output bit depends on the order of atomics:
+ *     1. a vertex is USABLE iff its three coordinates are finite and each |v_a| < 2^16 (svr_mesh_smooth's rule).
+ *     2. a face is VALID iff its three indices lie in [0, V), are pairwise distinct, and name usable vertices (the indices are
+ *        compared before any of them addresses memory).  Repeated valid faces each count.
+ *     3. q_a = (int64) rint((double)v_a * 1024), ties to even (the product is exact), so |q_a| <= 2^26.
+ *     4. per valid face (a, b, c): e1 = q_b - q_a, e2 = q_c - q_a, n = e1 x e2 component by component in int64,
+ *        (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), each |n_a| <= 2^55; n is added to the accumulators of a, of b
+ *        and of c.  The sums are taken modulo 2^64 (two's complement wrap), so they are defined, and equal to numpy's int64,
+ *        even where they overflow; below 256 faces per vertex no overflow is possible.
+ *     5. per vertex: x, y, z = (double) of the three sums (read as signed); len = sqrt((x*x + y*y) + z*z); if len > 0 the
+ *        normal is ((float)(x / len), (float)(y / len), (float)(z / len)), else (0, 0, 0).
+ *     6. STATE (uint8), the first that applies: 3 = not usable; 1 = in no valid face, or a zero sum (len is not > 0);
+ *        0 = has a normal.  counts (DEVICE int64 x 3) = the number of vertices in states 0, 1, 3, in this order.
+ *   The direction follows the faces' winding (counter-clockwise seen from the side the normal points to); nothing is flipped.
+ *   out: (V, 3) float32; state: (V,) uint8.  out overlapping verts and a workspace that is too small are SVR_E_BADARG; every
+ *   refusal happens before anything is enqueued.  ws: svr_mesh_vertex_normals_workspace_bytes(V, F) device bytes (negative =
+ *   SVR_E_BADSHAPE); needs no zeroing.  Asynchronous, no host synchronisation.  V == 0: only counts is written.  F == 0:
+ *   every normal is 0, every state 1 or 3, ws may be null.
+ *
+ * svr_mesh_shade.  tri: the ray caster's (F, 9) float64 table; faces: (F, 3) int32 (may be null when normals and colors are);
+ * face_map: the `face` output of svr_raycast_eval for the SAME tri, consts and image, (H, W) int32, negative = miss; consts:
+ * the 12 float32 constants in HOST memory, widened first; normals: (V, 3) float32 or null; colors: (V, 3) uint8 or null;
+ * albedo, background: 3 HOST uint8 each; ambient: float32 with 0 <= ambient <= 1 (else SVR_E_BADARG); rgb: (H, W, 3) uint8.
+ * All of tri ... rgb but consts, albedo and background are on the device.  Per pixel (u = column, v = row), float64, one
+ * rounding per operation, dot and cross as for svr_raycast_*:
+ *     1. a miss, or a face index outside [0, F): rgb = background.
+ *     2. d = the ray direction of svr_raycast_*; o = (t0, t1, t2); with a, b, c of the face, by the expressions of the pair test:
+ *        e1 = b - a; e2 = c - a; p = d x e2; det = dot(e1, p); inv = 1 / det; s = o - a; bu = dot(s, p) * inv; q = s x e1;
+ *        bv = dot(d, q) * inv; w0 = (1 - bu) - bv.  det == 0 cannot occur for a face the caster accepted; in a map from
+ *        elsewhere such a pixel takes background.
+ *     3. the shading normal: with normals and the face's three indices i0, i1, i2 in [0, V): N_a = (w0*n0_a + bu*n1_a) + bv*n2_a
+ *        (the float32 normals widened), len = sqrt(dot(N, N)), and N / len per component when len > 0.  In every other case (no
+ *        normals, len not > 0 -- NaN included --, an index outside [0, V)): the face's unit normal turned against the ray, as
+ *        svr_raycast_eval's `normal` computes it (m = (e1 x e2) / |e1 x e2|, negated when dot(m, d) > 0).
+ *     4. c = |dot(N, d)| / sqrt(dot(d, d)): the light is at the camera and the surface is two-sided, so it is never black from
+ *        behind;  I = a + (1 - a) * c  with a = (double)ambient.
+ *     5. the base colour per channel: with colors and the three indices in [0, V), (w0*c0 + bu*c1) + bv*c2 of the three
+ *        vertices' bytes widened; else albedo.
+ *     6. rgb = rint(base * I), half to even, clamped to [0, 255]; NaN gives 0.
+ *   One thread per pixel, no LDS, no atomics; a face or vertex index outside its range never becomes an address.  F == 0: every
+ *   pixel is background.
+ *
+ * svr_box_downsample_rgb8.  src (s*H, s*W, 3) uint8 -> dst (H, W, 3) uint8, s in {1, 2, 3, 4} (else SVR_E_BADARG), on the
+ * device, not overlapping: per channel (sum of the s x s block + s*s/2) / (s*s) in integers -- the mean rounded half up.
+ * Supersampling: the fine image is rendered with f' = s*f, cx' = s*cx + (s - 1)/2, cy' = s*cy + (s - 1)/2, computed in float64
+ * on the host from the float32 constants and rounded to float32 (the other nine unchanged).  Fine pixel s*u + i then sees the
+ * direction of coarse position u + (i - (s - 1)/2) / s: sub-pixel i lies at offset (i - (s - 1)/2) / s from the pixel centre,
+ * the s x s sub-pixels tile the pixel evenly.
+ * ------------------------------------------------------------------------------------- */
+int64_t svr_mesh_vertex_normals_workspace_bytes(int64_t V, int64_t F);
+int svr_mesh_vertex_normals(const float *verts, int64_t V, const int32_t *faces, int64_t F, void *ws, int64_t ws_bytes, float *out,
+                            uint8_t *state, int64_t *counts, void *stream);
+int svr_mesh_shade(const double *tri, const int32_t *faces, int64_t F, int64_t V, const int32_t *face_map, const float *consts /*[12]*/,
+                   int32_t H, int32_t W, const float *normals, const uint8_t *colors, const uint8_t *albedo /*[3]*/,
+                   const uint8_t *background /*[3]*/, float ambient, uint8_t *rgb, void *stream);
+int svr_box_downsample_rgb8(const uint8_t *src, int32_t H, int32_t W, int32_t s, uint8_t *dst, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Sample wire formats (replaces the Python loaders of dataset/implicit_dataset.py:24-56,
  * data_processing/volume_reader.py:36-45 and the np.load calls on process_sample.py:19-30's outputs).
  * The files are read on the host (svr_df_* / svr_npz_*: File formats, below).
@@ -1394,6 +1458,8 @@ int svr_grid_to_camera(const float *src, float *dst, int64_t n, const float *sca
  * Meshes and images, written (svr_mc_*, svr_voxel_mesh_*, svr_vertex_color_*, svr_depth_planes make the arrays):
  *   svr_write_obj: host only; verts (nv, 3) float32 and faces (nf, 3) int32 HOST arrays -> `v x y z` lines (%.9g,
  *                  float32 round trip) then `f a b c` lines (1-based).  SVR_E_IO on a failed open / write.
+ *   svr_write_obj_normals: the same with normals (nv, 3) float32, one per vertex: the `v` lines, then `vn x y z` lines
+ *                  (%.9g), then `f a//a b//b c//c` lines (1-based; a vertex and its normal share the index).
  *   svr_write_ply: host only; verts (nv, 3) float32, colors (nv, 3) uint8 and faces (nf, 3) int32 HOST arrays -> a binary
  *     little-endian PLY: the header below (LF line ends, the two counts in decimal), then per vertex 12 + 3 bytes (x, y, z,
  *     red, green, blue), then per face 1 + 12 bytes (the count 3, three indices, 0-based).  SVR_E_IO on a failed open / write.
@@ -1411,6 +1477,7 @@ int svr_grid_to_camera(const float *src, float *dst, int64_t n, const float *sca
  *       end_header
  *   svr_write_png_gray8: data (H, W) uint8 -> a PNG file: signature, IHDR (bit depth 8, colour type 0, no interlace), one
  *     zlib-deflated IDAT with filter type 0 on every scanline, IEND, CRC-32 on every chunk.
+ *   svr_write_png_rgb8: data (H, W, 3) uint8 -> the same format with colour type 2 (RGB), three bytes per pixel.
  *   svr_write_obj_points: pts (n, 3) float32 -> one line `v %f %f %f %f %f %f` per point: the coordinates + 0.5 (added in
  *     float32, then widened) and the colour 1 1 1 (visualize_point_list, util/visualize.py:14-20).  n == 0: an empty file.
  *
@@ -1434,6 +1501,8 @@ int svr_grid_to_camera(const float *src, float *dst, int64_t n, const float *sca
 int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf);
 int svr_write_ply(const char *path, const float *verts, const uint8_t *colors, int64_t nv, const int32_t *faces, int64_t nf);
 int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W);
+int svr_write_png_rgb8(const char *path, const uint8_t *data, int32_t H, int32_t W);
+int svr_write_obj_normals(const char *path, const float *verts, const float *normals, int64_t nv, const int32_t *faces, int64_t nf);
 int svr_write_obj_points(const char *path, const float *pts, int64_t n);
 int svr_df_dims(const char *path, int64_t *dims /*[3]*/);
 int svr_df_read(const char *path, float *payload, int64_t n);

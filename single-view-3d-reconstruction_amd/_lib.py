@@ -201,6 +201,10 @@ SIGNATURES = {
     "svr_mesh_simplify_emit": (C.c_int, [P, I64, P, I64, P, I64, P, P, P, P, P]),
     "svr_mesh_smooth_workspace_bytes": (I64, [I64, I64]),
     "svr_mesh_smooth": (C.c_int, [P, I64, P, I64, I32, F32, F32, I32, P, I64, P, P, P, P]),
+    "svr_mesh_vertex_normals_workspace_bytes": (I64, [I64, I64]),
+    "svr_mesh_vertex_normals": (C.c_int, [P, I64, P, I64, P, I64, P, P, P, P]),
+    "svr_mesh_shade": (C.c_int, [P, P, I64, I64, P, C.POINTER(F32), I32, I32, P, P, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), F32, P, P]),
+    "svr_box_downsample_rgb8": (C.c_int, [P, I32, I32, I32, P, P]),
     "svr_mc_workspace_bytes": (I64, [I32, I32, I32]),
     "svr_mc_count": (C.c_int, [P, I32, I32, I32, C.c_double, P, I64, P, P]),
     "svr_mc_emit": (C.c_int, [P, I32, I32, I32, C.c_double, P, P, P, P]),
@@ -246,6 +250,8 @@ SIGNATURES = {
     "svr_write_obj": (C.c_int, [C.c_char_p, P, I64, P, I64]),
     "svr_write_ply": (C.c_int, [C.c_char_p, P, P, I64, P, I64]),
     "svr_write_png_gray8": (C.c_int, [C.c_char_p, P, I32, I32]),
+    "svr_write_png_rgb8": (C.c_int, [C.c_char_p, P, I32, I32]),
+    "svr_write_obj_normals": (C.c_int, [C.c_char_p, P, P, I64, P, I64]),
     "svr_write_obj_points": (C.c_int, [C.c_char_p, P, I64]),
     "svr_df_dims": (C.c_int, [C.c_char_p, P]),
     "svr_df_read": (C.c_int, [C.c_char_p, P, I64]),

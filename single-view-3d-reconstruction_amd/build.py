@@ -40,6 +40,8 @@ SOURCES = {
     "mesh_components.hip": ["-ffp-contract=off"],
     "mesh_simplify.hip": ["-ffp-contract=off"],
     "mesh_smooth.hip": ["-ffp-contract=off"],
+    "mesh_normals.hip": ["-ffp-contract=off"],
+    "mesh_shade.hip": ["-ffp-contract=off"],
     "sample_io.hip": [],
     "io_npz.cpp": [],
     "io_df.cpp": [],

@@ -1,5 +1,6 @@
 // Mesh file writers (plain C++): the indexed .obj behind implicit_to_mesh / visualize_sdf (the reference's export_obj,
-// util/visualize.py:23-25), the point-list .obj of visualize_point_list (:14-20) and the binary PLY with vertex colours.
+// util/visualize.py:23-25) and its form with `vn` lines, the point-list .obj of visualize_point_list (:14-20) and the binary PLY
+// with vertex colours.
 // Built with -ffp-contract=off: svr_write_obj_points adds 0.5 in float32, one rounding per operation.
 #include "io_bytes.h"
 #include <charconv>
@@ -7,41 +8,64 @@
 
 using namespace svr;
 
-extern "C" int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf) {
-  SVR_CHECK(path && nv >= 0 && nf >= 0 && (verts || nv == 0) && (faces || nf == 0), SVR_E_BADARG, "write_obj: bad argument");
+// `v` lines, with `normals` one `vn` line per vertex after them, then the faces: `f a b c`, or `f a//a b//b c//c` with normals
+static int write_obj(const char *what, const char *path, const float *verts, const float *normals, int64_t nv, const int32_t *faces,
+                     int64_t nf) {
   OutFile out(path);
-  SVR_CHECK(out.f, SVR_E_IO, "write_obj: cannot open %s", path);
+  SVR_CHECK(out.f, SVR_E_IO, "%s: cannot open %s", what, path);
   std::vector<char> buf(1 << 20);
   size_t used = 0;
   auto flush = [&]() { out.write(buf.data(), 1, used); used = 0; };
   // %.9g: every float32 reads back exactly, also through a float64 parse and a cast
-  for (int64_t i = 0; i < nv; ++i) {
-    if (used + 64 > buf.size()) flush();
-    char *c = buf.data() + used;
-    char *end = buf.data() + buf.size();
-    *c++ = 'v';
-    for (int a = 0; a < 3; ++a) {
-      *c++ = ' ';
-      c = std::to_chars(c, end, verts[i * 3 + a], std::chars_format::general, 9).ptr;
+  auto rows = [&](const float *data, const char *tag) {
+    for (int64_t i = 0; i < nv; ++i) {
+      if (used + 64 > buf.size()) flush();
+      char *c = buf.data() + used;
+      char *end = buf.data() + buf.size();
+      for (const char *t = tag; *t; ++t) *c++ = *t;
+      for (int a = 0; a < 3; ++a) {
+        *c++ = ' ';
+        c = std::to_chars(c, end, data[i * 3 + a], std::chars_format::general, 9).ptr;
+      }
+      *c++ = '\n';
+      used = c - buf.data();
     }
-    *c++ = '\n';
-    used = c - buf.data();
-  }
+  };
+  rows(verts, "v");
+  if (normals) rows(normals, "vn");
   for (int64_t i = 0; i < nf; ++i) {
-    if (used + 48 > buf.size()) flush();
+    if (used + 96 > buf.size()) flush();
     char *c = buf.data() + used;
     char *end = buf.data() + buf.size();
     *c++ = 'f';
     for (int a = 0; a < 3; ++a) {
       *c++ = ' ';
       c = std::to_chars(c, end, (int64_t)faces[i * 3 + a] + 1).ptr;
+      if (normals) {
+        *c++ = '/';
+        *c++ = '/';
+        c = std::to_chars(c, end, (int64_t)faces[i * 3 + a] + 1).ptr;
+      }
     }
     *c++ = '\n';
     used = c - buf.data();
   }
   flush();
-  SVR_CHECK(out.close(), SVR_E_IO, "write_obj: write to %s failed", path);
+  SVR_CHECK(out.close(), SVR_E_IO, "%s: write to %s failed", what, path);
   return SVR_OK;
+}
+
+extern "C" int svr_write_obj(const char *path, const float *verts, int64_t nv, const int32_t *faces, int64_t nf) {
+  SVR_CHECK(path && nv >= 0 && nf >= 0 && (verts || nv == 0) && (faces || nf == 0), SVR_E_BADARG, "write_obj: bad argument");
+  return write_obj("write_obj", path, verts, nullptr, nv, faces, nf);
+}
+
+extern "C" int svr_write_obj_normals(const char *path, const float *verts, const float *normals, int64_t nv, const int32_t *faces,
+                                     int64_t nf) {
+  SVR_CHECK(path && nv >= 0 && nf >= 0 && ((verts && normals) || nv == 0) && (faces || nf == 0), SVR_E_BADARG,
+            "write_obj_normals: bad argument");
+  static const float none = 0.0f;                  // nv == 0: a non-null pointer that is never read selects the `//` form
+  return write_obj("write_obj_normals", path, verts, normals ? normals : &none, nv, faces, nf);
 }
 
 extern "C" int svr_write_obj_points(const char *path, const float *pts, int64_t n) {

@@ -1,5 +1,6 @@
-// 8-bit grayscale .png writer (plain C++ + zlib) behind visualize_depthmap (the reference goes through PIL,
-// util/visualize.py:28-49): signature, IHDR, one deflated IDAT with filter type 0 on every scanline, IEND.
+// 8-bit .png writers (plain C++ + zlib): grayscale behind visualize_depthmap (the reference goes through PIL,
+// util/visualize.py:28-49) and RGB behind the mesh previews (util/mesh_render.py): signature, IHDR, one deflated IDAT with
+// filter type 0 on every scanline, IEND.
 #include "io_bytes.h"
 #include <zlib.h>
 #include <vector>
@@ -19,33 +20,43 @@ static void write_chunk(OutFile &out, const char *type, const unsigned char *dat
   out.write(tail, 1, 4);
 }
 
-extern "C" int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W) {
-  SVR_CHECK(path && data, SVR_E_BADARG, "write_png_gray8: null pointer");
-  SVR_CHECK(H > 0 && W > 0 && ((int64_t)W + 1) * H < (1LL << 30), SVR_E_BADSHAPE, "write_png_gray8: image %d x %d", H, W);
+// `channels` bytes per pixel: 1 = colour type 0 (grayscale), 3 = colour type 2 (RGB); `what` names the entry point in messages
+static int write_png8(const char *what, const char *path, const uint8_t *data, int32_t H, int32_t W, int channels) {
+  SVR_CHECK(path && data, SVR_E_BADARG, "%s: null pointer", what);
+  SVR_CHECK(H > 0 && W > 0 && ((int64_t)W * channels + 1) * H < (1LL << 30), SVR_E_BADSHAPE, "%s: image %d x %d", what, H, W);
   // scanlines, each behind its filter-type byte 0 (None)
-  std::vector<unsigned char> raw((size_t)(W + 1) * H);
+  const size_t line = (size_t)W * channels;
+  std::vector<unsigned char> raw((line + 1) * H);
   for (int r = 0; r < H; ++r) {
-    raw[(size_t)r * (W + 1)] = 0;
-    memcpy(&raw[(size_t)r * (W + 1) + 1], data + (size_t)r * W, (size_t)W);
+    raw[(size_t)r * (line + 1)] = 0;
+    memcpy(&raw[(size_t)r * (line + 1) + 1], data + (size_t)r * line, line);
   }
   uLongf zlen = compressBound((uLong)raw.size());
   std::vector<unsigned char> z(zlen);
-  SVR_CHECK(compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) == Z_OK, SVR_E_IO, "write_png_gray8: deflate failed");
+  SVR_CHECK(compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) == Z_OK, SVR_E_IO, "%s: deflate failed", what);
   OutFile out(path);
-  SVR_CHECK(out.f, SVR_E_IO, "write_png_gray8: cannot open %s", path);
+  SVR_CHECK(out.f, SVR_E_IO, "%s: cannot open %s", what, path);
   static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
   unsigned char ihdr[13];
   wr_be32(ihdr, (uint32_t)W);
   wr_be32(ihdr + 4, (uint32_t)H);
-  ihdr[8] = 8;   // bit depth
-  ihdr[9] = 0;   // colour type: grayscale
-  ihdr[10] = 0;  // compression: deflate
-  ihdr[11] = 0;  // filter method 0
-  ihdr[12] = 0;  // no interlace
+  ihdr[8] = 8;                        // bit depth
+  ihdr[9] = channels == 3 ? 2 : 0;    // colour type: RGB or grayscale
+  ihdr[10] = 0;                       // compression: deflate
+  ihdr[11] = 0;                       // filter method 0
+  ihdr[12] = 0;                       // no interlace
   out.write(sig, 1, 8);
   write_chunk(out, "IHDR", ihdr, 13);
   write_chunk(out, "IDAT", z.data(), (uint32_t)zlen);
   write_chunk(out, "IEND", nullptr, 0);
-  SVR_CHECK(out.close(), SVR_E_IO, "write_png_gray8: write to %s failed", path);
+  SVR_CHECK(out.close(), SVR_E_IO, "%s: write to %s failed", what, path);
   return SVR_OK;
+}
+
+extern "C" int svr_write_png_gray8(const char *path, const uint8_t *data, int32_t H, int32_t W) {
+  return write_png8("write_png_gray8", path, data, H, W, 1);
+}
+
+extern "C" int svr_write_png_rgb8(const char *path, const uint8_t *data, int32_t H, int32_t W) {
+  return write_png8("write_png_rgb8", path, data, H, W, 3);
 }

@@ -57,13 +57,22 @@ def view_consts(intrinsic=None, scale_factor=1, consts=None):
     return np.asarray(_grid_consts(K, scale_factor), dtype=np.float32)
 
 
+def view_triangles(mesh, transform=None):
+    """The (F, 9) float64 HOST table of the mesh as the camera sees it (``transformed``, then mesh_to_df.triangle_table and
+    its checks): the one table the ray caster and whatever reads its face map afterwards (util.mesh_render) share."""
+    host_tri = triangle_table(transformed(mesh, transform))
+    if not np.isfinite(host_tri).all():
+        raise ValueError("render_depth: the transform sends a vertex to a non-finite position")
+    return host_tri
+
+
 def render_depth(mesh, intrinsic=None, scale_factor=1, size=DEFAULT_SIZE, near=0.0, far=None, miss=0.0, transform=None,
                  return_face=False, return_distance=False, return_normal=False, cull=True, list_budget_bytes=DEFAULT_LIST_BUDGET,
-                 stats=None, consts=None, tile=DEFAULT_TILE, return_shade=False):
+                 stats=None, consts=None, tile=DEFAULT_TILE, return_shade=False, return_tri=False):
     """-> depth (H, W) float32 on the device [, face (H, W) int32][, distance (H, W) float32][, normal (H, W, 3) float32]
-    [, shade (H, W) uint8], in this order, for the flags set: the depth in metres of the nearest face along every pixel's
-    ray (`miss` where there is none), the face, the ray length (what distance.exr holds), the unit normal turned towards the
-    camera, and the grey level of rgb.png.
+    [, shade (H, W) uint8][, tri (F, 9) float64], in this order, for the flags set: the depth in metres of the nearest face
+    along every pixel's ray (`miss` where there is none), the face, the ray length (what distance.exr holds), the unit normal
+    turned towards the camera, the grey level of rgb.png, and the device copy of ``view_triangles``' table that was cast.
 
     `mesh`: a path, a loaded mesh or a (V, F) pair in grid units; `transform`: a 4x4 float64 mesh -> grid affine applied
     first (see ``transformed``), so that one world-space mesh can be seen from several poses.  The camera: `intrinsic` (path
@@ -82,9 +91,7 @@ def render_depth(mesh, intrinsic=None, scale_factor=1, size=DEFAULT_SIZE, near=0
     if not near < far:
         raise ValueError(f"render_depth: near={near}, far={far}")
     k = view_consts(intrinsic, scale_factor, consts)
-    host_tri = triangle_table(transformed(mesh, transform))
-    if not np.isfinite(host_tri).all():
-        raise ValueError("render_depth: the transform sends a vertex to a non-finite position")
+    host_tri = view_triangles(mesh, transform)
     F = host_tri.shape[0]
     l = _lib.lib()
     kc = (C.c_float * 12)(*[float(v) for v in k])
@@ -126,7 +133,7 @@ def render_depth(mesh, intrinsic=None, scale_factor=1, size=DEFAULT_SIZE, near=0
                          list_mean=float(per.mean()), list_max=int(per.max()),
                          every_tile_faces=int((rects[:, 0] == -(1 << 30)).sum().item()),
                          largest_batch_bytes=max(int(host_off[b1] - host_off[b0]) * 4 for b0, b1 in batches))
-    out = [depth] + [t for t in (face, distance, normal, shade) if t is not None]
+    out = [depth] + [t for t in (face, distance, normal, shade, tri if return_tri else None) if t is not None]
     return out[0] if len(out) == 1 else tuple(out)
 
 

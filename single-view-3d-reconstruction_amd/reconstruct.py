@@ -33,8 +33,9 @@ uint8 and `color_state` (V,) uint8 (util/mesh_color.py).  
 ``python -m svr_amd.reconstruct --checkpoint C (--rgb a.png [b.png ...] | --distance d.exr) --out DIR [--inf_res n]
 [--block s] [--space grid|normalized|camera] [--flip] [--color [--color_bias metres]] [--keep_largest]
 [--min_component_faces N] [--min_component_extent CELLS] [--drop_unseen] [--smooth ITERATIONS [--smooth_lambda L]
-[--smooth_mu M]] [--simplify CELLS]`` prints one line per view:
-the written paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour state.
+[--smooth_mu M]] [--simplify CELLS] [--normals] [--preview [K]] [--preview_size H W] [--preview_ssaa S]`` prints one line per
+view: the written paths, vertex and face counts and, with ``--color``, ``seen= spread= unreached=``, the vertices per colour
+state; with ``--preview``, ``previews=K`` at its end.
 
 ``clean(keep_largest=False, min_faces=0, min_extent=0.0, drop_unseen=False)`` drops connected components of the predicted
 mesh, the floaters an occupancy network leaves beside the surface (util/mesh_clean.py), and keeps
@@ -51,7 +52,17 @@ mesh that is written, so ``--drop_unseen`` still decides on the unsimplified mes
 ``smooth(iterations=10, lam=0.5, mu=-0.53, fix_boundary=True)`` moves the vertices by Taubin's lambda|mu iteration
 (util/mesh_smooth.py) and keeps `smooth_state`; faces, components, clusters and colours stay.  Nothing
 calls it by default.  ``--smooth ITERATIONS [--smooth_lambda L] [--smooth_mu M]`` runs it after the component flags and before
-``--simplify``, so the clusters average smoothed positions."""
+``--simplify``, so the clusters average smoothed positions.
+
+``normals()`` computes area-weighted vertex normals (util/mesh_render.py) and keeps `vertex_normals` and
+`normal_state`; ``render(yaw=0, pitch=0, dolly=0, size=None, ssaa=2, color=None, shading="smooth")`` returns a shaded
+(H, W, 3) uint8 picture of the mesh from the input camera, or with the mesh turned in front of it; ``clean()``,
+``simplify()`` and ``smooth()`` forget the normals.  ``save(prefix, normals=True)`` writes `vn` lines into
+``<prefix>_predicted.obj``; ``save(prefix, preview=k)`` writes ``<prefix>_preview.png`` (the input camera; key "preview") and
+``<prefix>_preview_1.png`` ... ``_preview_{k-1}.png`` (yaws spread evenly over +-30 degrees at pitch 10 degrees).  Nothing
+calls them by default, and without them every file is byte for byte what it was.  ``--normals`` and ``--preview [K]`` (K = 1
+when given without a number; ``--preview_size H W``, ``--preview_ssaa S``) do the same from the command line, on the mesh that
+is written, with its colours when ``--color`` is set."""
 import argparse
 import os
 from pathlib import Path
@@ -65,7 +76,7 @@ from .data_processing import sample_io
 from .data_processing.distance_to_depth import FromDistanceToDepth, get_intrinsic
 from .model.ifnet import implicit_to_vertices
 from .util.mesh_color import DEFAULT_FILL, IDENTITY_MAP, vertex_colors
-from .util.visualize import export_obj, export_ply, visualize_depthmap, visualize_grid
+from .util.visualize import export_obj, export_ply, save_png, visualize_depthmap, visualize_grid
 
 SPACES = ("grid", "normalized", "camera")
 
@@ -85,6 +96,7 @@ class Reconstruction:
         self.components = self.kept = None              # clean()'s: the statistics before the filter, the flag per component
         self.vertex_cluster = None                      # simplify()'s: where each vertex of the mesh before it went
         self.smooth_state = None                        # smooth()'s: which vertices it moved
+        self.vertex_normals = self.normal_state = None  # normals()'s results
 
     def _camera_consts(self):
         K = self._intrinsic if self._intrinsic is not None else get_intrinsic()
@@ -103,6 +115,56 @@ class Reconstruction:
         v = self.vertices if self._inf_res == 1 else self.vertices / float(self._inf_res)
         as_host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)      # noqa: E731
         return render_depth((as_host(v), as_host(self.faces)), size=size, consts=consts, **kw)
+
+    def normals(self):
+        """Area-weighted unit normals of the predicted mesh's vertices (util.mesh_render.vertex_normals):
+        stores and returns `vertex_normals` (V, 3) float32 and `normal_state` (V,) uint8 (0 has a normal, 1 in no valid face or
+        a zero sum, 3 not usable) on the device.  They are those of the mesh as stored, in lattice index space, and follow the
+        faces' winding; ``clean()``, ``simplify()`` and ``smooth()`` forget them."""
+        from .util.mesh_render import vertex_normals
+        self.vertex_normals, self.normal_state = vertex_normals(self.vertices, self.faces)
+        return self.vertex_normals, self.normal_state
+
+    def normals_in(self, space):
+        """The stored normals (``normals()`` first when there are none) as the unit normals of ``vertices_in(space)``:
+        "grid" the stored tensor; "camera" and "normalized" scale the axes (by 1 / s00, 1 / s11, 1 / s22 and by 1 / dims), so
+        the normals go through util.mesh_render.transform_normals with that diagonal matrix -> a float32 numpy array."""
+        from .util.mesh_render import transform_normals
+        if self.vertex_normals is None:
+            self.normals()
+        if space == "grid":
+            return self.vertex_normals
+        if space == "normalized":
+            scale = np.round(self._scale_factor).astype(np.int64) / np.array([139, 104, 112], dtype=np.float64)
+        elif space == "camera":
+            scale = 1.0 / np.array([float(self._scale_shift[i]) for i in (0, 2, 4)], dtype=np.float64)
+        else:
+            raise ValueError(f"space must be one of {SPACES}, got {space!r}")
+        return transform_normals(self.vertex_normals.cpu().numpy(), np.diag(np.append(scale, 1.0)))
+
+    def render(self, yaw=0.0, pitch=0.0, dolly=0.0, size=None, ssaa=2, color=None, shading="smooth", **kw):
+        """A shaded picture of the predicted mesh (util.mesh_render.render_mesh; `kw` goes there: ambient, albedo, background,
+        tile, ...) -> (H, W, 3) uint8 on the device.  yaw = pitch = dolly = 0 is the input camera's view; otherwise the mesh
+        is turned in front of that camera by ``orbit_transform`` (`yaw`, `pitch` in degrees, `dolly` in grid cells along the
+        optical axis).  `size` defaults to the input depth map's.  `color`: None uses `colors` when they are stored, True
+        runs ``colorize()`` first when they are not, False shades the grey `albedo`; a (V, 3) uint8 array is used as given.
+        The vertices are divided by inf_res first, as ``render_depth`` does.  A mesh without faces gives an image of
+        `background`."""
+        from .util.mesh_render import orbit_transform, render_mesh
+        if size is None:
+            size = tuple(self.depth.shape[-2:]) if self.depth is not None else (240, 320)
+        if color is None or color is True:
+            if color is True and self.colors is None:
+                self.colorize()
+            colors = self.colors
+        else:
+            colors = None if color is False else color
+        consts = self._camera_consts()
+        v = self.vertices if self._inf_res == 1 else self.vertices / float(self._inf_res)
+        transform = None
+        if (yaw, pitch, dolly) != (0, 0, 0) and int(self.faces.shape[0]):
+            transform = orbit_transform(v, self.faces, yaw, pitch, dolly, consts=consts)
+        return render_mesh(v, self.faces, consts=consts, size=size, colors=colors, shading=shading, transform=transform, ssaa=ssaa, **kw)
 
     def vertices_in(self, space):
         """The predicted mesh's vertices in `space`: a device tensor ("grid", "camera") or a float32 numpy array ("normalized":
@@ -168,6 +230,7 @@ class Reconstruction:
             self.vertices, self.faces, mark, keep_largest=keep_largest, min_faces=min_faces,
             min_extent=float(min_extent) * self._inf_res, require_mark=bool(drop_unseen))
         self.vertices, self.faces = vertices, faces
+        self.vertex_normals = self.normal_state = None
         if self.colors is not None:
             self.colors, self.color_state = self.colors[index.long()], self.color_state[index.long()]
         return self
@@ -186,6 +249,7 @@ class Reconstruction:
         out = simplify_mesh(self.vertices, self.faces, float(cell) * self._inf_res)
         self.vertices, self.faces, self.vertex_cluster = out.vertices, out.faces, out.vertex_cluster
         self.colors = self.color_state = None
+        self.vertex_normals = self.normal_state = None
         return self
 
     def smooth(self, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True):
@@ -202,9 +266,17 @@ class Reconstruction:
             return self
         out = smooth_mesh(self.vertices, self.faces, iterations=iterations, lam=lam, mu=mu, fix_boundary=fix_boundary)
         self.vertices, self.smooth_state = out.vertices, out.state
+        self.vertex_normals = self.normal_state = None
         return self
 
-    def save(self, prefix, space="grid", color=False):
+    def save(self, prefix, space="grid", color=False, normals=False, preview=0, preview_size=None, preview_ssaa=2):
+        """Module docstring; `normals` writes `vn` lines into ``_predicted.obj`` (``normals_in(space)``); `preview` = k > 0 writes
+        k pictures of the mesh (``render``, at `preview_size`, default the depth map's, and `preview_ssaa`):
+        ``<prefix>_preview.png`` from the input camera (key "preview") and ``<prefix>_preview_1.png`` ...
+        ``_preview_{k-1}.png`` (keys "preview_1" ...) at pitch 10 degrees and the k - 1 yaws of
+        ``numpy.linspace(-30, 30, k - 1)``.  The defaults write what was always written."""
+        if isinstance(preview, bool) or int(preview) != preview or preview < 0:
+            raise ValueError(f"save: preview={preview!r} (need a number of pictures, 0 for none)")
         vertices = self.vertices_in(space)
         prefix = os.fspath(prefix)
         if os.path.dirname(prefix):
@@ -213,7 +285,7 @@ class Reconstruction:
                  "depthmap_png": prefix + "_depthmap.png", "depthmap_exr": prefix + "_depthmap.exr"}
         vox = self.voxel_occupancy
         visualize_grid(vox.reshape(vox.shape[-3:]), paths["voxelized"])
-        export_obj(vertices, self.faces, paths["predicted"])
+        export_obj(vertices, self.faces, paths["predicted"], normals=self.normals_in(space) if normals else None)
         visualize_depthmap(self.depth, prefix + "_depthmap", flip=True)
         if not os.path.exists(paths["voxelized"]):
             del paths["voxelized"]
@@ -222,6 +294,11 @@ class Reconstruction:
                 self.colorize()
             paths["predicted_ply"] = prefix + "_predicted.ply"
             export_ply(vertices, self.faces, self.colors, paths["predicted_ply"])
+        for i in range(int(preview)):
+            key = "preview" if i == 0 else f"preview_{i}"
+            paths[key] = prefix + "_" + key + ".png"
+            view = {} if i == 0 else {"yaw": float(np.linspace(-30.0, 30.0, int(preview) - 1)[i - 1]), "pitch": 10.0}
+            save_png(self.render(size=preview_size, ssaa=preview_ssaa, **view), paths[key])
         return paths
 
 
@@ -357,7 +434,17 @@ def main(argv=None):
                         help="Taubin lambda|mu smoothing of the mesh, ITERATIONS times, rims on the lattice border held (default: off)")
     parser.add_argument("--smooth_lambda", type=float, default=0.5, help="the shrinking step of --smooth, 0 < L <= 1")
     parser.add_argument("--smooth_mu", type=float, default=-0.53, help="the inflating step of --smooth, -1 <= M <= 0 (0: plain Laplacian)")
+    parser.add_argument("--normals", action="store_true", help="write vertex normals (vn lines) into <name>_predicted.obj")
+    parser.add_argument("--preview", type=int, nargs="?", const=1, default=None, metavar="K",
+                        help="write K shaded pictures of the mesh: <name>_preview.png from the input camera, the others from beside it "
+                             "(default when given: 1)")
+    parser.add_argument("--preview_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="size of the pictures (default: the depth map's)")
+    parser.add_argument("--preview_ssaa", type=int, default=2, metavar="S", help="sub-pixels per pixel and axis of the pictures, 1 to 4")
     args = parser.parse_args(argv)
+    if args.preview is not None and not args.preview > 0:
+        parser.error("--preview needs a positive number of pictures")
+    if args.preview_ssaa not in (1, 2, 3, 4):
+        parser.error("--preview_ssaa needs 1, 2, 3 or 4")
     if args.smooth is not None and not 0 < args.smooth <= 1024:
         parser.error("--smooth needs a positive number of iterations, 1024 at the most")
     if args.color and args.distance:
@@ -395,8 +482,10 @@ def main(argv=None):
             _, state = view.colorize(bias=args.color_bias)
             n = torch.bincount(state.long(), minlength=3).tolist()
             counts = f" seen={n[1]} spread={n[2]} unreached={n[0]}"
-        paths = view.save(Path(args.out) / name, space=args.space, color=args.color)
-        print(" ".join(paths.values()), f"vertices={view.vertices.shape[0]} faces={view.faces.shape[0]}" + counts + parts)
+        paths = view.save(Path(args.out) / name, space=args.space, color=args.color, normals=args.normals, preview=args.preview or 0,
+                          preview_size=args.preview_size, preview_ssaa=args.preview_ssaa)
+        shown = "" if args.preview is None else f" previews={args.preview}"
+        print(" ".join(paths.values()), f"vertices={view.vertices.shape[0]} faces={view.faces.shape[0]}" + counts + parts + shown)
     return 0
 
 

@@ -9,8 +9,10 @@ float32 rounding of `level`, can classify differently).  The comparison with `le
 in float64.  The mesh is in the field's index space (x along axis 0); the exact rules (inside = v < level, vertex and
 face order, outward winding, open surfaces at the lattice border) are in include/svr_hip.h and DESIGN.md section 9.
 
-``export_obj(vertices, faces, path)``: `v x y z` lines (%.9g: float32 round trip), then 1-based `f a b c` lines,
-written by the library's C++ host code.  ``visualize_sdf(sdf, output_path, level=0.75)``: the two together.
+``export_obj(vertices, faces, path, normals=None)``: `v x y z` lines (%.9g: float32 round trip), then 1-based `f a b c` lines,
+written by the library's C++ host code; with `normals` (V, 3) float32 (util.mesh_render.vertex_normals) `vn x y z` lines follow
+the `v` lines and the faces read `f a//a b//b c//c`.  ``visualize_sdf(sdf, output_path, level=0.75)``: the two together.
+``save_png(rgb, path)``: an (H, W, 3) uint8 image as an 8-bit RGB .png.
 ``export_ply(vertices, faces, colors, path)``: the same mesh with one uint8 RGB colour per vertex, as a binary PLY.
 
 The other functions of the reference's util/visualize.py (:10-20,28-49), which the scene trainer's validation / test
@@ -78,11 +80,24 @@ def _host(a, dtype):
     return np.ascontiguousarray(np.asarray(a), dtype=dtype)
 
 
-def export_obj(vertices, faces, path):
+def export_obj(vertices, faces, path, normals=None):
     v = _host(vertices, np.float32).reshape(-1, 3)
     f = _host(faces, np.int32).reshape(-1, 3)
+    if normals is not None:
+        n = _host(normals, np.float32).reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError(f"export_obj: {len(n)} normals for {len(v)} vertices")
+        check(_lib.lib().svr_write_obj_normals(os.fsencode(path), v.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p), len(v),
+                                               f.ctypes.data_as(C.c_void_p), len(f)), "write_obj_normals")
+        return
     check(_lib.lib().svr_write_obj(os.fsencode(path), v.ctypes.data_as(C.c_void_p), len(v), f.ctypes.data_as(C.c_void_p),
                                    len(f)), "write_obj")
+
+
+def save_png(rgb, path):
+    """An (H, W, 3) uint8 image (device tensor or numpy array) as an 8-bit RGB .png: util.mesh_render.save_png."""
+    from .mesh_render import save_png as write
+    write(rgb, path)
 
 
 def export_ply(vertices, faces, colors, path):
